@@ -9,6 +9,11 @@ One process per GPU.  A "step" = one pass of the reverse-process hot path over o
 Philox noise draw, UNetv2 forward (eps prediction), p_sample update, device-side step advance
 (rho_diffusion/diffusion/ddpm.py:195-218).  Sampling shards by independent samples: no data-path
 collective, weak scaling (per-GPU batch fixed).  Rank 0 prints ONE JSON line.
+
+A plain run times the headline leg only (the sampling step; --mode selects another).  --full adds everything
+else the line has carried: the DDIM and training legs, the roofline and per-kind figures, the use_checkpoint
+training leg and the CPU oracle baseline.  --dump-outputs DIR writes what the timed steps computed in their
+last step as DIR/<name>.npy (float32; see dump_array).
 """
 from __future__ import annotations
 
@@ -32,9 +37,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--mode", choices=["sample", "train", "ddim", "both"], default="both",
-                    help="sample: denoising steps/s; train: training samples/s; both (default): `value` is the denoising rate, "
-                         "the training rate rides along in the same JSON line")
+    ap.add_argument("--mode", choices=["sample", "train", "ddim", "both"], default=None,
+                    help="sample (default): denoising steps/s; train: training samples/s; both (default with --full): `value` is the "
+                         "denoising rate, the DDIM and training rates ride along in the same JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: --mode both by default, roofline / per-kind figures, the "
+                         "use_checkpoint training leg, the CPU oracle baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)")
     ap.add_argument("--train-steps", type=int, default=None, help="timed training steps in --mode both (default: --steps)")
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch (BASELINE configs[2]: 32)")
     ap.add_argument("--grid", type=int, default=64)
@@ -46,13 +56,17 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-checkpoint-leg", action="store_true", help="skip the short use_checkpoint=True training leg")
     ap.add_argument("--cpu-steps", type=int, default=2)
-    ap.add_argument("--dump-ops", default=None, help="write the per-launch profile (kind, shape, ms, TFLOP/s) to this file")
+    ap.add_argument("--dump-ops", default=None, help="write the per-launch profile (kind, shape, ms, TFLOP/s) to this file (--full)")
     ap.add_argument("--labels", action="store_true",
                     help="class-conditional backbone: num_classes=25, MultiEmbeddings(embedding_dim=4*mc) over the DeepGalaxy "
                          "parameter space, y [B, 4] (BASELINE configs[4]; needs --mc 32 for the reference's embedding_dim=128)")
     ap.add_argument("--config", choices=sorted(PRESETS), default=None,
                     help="BASELINE.json configuration preset (sets --dims/--grid/--mc/--batch/--dtype/--labels); default = c3")
     args = ap.parse_args()
+    if args.mode is None:
+        args.mode = "both" if args.full else "sample"
+    if args.dump_ops and not args.full:
+        ap.error("--dump-ops comes from the roofline pass: add --full")
     if args.config:
         for k, v in PRESETS[args.config].items():
             setattr(args, k, v)
@@ -317,6 +331,30 @@ def hbm_pipeline_kernels(fns):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 22          # per array (16 MB of float32)
+DUMP_MAX_BYTES = 64_000_000       # all arrays of one --dump-outputs directory (--full: 4 + 4 + 4 + 2 M elements at most)
+
+
+def dump_array(t, cap=DUMP_MAX_ELEMS):
+    """Host float32 copy of `t`; above `cap` elements, a fixed sample of `cap` of them (flattened, sorted indices drawn from a
+    seeded generator: the same positions for the same shape in every run)."""
+    t = t.detach()
+    if t.numel() > cap:
+        g = torch.Generator().manual_seed(20251016)
+        idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def launch_self(args) -> int:
     """`python bench.py --gpus N` with N > 1 and no launcher environment: this process becomes the launcher.  It starts N ranks
     of this same script (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set as torch.distributed.run would), relays rank 0's JSON
@@ -359,6 +397,8 @@ def main():
         torch.cuda.synchronize()
 
     results = {}
+    outputs = {}                # --dump-outputs: host copies taken right after each leg's timed steps
+    dump = args.dump_outputs is not None and rank == 0
     roofline = None
     ranks_counted = 1
     if world > 1:   # warm-up collective (cf. xpu.py:374-375), not part of the sampling data path; it also counts the ranks
@@ -408,11 +448,14 @@ def main():
         # labels are embedded once per chain (DDPM.reverse_process does the same through _preembed_conditions): the step gets [B, 4 mc]
         cc = ddpm._preembed_conditions(labels_for(B, device)) if args.labels else None
 
+        last_pred = {}
+
         def sample_step():
             ops.philox_normal(z, ddpm.noise_seed, 0, offset_dev=off_dev)
             pred = engine.forward(x_t, None, cc, t_scalar_dev=t_dev)
             ops.p_sample_step(x_t, pred, z, tables["coef"], t_dev)
             ops.step_advance(t_dev, off_dev, (n_elem + 3) // 4)
+            last_pred["eps"] = pred             # (under capture: the graph's output buffer, rewritten by every replay)
 
         step_fn, graphed = sample_step, False
         if not args.no_graph:
@@ -430,8 +473,11 @@ def main():
         dt, med = timed(step_fn, args.steps, args.warmup)
         assert torch.isfinite(x_t).all(), "non-finite state after the timed steps"
         results["sample"] = dict(dt=dt, steps=args.steps, graphed=graphed, median_ms=med, rank_ms=dict(rank_spread))
+        if dump:
+            outputs["sample_x"] = dump_array(x_t)                      # the state after the last timed step
+            outputs["sample_eps"] = dump_array(last_pred["eps"])       # its UNet eps prediction
         hbm_pipe = {}
-        if rank == 0 and not args.no_roofline:
+        if rank == 0 and args.full and not args.no_roofline:
             roofline = roofline_of(next(iter(engine._plans.values())), args)
             # the step's own HBM-regime kernels: bytes / HIP-event time against the 8 TB/s peak.  t_dev is parked at 500
             # (a mid-chain step: noise term on) and restored, so the state stays finite
@@ -468,7 +514,9 @@ def main():
         dt, med = timed(ddim_step, args.steps, args.warmup)
         assert torch.isfinite(xd).all(), "non-finite DDIM state after the timed steps"
         results["ddim"] = dict(dt=dt, steps=args.steps, median_ms=med)
-        if rank == 0 and not args.no_roofline:
+        if dump:
+            outputs["ddim_x"] = dump_array(xd)
+        if rank == 0 and args.full and not args.no_roofline:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             x0_hat = engine.forward(xd, None, ccd, t_scalar_dev=td)
             torch.cuda.synchronize()
@@ -501,7 +549,12 @@ def main():
         results["train"] = dict(dt=dt, steps=tsteps, loss=float(last["loss"].detach()), median_ms=med, rank_ms=dict(rank_spread),
                                 peak_mem_gb=round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 1),
                                 plan_gb=round(engine._last_train_plan.nbytes() / 2 ** 30, 1))
-        if rank == 0 and not args.no_roofline:
+        if dump:
+            outputs["train_loss"] = dump_array(last["loss"])
+            # the weights after the last optimizer step: the optimizer's flat fp32 arena (a fixed sample of it: see dump_array)
+            flat_ = [a_["flat"] for a_ in trainer.opt.build_arena()]
+            outputs["train_params"] = dump_array(flat_[0] if len(flat_) == 1 else torch.cat(flat_), cap=DUMP_MAX_ELEMS // 2)
+        if rank == 0 and args.full and not args.no_roofline:
             tp = engine._last_train_plan
             bprof = tp.profile(repeats=1, backward=True)
             fk, bk = by_kind(tp.profile(repeats=1)), by_kind(bprof)
@@ -573,7 +626,7 @@ def main():
                 "modelled_allreduce_finish_ms": [round(f_, 2) for f_ in fin],
                 "modelled_exposed_ms": round(max(0.0, (fin[-1] if fin else 0.0) - bwd_ms), 2)}
             del tp, bprof
-        if not args.no_checkpoint_leg:
+        if args.full and not args.no_checkpoint_leg:
             # the same step with use_checkpoint=True on every ResBlock (reference: layers.py:153-199, unet_v2.py:266-271): activated
             # conv inputs are re-materialised in backward instead of kept.  Reported beside the main training rate, never as `value`.
             from rho_diffusion_amd.models.unet_v2 import ResBlock
@@ -650,12 +703,14 @@ def main():
         out["training"]["roofline"]["hbm_kernels_GBps"] = results["train"].get("hbm_kernels_GBps", {})
         if results["train"].get("ddp_overlap"):
             out["training"]["ddp_overlap"] = results["train"]["ddp_overlap"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(kw, ddpm, args)
-    elif rank == 0 and world > 1:
+    elif rank == 0 and world > 1 and args.full:
         # the CPU oracle is timed by the N = 1 run only (the contract: rank 0 at N = 1); the multi-GPU line points at it
         out["cpu_baseline"] = {"value": None, "kind": "port", "sample": "see the N=1 line of this bench (python bench.py --gpus 1): "
                                "the CPU oracle is timed there, on rank 0's host cores"}
+    if dump:
+        write_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

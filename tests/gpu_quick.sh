@@ -1,11 +1,12 @@
 #!/bin/bash
 # usage: bash tests/gpu_quick.sh "<pytest -k expr>" <bench mode> <tag>
-mkdir -p gpurun_out
-timeout -k 10 900 python -m pytest tests -m gpu -q -p no:cacheprovider -x -k "$1" > gpurun_out/tq_$3.log 2>&1; tail -3 gpurun_out/tq_$3.log
-timeout -k 10 600 python bench.py --mode $2 --steps 5 --warmup 2 --train-steps 3 --no-cpu-baseline --dump-ops gpurun_out/ops_$3.txt > gpurun_out/bench_$3.log 2>&1; echo "bench exit $?" >> gpurun_out/bench_$3.log
+OUT=${RHO_RUN_OUT:-runs}      # logs and profiles (git-ignored)
+mkdir -p $OUT
+timeout -k 10 900 python -m pytest tests -m gpu -q -p no:cacheprovider -x -k "$1" > $OUT/tq_$3.log 2>&1; tail -3 $OUT/tq_$3.log
+timeout -k 10 600 python bench.py --full --mode $2 --steps 5 --warmup 2 --train-steps 3 --no-cpu-baseline --dump-ops $OUT/ops_$3.txt > $OUT/bench_$3.log 2>&1; echo "bench exit $?" >> $OUT/bench_$3.log
 python - <<PY
 import json,re
-t=open("gpurun_out/bench_$3.log").read()
+t=open("$OUT/bench_$3.log").read()
 m=re.search(r'^\{.*\}$', t, re.M)
 if m:
     j=json.loads(m.group(0))

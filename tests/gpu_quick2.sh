@@ -1,11 +1,12 @@
 #!/bin/bash
 # usage: bash tests/gpu_quick2.sh "<pytest -k expr>" "<bench args>" <tag>   (tests, then one bench line summarised)
-mkdir -p gpurun_out
-timeout -k 10 900 python -m pytest tests -m gpu -q -p no:cacheprovider -x -k "$1" > gpurun_out/q2_$3_tests.log 2>&1; echo "exit $?" >> gpurun_out/q2_$3_tests.log; tail -4 gpurun_out/q2_$3_tests.log
-timeout -k 10 600 python bench.py $2 --no-cpu-baseline --no-checkpoint-leg > gpurun_out/q2_$3_bench.log 2>&1; echo "bench exit $?" >> gpurun_out/q2_$3_bench.log
+OUT=${RHO_RUN_OUT:-runs}      # logs and profiles (git-ignored)
+mkdir -p $OUT
+timeout -k 10 900 python -m pytest tests -m gpu -q -p no:cacheprovider -x -k "$1" > $OUT/q2_$3_tests.log 2>&1; echo "exit $?" >> $OUT/q2_$3_tests.log; tail -4 $OUT/q2_$3_tests.log
+timeout -k 10 600 python bench.py --full $2 --no-cpu-baseline --no-checkpoint-leg > $OUT/q2_$3_bench.log 2>&1; echo "bench exit $?" >> $OUT/q2_$3_bench.log
 python - <<PY
 import json,re
-t=open("gpurun_out/q2_$3_bench.log").read()
+t=open("$OUT/q2_$3_bench.log").read()
 m=re.search(r'^\{.*\}$', t, re.M)
 if m:
     j=json.loads(m.group(0))

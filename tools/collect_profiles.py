@@ -1,10 +1,10 @@
-"""Copy the artefacts of tests/gpu_profile_all.sh <tag> (gpurun_out/) into profiles/ under the round's naming and print the headline numbers.
-usage: python tools/collect_profiles.py <tag>"""
+"""Copy the artefacts of tests/gpu_profile_all.sh <tag> ($RHO_RUN_OUT, default runs/) into profiles/ under the round's naming and print the
+headline numbers.  usage: python tools/collect_profiles.py <tag>"""
 import glob, json, os, re, shutil, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.path.join(ROOT, os.environ.get("RHO_RUN_OUT", "runs")), os.path.join(ROOT, "profiles")
 for cfg in ("c3", "c5", "c2", "c1"):
     t = tag if cfg == "c3" else f"{tag}_{cfg}"
     for kind, sub in (("both", f"prof_{t}"), ("sample", f"prof_{t}_sample")):
