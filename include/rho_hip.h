@@ -35,9 +35,9 @@ extern "C" {
 #define RHO_E_SHAPE (-3)    /* tile / shape constraint violated */
 
 /* ABI version: bumped on ANY signature / struct-layout change (2: table_len in rho_q_sample(_coef), fmt in rho_gn_bwd_finalize,
- * rho_conv_desc grew; 3: round-3 additions).  A loader must compare rho_abi_version() with the header it was written against
+ * rho_conv_desc grew; 3: round-3 additions; 9: the rho_gd_* / metrics entry points of csrc/gaussian.hip).  A loader must compare rho_abi_version() with the header it was written against
  * before calling anything else (hip.py does; a build with all symbols but older signatures would be called with shifted arguments). */
-#define RHO_ABI_VERSION 8
+#define RHO_ABI_VERSION 9
 int rho_abi_version(void);
 /* static string: target arch + build flags */
 const char* rho_build_info(void);
@@ -534,6 +534,90 @@ int rho_ddim_step(const float* x_t, const float* model_out, const float* quantil
 int rho_ddpm_sched_step(const float* x_t, const float* model_out, const float* noise, float* x_prev, float* pred_xstart,
                         int64_t n, int eps_mode, float sqrt_beta_prod, float sqrt_alpha_prod, float clip, float c0, float c1,
                         float sigma, void* stream);
+
+/* ---- GaussianDiffusionPipeline API beyond the fixed DDIM path (gaussian_diffusion.py:277-1009; csrc/gaussian.hip) --------
+ * Per-sample t: every entry point gathers rows of ONE packed float32 table tab[RHO_GD_ROWS][table_len] (the pipeline's float64
+ * tables cast to float32, as _extract_into_tensor does) at t[b] (int64 [batch] on the device).  A t[b] outside [0, table_len)
+ * sets *err_flag |= 4 (optional flag) and reads the clamped row, as rho_q_sample_coef.  Tensors: contiguous float32
+ * [batch, per_sample]; batch <= 65535.  mean_type: RHO_GD_START_X (x0-predicting model) or RHO_GD_EPSILON. */
+#define RHO_GD_SQRT_RECIP 0      /* sqrt(1/abar) */
+#define RHO_GD_SQRT_RECIPM1 1    /* sqrt(1/abar - 1) */
+#define RHO_GD_COEF1 2           /* posterior_mean_coef1 */
+#define RHO_GD_COEF2 3           /* posterior_mean_coef2 */
+#define RHO_GD_MODEL_VAR 4       /* model variance: FIXED_LARGE append(posterior_variance[1], betas[1:]) or FIXED_SMALL posterior_variance */
+#define RHO_GD_MODEL_LOGVAR 5    /* its log (FIXED_SMALL: posterior_log_variance_clipped) */
+#define RHO_GD_POST_LOGVAR 6     /* posterior_log_variance_clipped */
+#define RHO_GD_ABAR 7            /* alphas_cumprod */
+#define RHO_GD_ABAR_PREV 8
+#define RHO_GD_ABAR_NEXT 9
+#define RHO_GD_SQRT_ABAR 10
+#define RHO_GD_LOG_1M_ABAR 11    /* log(1 - abar) */
+#define RHO_GD_1M_ABAR 12        /* 1 - abar */
+#define RHO_GD_POST_VAR 13       /* posterior_variance */
+#define RHO_GD_ROWS 14
+#define RHO_GD_START_X 0
+#define RHO_GD_EPSILON 1
+
+/* Table-coefficient elementwise forms, a = tab[row_a][t_b], b = tab[row_b][t_b]:
+ *   op 0: out = a*x                q_mean_variance's mean (:277-292)
+ *   op 1: out = a*x + b*y          q_posterior_mean_variance's mean (:314-336)
+ *   op 2: out = a*x - b*y          _predict_xstart_from_eps (:445-450)
+ *   op 3: out = (a*x - y) / b      _predict_eps_from_xstart (:462-466)
+ * float32 in the reference's operation order, no contraction.  y is ignored by op 0. */
+int rho_gd_affine(const float* x, const float* y, float* out, const int64_t* t, const float* tab, int64_t table_len, int row_a,
+                  int row_b, int op, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);
+
+/* p_mean_variance (:338-443, START_X / EPSILON, fixed variances) + condition_mean (:473-486) + p_sample (:512-556), one pass:
+ *   x0 = START_X ? model_out : sqrt_recip*x_t - sqrt_recipm1*model_out;  quantile != NULL: s = max(q[b], 1), x0 = clamp(x0, -s, s)/s
+ *   out = coef1*x0 + coef2*x_t  (+ model_var*grad)  (+ ((t != 0) * exp(0.5*model_logvar)) * noise)
+ * grad, noise, quantile, pred_xstart may be NULL.  Without noise, out is p_mean_variance's "mean". */
+int rho_gd_posterior_step(const float* x_t, const float* model_out, const int64_t* t, const float* tab, int64_t table_len,
+                          int mean_type, const float* quantile, const float* grad, const float* noise, float* out,
+                          float* pred_xstart, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);
+
+/* ddim_sample (:654-702) with condition_score (:488-510) when grad != NULL, or (reverse = 1) ddim_reverse_sample (:704-740), per-sample t:
+ *   x0 as rho_gd_posterior_step;  grad: eps = (sr*x - x0)/srm1 - sqrt(1 - abar)*grad, x0 = sr*x - srm1*eps
+ *   eps = (sr*x - x0)/srm1
+ *   forward: sigma = eta*sqrt((1 - abar_prev)/(1 - abar))*sqrt(1 - abar/abar_prev)
+ *            sample = x0*sqrt(abar_prev) + sqrt(1 - abar_prev - sigma^2)*eps  (+ ((t != 0)*sigma)*noise; noise NULL = no noise term)
+ *   reverse: sample = x0*sqrt(abar_next) + sqrt(1 - abar_next)*eps   (eta 0, no grad, no noise)
+ * rho_ddim_step stays the batch-uniform form with host scalars. */
+int rho_gd_ddim_step(const float* x_t, const float* model_out, const int64_t* t, const float* tab, int64_t table_len,
+                     int mean_type, const float* quantile, const float* grad, const float* noise, float eta, int reverse,
+                     float* sample, float* pred_xstart, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);
+
+/* Scratch of the per-sample reductions (rho_gd_vlb_terms, rho_gd_mse_per_sample), bytes. */
+int64_t rho_gd_reduce_workspace_bytes(int64_t batch, int64_t per_sample);
+
+/* _vb_terms_bpd (:826-859) and the per-timestep statistics of calc_bpd_loop (:936-1009), fused; per sample b, written at b*out_stride:
+ *   vb = where(t == 0, mean(-discretized_gaussian_log_likelihood(x_start, model_mean, 0.5*model_logvar)),
+ *                      mean(normal_kl(true_mean, post_logvar, model_mean, model_logvar))) / ln 2
+ *   xstart_mse = mean((pred_xstart - x_start)^2),  mse = mean(((sr*x_t - pred_xstart)/srm1 - noise)^2)
+ * raw_kl / raw_nll [batch] (optional): both bpd terms.  prior = 1: _prior_bpd (:936-951), vb = mean(normal_kl(sqrt_abar*x_start,
+ * log(1-abar), 0, 0)) / ln 2 at t = table_len-1 (x_t, model_out, t, noise unused).  Two-stage fixed-order reduction (double partials,
+ * no atomics): bit-reproducible.  xstart_mse, mse, pred_xstart, quantile may be NULL; noise only when mse is NULL. */
+int rho_gd_vlb_terms(const float* x_start, const float* x_t, const float* model_out, const int64_t* t, const float* tab,
+                     int64_t table_len, int mean_type, const float* quantile, const float* noise, int prior, float* vb,
+                     float* xstart_mse, float* mse, int64_t out_stride, float* raw_kl, float* raw_nll, float* pred_xstart,
+                     void* workspace, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);
+
+/* training_losses' MSE term (:861-934): loss[b] = mean_flat((target - out)^2), fixed-order two-stage reduction; and its backward
+ * grad = -((g[b] / per_sample) * (2 * (target - out))). */
+int rho_gd_mse_per_sample(const float* target, const float* out, float* loss, void* workspace, int64_t batch, int64_t per_sample,
+                          void* stream);
+int rho_gd_mse_per_sample_bwd(const float* target, const float* out, const float* g, float* grad, int64_t batch, int64_t per_sample,
+                              void* stream);
+
+/* rho_diffusion/metrics/losses.py, float32 elementwise over [batch, per_sample].  Operand k has mode (modes >> 2k) & 3:
+ * 0 full tensor, 1 per-sample [batch], 2 the scalar argument s_* (its pointer may be NULL).
+ *   normal_kl (:28-53): 0.5*(-1 + lv2 - lv1 + exp(lv1 - lv2) + (m1 - m2)^2*exp(-lv2))
+ *   discretized_gaussian_log_likelihood (:64-93): tanh CDF approximation, clamps at 1e-12, where-branches at x < -0.999 / x > 0.999
+ *   approx_standard_normal_cdf (:56-61) */
+int rho_normal_kl(const float* mean1, const float* logvar1, const float* mean2, const float* logvar2, float s_mean1, float s_logvar1,
+                  float s_mean2, float s_logvar2, int modes, float* out, int64_t batch, int64_t per_sample, void* stream);
+int rho_discretized_gaussian_ll(const float* x, const float* means, const float* log_scales, float s_x, float s_means, float s_log_scales,
+                                int modes, float* out, int64_t batch, int64_t per_sample, void* stream);
+int rho_approx_normal_cdf(const float* x, float* out, int64_t n, void* stream);
 
 /* Channel sums of a channels-last tensor (conv bias gradients; additive-embedding gradients):
  * out_nc[n*nc_stride + c] (+)= sum_pos x[n,pos,c];  out_c[c] (+)= sum_n out_nc[n][c] (optional).

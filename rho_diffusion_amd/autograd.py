@@ -52,3 +52,23 @@ class MSELossFunction(torch.autograd.Function):
 
 def mse_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return MSELossFunction.apply(pred, target)
+
+
+class PerSampleMSEFunction(torch.autograd.Function):
+    """mean_flat((target - pred)^2) -> [N] (gaussian_diffusion.py:925, training_losses' "mse" term) with the fixed-order HIP reduction;
+    the backward applies the per-sample upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        pred, target = pred.contiguous().float(), target.contiguous().float()
+        ctx.save_for_backward(pred, target)
+        return ops.gd_mse_per_sample(target, pred)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target = ctx.saved_tensors
+        return ops.gd_mse_per_sample_bwd(target, pred, g.contiguous().float()), None
+
+
+def mse_per_sample(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    return PerSampleMSEFunction.apply(pred, target)

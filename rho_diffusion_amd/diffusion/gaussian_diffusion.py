@@ -15,9 +15,16 @@ The per-step scalars (four table entries) are kernel arguments computed on the h
 
 ``training_step`` (:1153-1210) reproduces the reference's objective as written: the data are noised twice with the same
 noise (:1186 then :877) and the backbone output is regressed on the once-noised data.
+
+The rest of the reference class's public API (guided-diffusion's) is built on csrc/gaussian.hip, for the mean types START_X /
+EPSILON and the fixed variances: the distribution helpers (:277-510), ancestral sampling (:512-652), the DDIM loop with eta and
+``cond_fn`` (:654-702, :742-824), DDIM inversion (:704-740), the variational bound in bits per dimension (:826-859, :936-1009)
+and ``training_losses`` (:861-934).  Every kernel gathers per-sample rows of one packed float32 table (``_gd_table``) at a
+device ``t[B]``; the loops never synchronise with the host and poll the error flag once at the end.
 """
 from __future__ import annotations
 
+import enum
 import math
 import os
 from typing import Any, Mapping, Union
@@ -27,12 +34,64 @@ import torch
 from torch import Tensor
 
 from .. import hip
+from .. import metrics  # noqa: F401  (rho_diffusion.metrics.losses resolves under install_alias, as the reference imports it here)
 from ..engine import ops
 from ..registry import registry
 from ..utils import sample_from_discrete_parameter_space, save_model_checkpoint
 from .abstract_diffusion import AbstractDiffusionPipeline
 
-__all__ = ["GaussianDiffusionPipeline", "get_named_beta_schedule", "betas_for_alpha_bar", "diffusion_tables", "ddim_coefficients"]
+__all__ = ["GaussianDiffusionPipeline", "get_named_beta_schedule", "betas_for_alpha_bar", "diffusion_tables", "ddim_coefficients",
+           "ModelMeanType", "ModelVarType", "LossType"]
+
+
+class ModelMeanType(enum.Enum):
+    """Which type of output the model predicts (:107-113)."""
+    PREVIOUS_X = enum.auto()  # the model predicts x_{t-1}
+    START_X = enum.auto()  # the model predicts x_0
+    EPSILON = enum.auto()  # the model predicts epsilon
+
+
+class ModelVarType(enum.Enum):
+    """What is used as the model's output variance (:116-127)."""
+    LEARNED = enum.auto()
+    FIXED_SMALL = enum.auto()
+    FIXED_LARGE = enum.auto()
+    LEARNED_RANGE = enum.auto()
+
+
+class LossType(enum.Enum):
+    """:130-141."""
+    MSE = enum.auto()  # use raw MSE loss (and KL when learning variances)
+    RESCALED_MSE = enum.auto()  # use raw MSE loss (with RESCALED_KL when learning variances)
+    KL = enum.auto()  # use the variational lower-bound
+    RESCALED_KL = enum.auto()  # like KL, but rescale to estimate the full VLB
+
+    def is_vb(self):
+        return self == LossType.KL or self == LossType.RESCALED_KL
+
+
+def model_variance_tables(tables: Mapping[str, np.ndarray], var_type: ModelVarType):
+    """float64 (variance, log_variance) of a fixed variance type (:385-398); the learned types are not built."""
+    if var_type == ModelVarType.FIXED_LARGE:
+        v = np.append(tables["posterior_variance"][1], tables["betas"][1:])
+        return v, np.log(v)
+    if var_type == ModelVarType.FIXED_SMALL:
+        return tables["posterior_variance"], tables["posterior_log_variance_clipped"]
+    raise NotImplementedError(f"model_var_type {var_type}: learned variances (gaussian_diffusion.py:368-383) need a 2C-channel "
+                              "backbone and are not built; use FIXED_LARGE or FIXED_SMALL")
+
+
+def gd_table_rows(tables: Mapping[str, np.ndarray], var_type: ModelVarType) -> np.ndarray:
+    """The packed float32 [RHO_GD_ROWS, T] table of csrc/gaussian.hip (row order ops.GD_ROWS): each float64 table cast to float32
+    as ``_extract_into_tensor`` (:91-105) casts it."""
+    var, logvar = model_variance_tables(tables, var_type)
+    ac = tables["alphas_cumprod"]
+    rows = {"sqrt_recip": tables["sqrt_recip_alphas_cumprod"], "sqrt_recipm1": tables["sqrt_recipm1_alphas_cumprod"],
+            "coef1": tables["posterior_mean_coef1"], "coef2": tables["posterior_mean_coef2"], "model_var": var, "model_logvar": logvar,
+            "post_logvar": tables["posterior_log_variance_clipped"], "abar": ac, "abar_prev": tables["alphas_cumprod_prev"],
+            "abar_next": tables["alphas_cumprod_next"], "sqrt_abar": tables["sqrt_alphas_cumprod"],
+            "log_1m_abar": tables["log_one_minus_alphas_cumprod"], "1m_abar": 1.0 - ac, "post_var": tables["posterior_variance"]}
+    return np.stack([np.asarray(rows[k], dtype=np.float64).astype(np.float32) for k in ops.GD_ROWS])
 
 
 def betas_for_alpha_bar(num_diffusion_timesteps: int, alpha_bar, max_beta: float = 0.999) -> np.ndarray:
@@ -107,6 +166,10 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         self.sample_parameter_space = sample_parameter_space
         self.save_weights_every_n_epochs = save_checkpoint_every_n_epochs
         self.rescale_timesteps = False
+        # the reference's fixed configuration (:199-233); users may set other supported values afterwards
+        self.loss_type = LossType.MSE
+        self.model_mean_type = ModelMeanType.START_X
+        self.model_var_type = ModelVarType.FIXED_LARGE
 
         # float64 tables (:237-273)
         self.tables = diffusion_tables(get_named_beta_schedule("cosine", int(timesteps)))
@@ -119,6 +182,9 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         self._noise_offset = 0
         self._dev_tables = {}
         self._quant_ws = None
+        self._gd_tables = {}
+        self._gd_err = None
+        self._gd_ws = None
 
     # ------------------------------------------------------------------ noise / q_sample
     def noise(self, data: Tensor) -> Tensor:
@@ -210,6 +276,398 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
             ops.step_advance(t_dev, None, 0)
         self._check_backbone_errors()
         return {"buffer": buf, "denoised": x_t}
+
+    # ------------------------------------------------------------------ guided-diffusion API (csrc/gaussian.hip)
+    def _mean_code(self) -> int:
+        if self.model_mean_type == ModelMeanType.START_X:
+            return ops.GD_START_X
+        if self.model_mean_type == ModelMeanType.EPSILON:
+            return ops.GD_EPSILON
+        if self.model_mean_type == ModelMeanType.PREVIOUS_X:
+            raise NotImplementedError("model_mean_type PREVIOUS_X (gaussian_diffusion.py:417-422, _predict_xstart_from_xprev :452-460) "
+                                      "is not built; use START_X or EPSILON")
+        raise NotImplementedError(self.model_mean_type)
+
+    def _gd_table(self, device) -> Tensor:
+        """Packed float32 [RHO_GD_ROWS, T] table for the current ``model_var_type`` on ``device``."""
+        key = (str(device), self.model_var_type)
+        if key not in self._gd_tables:
+            self._gd_tables[key] = torch.from_numpy(gd_table_rows(self.tables, self.model_var_type)).to(device).contiguous()
+        return self._gd_tables[key]
+
+    def _gd_flag(self, device) -> Tensor:
+        if self._gd_err is None or self._gd_err.device != torch.device(device):
+            self._gd_err = torch.zeros(1, dtype=torch.int32, device=device)
+        return self._gd_err
+
+    def _check_backbone_errors(self) -> None:
+        """The backbone's flag, then the timestep flag of the table gathers (bit 4): a t outside [0, T) raises IndexError like the
+        reference's table lookup (:91-105).  Polled only where the pipeline synchronises anyway."""
+        super()._check_backbone_errors()
+        if self._gd_err is not None:
+            v = int(self._gd_err.item())
+            if v & 4:
+                self._gd_err.zero_()
+                raise IndexError(f"GaussianDiffusionPipeline: a timestep is outside [0, {self.timesteps}) (gaussian_diffusion.py:91-105)")
+
+    def _gd_view(self, tab: Tensor, row: str, t: Tensor, shape) -> Tensor:
+        """``_extract_into_tensor`` (:91-105): the table row gathered at t, as an expanded [B, 1, ...] view.  An out-of-range t reads
+        the clamped row here too; the kernels of the same call flag it (IndexError at the next poll)."""
+        t = t.clamp(0, tab.shape[1] - 1)
+        return tab[ops.GD_ROW[row]][t].view(-1, *([1] * (len(shape) - 1))).expand(shape)
+
+    @staticmethod
+    def _gd_x(x: Tensor, name: str) -> Tensor:
+        hip.require_gpu(x, name)
+        return x.float().contiguous()
+
+    @staticmethod
+    def _gd_t(t, batch: int, device) -> Tensor:
+        if not torch.is_tensor(t):
+            t = torch.tensor(t)
+        t = t.reshape(-1).to(device=device, dtype=torch.int64).contiguous()
+        assert t.shape == (batch,), f"t must have shape ({batch},), got {tuple(t.shape)}"
+        return t
+
+    def _gd_model_kwargs(self, model_kwargs) -> dict:
+        kw = dict(model_kwargs or {})
+        if kw.get("y") is not None:
+            kw["y"] = self._preembed_conditions(kw["y"])
+        return kw
+
+    def _gd_model(self, model, x: Tensor, t: Tensor, kw: dict, t_dev: Tensor = None) -> Tensor:
+        """model(x, t, **model_kwargs) as a contiguous float32 tensor of x's shape.  The backbone inside a loop (batch-uniform t)
+        runs on the engine with the device-resident timestep ``t_dev``, as reverse_process does."""
+        if t_dev is not None and model is self.backbone and hasattr(model, "engine") and set(kw) <= {"y"}:
+            out = model.engine().forward(x, None, kw.get("y"), t_scalar_dev=t_dev)
+        else:
+            out = model(x, self._scale_timesteps(t), **kw)
+        if tuple(out.shape) != tuple(x.shape):
+            raise NotImplementedError(f"model output {tuple(out.shape)} for x {tuple(x.shape)}: a learned-variance (2C-channel) backbone "
+                                      "(gaussian_diffusion.py:368-383) is not built")
+        hip.require_gpu(out, "model output")
+        return out.float().contiguous()
+
+    def _scale_timesteps(self, t):
+        """:468-471."""
+        if self.rescale_timesteps:
+            return t.float() * (1000.0 / self.timesteps)
+        return t
+
+    def _quantile(self, x: Tensor) -> Tensor:
+        B = x.shape[0]
+        need = hip.lib().rho_abs_quantile_workspace_bytes(B)
+        if self._quant_ws is None or self._quant_ws.device != x.device or self._quant_ws.numel() * 4 < need:
+            self._quant_ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=x.device)
+        return ops.abs_quantile(x, self.dynamic_thresholding_percentile, workspace=self._quant_ws)
+
+    def _x0_source(self, x: Tensor, mo: Tensor, t: Tensor, tab: Tensor, clip_denoised: bool, denoised_fn):
+        """(source, mean code, quantile) for the step kernels: ``process_xstart`` (:400-415).  The model output goes to the kernel
+        as it is unless x0 must exist before the quantile or ``denoised_fn`` (EPSILON with thresholding, any denoised_fn): then x0
+        is materialised first and handed over as a START_X output."""
+        code = self._mean_code()
+        if denoised_fn is None:
+            if clip_denoised and code == ops.GD_EPSILON:
+                mo = ops.gd_affine(x, mo, t, tab, "sqrt_recip", "sqrt_recipm1", "ax-by", err_flag=self._gd_flag(x.device))
+                code = ops.GD_START_X
+            return mo, code, (self._quantile(mo) if clip_denoised else None)
+        if code == ops.GD_EPSILON:
+            mo = ops.gd_affine(x, mo, t, tab, "sqrt_recip", "sqrt_recipm1", "ax-by", err_flag=self._gd_flag(x.device))
+        x0 = self._gd_x(denoised_fn(mo), "denoised_fn output")
+        return x0, ops.GD_START_X, (self._quantile(x0) if clip_denoised else None)
+
+    def _cond_grad(self, cond_fn, x: Tensor, t: Tensor, model_kwargs) -> Tensor:
+        g = cond_fn(x, self._scale_timesteps(t), **(model_kwargs or {}))
+        return self._gd_x(g, "cond_fn output")
+
+    # ---- distribution helpers
+    def q_mean_variance(self, x_start: Tensor, t: Tensor):
+        """:277-292: (mean, variance, log_variance) of q(x_t | x_0)."""
+        x = self._gd_x(x_start, "x_start")
+        t = self._gd_t(t, x.shape[0], x.device)
+        tab = self._gd_table(x.device)
+        mean = ops.gd_affine(x, None, t, tab, "sqrt_abar", None, "ax", err_flag=self._gd_flag(x.device))
+        return mean, self._gd_view(tab, "1m_abar", t, x.shape), self._gd_view(tab, "log_1m_abar", t, x.shape)
+
+    def q_posterior_mean_variance(self, x_start: Tensor, x_t: Tensor, t: Tensor):
+        """:314-336: (mean, variance, log_variance_clipped) of q(x_{t-1} | x_t, x_0)."""
+        assert x_start.shape == x_t.shape
+        xs, xt = self._gd_x(x_start, "x_start"), self._gd_x(x_t, "x_t")
+        t = self._gd_t(t, xs.shape[0], xs.device)
+        tab = self._gd_table(xs.device)
+        mean = ops.gd_affine(xs, xt, t, tab, "coef1", "coef2", "ax+by", err_flag=self._gd_flag(xs.device))
+        return mean, self._gd_view(tab, "post_var", t, xs.shape), self._gd_view(tab, "post_logvar", t, xs.shape)
+
+    def _predict_xstart_from_eps(self, x_t: Tensor, t: Tensor, eps: Tensor) -> Tensor:
+        """:445-450."""
+        assert x_t.shape == eps.shape
+        x = self._gd_x(x_t, "x_t")
+        t = self._gd_t(t, x.shape[0], x.device)
+        return ops.gd_affine(x, self._gd_x(eps, "eps"), t, self._gd_table(x.device), "sqrt_recip", "sqrt_recipm1", "ax-by",
+                             err_flag=self._gd_flag(x.device))
+
+    def _predict_eps_from_xstart(self, x_t: Tensor, t: Tensor, pred_xstart: Tensor) -> Tensor:
+        """:462-466."""
+        x = self._gd_x(x_t, "x_t")
+        t = self._gd_t(t, x.shape[0], x.device)
+        return ops.gd_affine(x, self._gd_x(pred_xstart, "pred_xstart"), t, self._gd_table(x.device), "sqrt_recip", "sqrt_recipm1",
+                             "(ax-y)/b", err_flag=self._gd_flag(x.device))
+
+    def p_mean_variance(self, model, x: Tensor, t: Tensor, clip_denoised: bool = True, denoised_fn=None, model_kwargs=None) -> dict:
+        """:338-443 (START_X / EPSILON, FIXED_LARGE / FIXED_SMALL).  ``clip_denoised`` is the reference's dynamic thresholding
+        (per-sample 0.9-quantile of |x0|, s = max(q, 1), clamp and divide), applied after ``denoised_fn``."""
+        x = self._gd_x(x, "x")
+        B = x.shape[0]
+        t = self._gd_t(t, B, x.device)
+        tab = self._gd_table(x.device)
+        mo = self._gd_model(model, x, t, self._gd_model_kwargs(model_kwargs))
+        src, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
+        mean, px = torch.empty_like(x), torch.empty_like(x)
+        ops.gd_posterior_step(x, src, t, tab, code, q, None, None, mean, px, err_flag=self._gd_flag(x.device))
+        return {"mean": mean, "variance": self._gd_view(tab, "model_var", t, x.shape),
+                "log_variance": self._gd_view(tab, "model_logvar", t, x.shape), "pred_xstart": px}
+
+    def condition_mean(self, cond_fn, p_mean_var: dict, x: Tensor, t: Tensor, model_kwargs=None) -> Tensor:
+        """:473-486: mean + variance * cond_fn(x, t).  The mean is re-derived from ``p_mean_var["pred_xstart"]`` in the same pass
+        (bit-equal to the "mean" p_mean_variance returns for it)."""
+        x = self._gd_x(x, "x")
+        t = self._gd_t(t, x.shape[0], x.device)
+        tab = self._gd_table(x.device)
+        g = self._cond_grad(cond_fn, x, t, model_kwargs)
+        out = torch.empty_like(x)
+        ops.gd_posterior_step(x, self._gd_x(p_mean_var["pred_xstart"], "pred_xstart"), t, tab, ops.GD_START_X, None, g, None, out, None,
+                              err_flag=self._gd_flag(x.device))
+        return out
+
+    def condition_score(self, cond_fn, p_mean_var: dict, x: Tensor, t: Tensor, model_kwargs=None) -> dict:
+        """:488-510: eps = eps(pred_xstart) - sqrt(1 - abar) * cond_fn(x, t); pred_xstart and mean re-derived from it."""
+        x = self._gd_x(x, "x")
+        t = self._gd_t(t, x.shape[0], x.device)
+        tab = self._gd_table(x.device)
+        g = self._cond_grad(cond_fn, x, t, model_kwargs)
+        px, scratch = torch.empty_like(x), torch.empty_like(x)
+        flag = self._gd_flag(x.device)
+        ops.gd_ddim_step(x, self._gd_x(p_mean_var["pred_xstart"], "pred_xstart"), t, tab, ops.GD_START_X, None, g, None, 0.0, False,
+                         scratch, px, err_flag=flag)
+        out = dict(p_mean_var)
+        out["pred_xstart"] = px
+        out["mean"] = ops.gd_affine(px, x, t, tab, "coef1", "coef2", "ax+by", out=scratch, err_flag=flag)
+        return out
+
+    # ---- ancestral sampling
+    def _p_step(self, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, kw, sample, px, t_dev=None) -> dict:
+        tab = self._gd_table(x.device)
+        mo = self._gd_model(model, x, t, kw, t_dev)
+        src, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
+        noise = self.noise(x)                                                  # :545, drawn before cond_fn runs
+        g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
+        ops.gd_posterior_step(x, src, t, tab, code, q, g, noise, sample, px, err_flag=self._gd_flag(x.device))
+        return {"sample": sample, "pred_xstart": px}
+
+    @torch.no_grad()
+    def p_sample(self, model, x: Tensor, t: Tensor, clip_denoised: bool = True, denoised_fn=None, cond_fn=None, model_kwargs=None) -> dict:
+        """:512-556: one ancestral step x_t -> x_{t-1} (no noise where t == 0)."""
+        x = self._gd_x(x, "x")
+        t = self._gd_t(t, x.shape[0], x.device)
+        return self._p_step(model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, self._gd_model_kwargs(model_kwargs),
+                            torch.empty_like(x), torch.empty_like(x))
+
+    def _loop_device(self, model, device):
+        if device is not None:
+            return torch.device(device)
+        params = model.parameters() if hasattr(model, "parameters") else self.backbone.parameters()
+        return next(params).device
+
+    def _loop(self, step, model, shape, noise, device, progress, fresh: bool):
+        """Shared body of the sampling loops: start from ``noise`` or ``self.noise`` (:620-623), run t = T-1 .. 0 on device-resident
+        timesteps, no host synchronisation; one error poll after the last step."""
+        assert isinstance(shape, (tuple, list))
+        dev = self._loop_device(model, device)
+        if noise is not None:
+            img = self._gd_x(noise, "noise")
+        else:
+            img = self.noise(torch.empty(tuple(shape), dtype=torch.float32, device=dev))
+        T = self.timesteps
+        ts = torch.arange(T - 1, -1, -1, dtype=torch.int64, device=dev).view(T, 1).expand(T, img.shape[0]).contiguous()
+        t_dev = torch.full((1,), T - 1, dtype=torch.int32, device=dev)
+        bufs = None if fresh else (torch.empty_like(img), torch.empty_like(img), torch.empty_like(img))
+        indices = range(T)
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        for j in indices:
+            if fresh:
+                sample, px = torch.empty_like(img), torch.empty_like(img)
+            else:
+                sample, px = bufs[j % 2], bufs[2]
+            out = step(img, ts[j], sample, px, t_dev)
+            ops.step_advance(t_dev, None, 0)
+            yield out
+            img = out["sample"]
+        self._check_backbone_errors()
+
+    @torch.no_grad()
+    def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, device=None,
+                      progress=False) -> Tensor:
+        """:558-602."""
+        final = None
+        for final in self._p_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, fresh=False):
+            pass
+        return final["sample"]
+
+    def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                                  device=None, progress=False):
+        """:604-652: yields p_sample's dict at every timestep (fresh tensors)."""
+        yield from self._p_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, fresh=True)
+
+    def _p_loop(self, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, fresh):
+        kw = self._gd_model_kwargs(model_kwargs)
+
+        def step(x, t, sample, px, t_dev):
+            return self._p_step(model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, kw, sample, px, t_dev)
+        with torch.no_grad():
+            yield from self._loop(step, model, shape, noise, device, progress, fresh)
+
+    # ---- DDIM
+    def _ddim_step(self, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, kw, eta, reverse, sample, px, t_dev=None) -> dict:
+        tab = self._gd_table(x.device)
+        mo = self._gd_model(model, x, t, kw, t_dev)
+        src, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
+        g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
+        # :685: the reference draws the noise at every step; with eta = 0 it is multiplied by 0 and no used draw follows it
+        noise = self.noise(x) if (not reverse and eta != 0.0) else None
+        ops.gd_ddim_step(x, src, t, tab, code, q, g, noise, eta, reverse, sample, px, err_flag=self._gd_flag(x.device))
+        return {"sample": sample, "pred_xstart": px}
+
+    @torch.no_grad()
+    def ddim_sample(self, model, x: Tensor, t: Tensor, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                    eta=0.0) -> dict:
+        """:654-702: one DDIM step with ``eta`` (sigma :687-691); ``cond_fn`` through condition_score."""
+        x = self._gd_x(x, "x")
+        t = self._gd_t(t, x.shape[0], x.device)
+        return self._ddim_step(model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, self._gd_model_kwargs(model_kwargs),
+                               float(eta), False, torch.empty_like(x), torch.empty_like(x))
+
+    @torch.no_grad()
+    def ddim_reverse_sample(self, model, x: Tensor, t: Tensor, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0) -> dict:
+        """:704-740: x_t -> x_{t+1} along the deterministic DDIM path (alphas_cumprod_next)."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        x = self._gd_x(x, "x")
+        t = self._gd_t(t, x.shape[0], x.device)
+        return self._ddim_step(model, x, t, clip_denoised, denoised_fn, None, model_kwargs, self._gd_model_kwargs(model_kwargs), 0.0, True,
+                               torch.empty_like(x), torch.empty_like(x))
+
+    @torch.no_grad()
+    def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                         device=None, progress=False, eta=0.0) -> Tensor:
+        """:742-775."""
+        final = None
+        for final in self._ddim_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, eta,
+                                     fresh=False):
+            pass
+        return final["sample"]
+
+    def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                     model_kwargs=None, device=None, progress=False, eta=0.0):
+        """:777-824: yields ddim_sample's dict at every timestep (fresh tensors)."""
+        yield from self._ddim_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, eta, fresh=True)
+
+    def _ddim_loop(self, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, eta, fresh):
+        kw = self._gd_model_kwargs(model_kwargs)
+
+        def step(x, t, sample, px, t_dev):
+            return self._ddim_step(model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, kw, float(eta), False, sample, px, t_dev)
+        with torch.no_grad():
+            yield from self._loop(step, model, shape, noise, device, progress, fresh)
+
+    # ---- variational bound
+    def _vb_step(self, model, x_start, x_t, t, clip_denoised, kw, vb, xstart_mse=None, mse=None, noise=None, raw_kl=None, raw_nll=None,
+                 px=None, t_dev=None):
+        tab = self._gd_table(x_start.device)
+        mo = self._gd_model(model, x_t, t, kw, t_dev)
+        src, code, q = self._x0_source(x_t, mo, t, tab, clip_denoised, None)
+        self._gd_ws = ops.gd_workspace(x_start.shape[0], x_start.numel() // x_start.shape[0], x_start.device, self._gd_ws)
+        ops.gd_vlb_terms(x_start, x_t, src, t, tab, code, q, noise, vb, xstart_mse, mse, raw_kl, raw_nll, px, workspace=self._gd_ws,
+                         err_flag=self._gd_flag(x_start.device))
+
+    @torch.no_grad()
+    def _vb_terms_bpd(self, model, x_start: Tensor, x_t: Tensor, t: Tensor, clip_denoised=True, model_kwargs=None) -> dict:
+        """:826-859: {"output": [N] decoder NLL (t == 0) or KL(q(x_{t-1}|x_t,x_0) || p(x_{t-1}|x_t)) in bits, "pred_xstart"}."""
+        xs, xt = self._gd_x(x_start, "x_start"), self._gd_x(x_t, "x_t")
+        t = self._gd_t(t, xs.shape[0], xs.device)
+        out = torch.empty(xs.shape[0], dtype=torch.float32, device=xs.device)
+        px = torch.empty_like(xs)
+        self._vb_step(model, xs, xt, t, clip_denoised, self._gd_model_kwargs(model_kwargs), out, px=px)
+        return {"output": out, "pred_xstart": px}
+
+    def _vb_terms_raw(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """Both terms of _vb_terms_bpd, [N] each in bits: (kl, decoder_nll) - what the reference's ``where`` selects from."""
+        xs, xt = self._gd_x(x_start, "x_start"), self._gd_x(x_t, "x_t")
+        t = self._gd_t(t, xs.shape[0], xs.device)
+        B = xs.shape[0]
+        vb, kl, nll = (torch.empty(B, dtype=torch.float32, device=xs.device) for _ in range(3))
+        with torch.no_grad():
+            self._vb_step(model, xs, xt, t, clip_denoised, self._gd_model_kwargs(model_kwargs), vb, raw_kl=kl, raw_nll=nll)
+        return kl, nll
+
+    @torch.no_grad()
+    def _prior_bpd(self, x_start: Tensor) -> Tensor:
+        """:936-951: KL(q(x_{T-1} | x_0) || N(0, 1)) per sample, in bits."""
+        xs = self._gd_x(x_start, "x_start")
+        out = torch.empty(xs.shape[0], dtype=torch.float32, device=xs.device)
+        self._gd_ws = ops.gd_workspace(xs.shape[0], xs.numel() // xs.shape[0], xs.device, self._gd_ws)
+        ops.gd_vlb_terms(xs, None, None, None, self._gd_table(xs.device), ops.GD_START_X, None, None, out, prior=True, workspace=self._gd_ws)
+        return out
+
+    @torch.no_grad()
+    def calc_bpd_loop(self, model, x_start: Tensor, clip_denoised=True, model_kwargs=None) -> dict:
+        """:953-1009: the whole variational bound in bits per dimension.  Column j of vb / xstart_mse / mse holds timestep T-1-j,
+        written on the device by the fused kernel; one noise draw per timestep; no host synchronisation until the error poll."""
+        xs = self._gd_x(x_start, "x_start")
+        dev, B, T = xs.device, xs.shape[0], self.timesteps
+        kw = self._gd_model_kwargs(model_kwargs)
+        vb, xstart_mse, mse = (torch.empty((B, T), dtype=torch.float32, device=dev) for _ in range(3))
+        ts = torch.arange(T - 1, -1, -1, dtype=torch.int64, device=dev).view(T, 1).expand(T, B).contiguous()
+        t_dev = torch.full((1,), T - 1, dtype=torch.int32, device=dev)
+        x_t = torch.empty_like(xs)
+        ca, cb = self._table("sqrt_alphas_cumprod", dev), self._table("sqrt_one_minus_alphas_cumprod", dev)
+        flag = self._gd_flag(dev)
+        for j in range(T):
+            noise = self.noise(xs)
+            ops.q_sample_coef(xs, noise.float().contiguous(), ts[j], ca, cb, out=x_t, err_flag=flag)
+            self._vb_step(model, xs, x_t, ts[j], clip_denoised, kw, vb[:, j], xstart_mse[:, j], mse[:, j], noise=noise.float().contiguous(),
+                          t_dev=t_dev)
+            ops.step_advance(t_dev, None, 0)
+        prior_bpd = self._prior_bpd(xs)
+        total_bpd = vb.sum(dim=1) + prior_bpd
+        self._check_backbone_errors()
+        return {"total_bpd": total_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+
+    # ---- training loss
+    def training_losses(self, model, x_start: Tensor, t: Tensor, model_kwargs={}, noise: Tensor = None) -> dict:
+        """:861-934 for MSE / RESCALED_MSE (equal without a learned variance): {"loss", "mse"}, [N] each, differentiable through
+        the backbone.  The target is x_start (START_X) or the noise (EPSILON)."""
+        if self.loss_type.is_vb():
+            raise NotImplementedError(f"loss_type {self.loss_type}: the variational-bound training loss (gaussian_diffusion.py:877-889) "
+                                      "is not built; the pipeline's fixed configuration (:211-216) uses MSE")
+        if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE):
+            raise NotImplementedError(self.loss_type)
+        model_variance_tables(self.tables, self.model_var_type)                    # refuses the learned variances (:368-383)
+        code = self._mean_code()
+        xs = self._gd_x(x_start, "x_start")
+        t = self._gd_t(t, xs.shape[0], xs.device)
+        if noise is None:
+            noise = self.noise(xs)
+        assert noise.shape == x_start.shape
+        noise = self._gd_x(noise, "noise")
+        x_t = self.q_sample(xs, t, noise=noise)
+        out = model(x_t, self._scale_timesteps(t), **(model_kwargs or {}))
+        if tuple(out.shape) != tuple(xs.shape):
+            raise NotImplementedError(f"model output {tuple(out.shape)} for x {tuple(xs.shape)}: learned variances (:368-383) are not built")
+        from ..autograd import mse_per_sample
+        target = xs if code == ops.GD_START_X else noise
+        mse = mse_per_sample(out, target)
+        return {"mse": mse, "loss": mse}
 
     # ------------------------------------------------------------------ wrappers
     def generate(self, parameter_space=None, random=False, save_figure_as=None):

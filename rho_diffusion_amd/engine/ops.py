@@ -93,6 +93,156 @@ def ddim_step(x_t: Tensor, model_out: Tensor, quantile: Tensor, noise: Optional[
     return x_prev
 
 
+# GaussianDiffusionPipeline API (csrc/gaussian.hip): rows of the packed per-timestep table (include/rho_hip.h RHO_GD_*)
+GD_ROWS = ("sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "model_var", "model_logvar", "post_logvar", "abar", "abar_prev", "abar_next",
+           "sqrt_abar", "log_1m_abar", "1m_abar", "post_var")
+GD_ROW = {k: i for i, k in enumerate(GD_ROWS)}
+GD_START_X, GD_EPSILON = 0, 1
+GD_AFFINE_OPS = {"ax": 0, "ax+by": 1, "ax-by": 2, "(ax-y)/b": 3}
+
+
+def _gd_t(t: Tensor, batch: int) -> Tensor:
+    if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1 or t.numel() != batch:
+        raise RhoHipError(f"t must be a contiguous int64 [{batch}] GPU tensor, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _gd_tab(tab: Tensor) -> int:
+    _f32c(tab, "tab")
+    if tab.dim() != 2 or tab.shape[0] != len(GD_ROWS):
+        raise RhoHipError(f"tab must be float32 [{len(GD_ROWS)}, T], got {tuple(tab.shape)}")
+    return tab.shape[1]
+
+
+def _same(x: Tensor, *others) -> None:
+    for name, o in others:
+        if o is not None:
+            _f32c(o, name)
+            if o.shape != x.shape:
+                raise RhoHipError(f"{name} has shape {tuple(o.shape)}, expected {tuple(x.shape)}")
+
+
+def gd_affine(x: Tensor, y: Optional[Tensor], t: Tensor, tab: Tensor, row_a: str, row_b: Optional[str], op: str,
+              out: Optional[Tensor] = None, err_flag: Optional[Tensor] = None) -> Tensor:
+    """out = a[t]*x | a[t]*x + b[t]*y | a[t]*x - b[t]*y | (a[t]*x - y)/b[t] with a, b rows of the packed table (rho_gd_affine)."""
+    _f32c(x, "x")
+    _same(x, ("y", y))
+    B = x.shape[0]
+    T = _gd_tab(tab)
+    out = torch.empty_like(x) if out is None else out
+    _same(x, ("out", out))
+    check(hip.lib().rho_gd_affine(ptr(x), ptr(y), ptr(out), ptr(_gd_t(t, B)), ptr(tab), T, GD_ROW[row_a], GD_ROW[row_b] if row_b else 0,
+                                  GD_AFFINE_OPS[op], B, x.numel() // B, ptr(err_flag), stream()), "rho_gd_affine")
+    return out
+
+
+def gd_posterior_step(x_t: Tensor, model_out: Tensor, t: Tensor, tab: Tensor, mean_type: int, quantile: Optional[Tensor],
+                      grad: Optional[Tensor], noise: Optional[Tensor], out: Tensor, pred_xstart: Optional[Tensor],
+                      err_flag: Optional[Tensor] = None) -> Tensor:
+    """p_mean_variance / condition_mean / p_sample in one pass (rho_gd_posterior_step)."""
+    _f32c(x_t, "x_t")
+    _same(x_t, ("model_out", model_out), ("grad", grad), ("noise", noise), ("out", out), ("pred_xstart", pred_xstart))
+    B = x_t.shape[0]
+    if quantile is not None and (_f32c(quantile, "quantile").numel() != B):
+        raise RhoHipError("quantile must be float32 [B]")
+    check(hip.lib().rho_gd_posterior_step(ptr(x_t), ptr(model_out), ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab), mean_type, ptr(quantile),
+                                          ptr(grad), ptr(noise), ptr(out), ptr(pred_xstart), B, x_t.numel() // B, ptr(err_flag), stream()),
+          "rho_gd_posterior_step")
+    return out
+
+
+def gd_ddim_step(x_t: Tensor, model_out: Tensor, t: Tensor, tab: Tensor, mean_type: int, quantile: Optional[Tensor],
+                 grad: Optional[Tensor], noise: Optional[Tensor], eta: float, reverse: bool, sample: Tensor, pred_xstart: Optional[Tensor],
+                 err_flag: Optional[Tensor] = None) -> Tensor:
+    """ddim_sample (eta, condition_score) or ddim_reverse_sample with per-sample t (rho_gd_ddim_step)."""
+    _f32c(x_t, "x_t")
+    _same(x_t, ("model_out", model_out), ("grad", grad), ("noise", noise), ("sample", sample), ("pred_xstart", pred_xstart))
+    B = x_t.shape[0]
+    if quantile is not None and (_f32c(quantile, "quantile").numel() != B):
+        raise RhoHipError("quantile must be float32 [B]")
+    check(hip.lib().rho_gd_ddim_step(ptr(x_t), ptr(model_out), ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab), mean_type, ptr(quantile), ptr(grad),
+                                     ptr(noise), float(eta), 1 if reverse else 0, ptr(sample), ptr(pred_xstart), B, x_t.numel() // B,
+                                     ptr(err_flag), stream()), "rho_gd_ddim_step")
+    return sample
+
+
+def gd_workspace(batch: int, per_sample: int, device, ws: Optional[Tensor] = None) -> Tensor:
+    need = hip.lib().rho_gd_reduce_workspace_bytes(batch, per_sample)
+    if ws is None or ws.device != torch.device(device) or ws.numel() * ws.element_size() < need:
+        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+def gd_vlb_terms(x_start: Tensor, x_t: Optional[Tensor], model_out: Optional[Tensor], t: Optional[Tensor], tab: Tensor, mean_type: int,
+                 quantile: Optional[Tensor], noise: Optional[Tensor], vb: Tensor, xstart_mse: Optional[Tensor] = None,
+                 mse: Optional[Tensor] = None, raw_kl: Optional[Tensor] = None, raw_nll: Optional[Tensor] = None,
+                 pred_xstart: Optional[Tensor] = None, prior: bool = False, workspace: Optional[Tensor] = None,
+                 err_flag: Optional[Tensor] = None) -> Tensor:
+    """_vb_terms_bpd + calc_bpd_loop statistics (or _prior_bpd) per sample (rho_gd_vlb_terms).  vb / xstart_mse / mse: float32 with
+    B elements at a common stride (e.g. column j of an [N, T] tensor)."""
+    _f32c(x_start, "x_start")
+    _same(x_start, ("x_t", x_t), ("model_out", model_out), ("noise", noise), ("pred_xstart", pred_xstart))
+    B, n = x_start.shape[0], x_start.numel() // x_start.shape[0]
+    stride = vb.stride(0) if vb.dim() == 1 else 1
+    for name, o in (("vb", vb), ("xstart_mse", xstart_mse), ("mse", mse)):
+        if o is not None and (o.dtype != torch.float32 or not o.is_cuda or o.dim() != 1 or o.numel() != B or (B > 1 and o.stride(0) != stride)):
+            raise RhoHipError(f"{name} must be float32 [B] on the GPU with vb's stride")
+    for name, o in (("raw_kl", raw_kl), ("raw_nll", raw_nll), ("quantile", quantile)):
+        if o is not None and (_f32c(o, name).numel() != B):
+            raise RhoHipError(f"{name} must be float32 [B]")
+    ws = gd_workspace(B, n, x_start.device, workspace)
+    check(hip.lib().rho_gd_vlb_terms(ptr(x_start), ptr(x_t), ptr(model_out), ptr(_gd_t(t, B)) if t is not None else None, ptr(tab),
+                                     _gd_tab(tab), mean_type, ptr(quantile), ptr(noise), 1 if prior else 0, ptr(vb), ptr(xstart_mse),
+                                     ptr(mse), max(stride, 1), ptr(raw_kl), ptr(raw_nll), ptr(pred_xstart), ptr(ws), B, n, ptr(err_flag),
+                                     stream()), "rho_gd_vlb_terms")
+    return vb
+
+
+def gd_mse_per_sample(target: Tensor, out: Tensor, workspace: Optional[Tensor] = None) -> Tensor:
+    """mean_flat((target - out)^2) -> float32 [B], fixed-order reduction (rho_gd_mse_per_sample)."""
+    _f32c(target, "target")
+    _same(target, ("out", out))
+    B, n = target.shape[0], target.numel() // target.shape[0]
+    loss = torch.empty(B, dtype=torch.float32, device=target.device)
+    ws = gd_workspace(B, n, target.device, workspace)
+    check(hip.lib().rho_gd_mse_per_sample(ptr(target), ptr(out), ptr(loss), ptr(ws), B, n, stream()), "rho_gd_mse_per_sample")
+    return loss
+
+
+def gd_mse_per_sample_bwd(target: Tensor, out: Tensor, g: Tensor) -> Tensor:
+    _f32c(target, "target")
+    _same(target, ("out", out))
+    B, n = target.shape[0], target.numel() // target.shape[0]
+    if _f32c(g, "g").numel() != B:
+        raise RhoHipError("g must be float32 [B]")
+    grad = torch.empty_like(out)
+    check(hip.lib().rho_gd_mse_per_sample_bwd(ptr(target), ptr(out), ptr(g), ptr(grad), B, n, stream()), "rho_gd_mse_per_sample_bwd")
+    return grad
+
+
+def normal_kl(operands, out: Tensor, batch: int, per_sample: int) -> Tensor:
+    """operands: 4 x (tensor or None, mode, scalar) as rho_normal_kl takes them (mode 0 full, 1 per-sample, 2 scalar)."""
+    ps = [ptr(o[0]) for o in operands]
+    modes = sum(o[1] << (2 * k) for k, o in enumerate(operands))
+    check(hip.lib().rho_normal_kl(*ps, *[float(o[2]) for o in operands], modes, ptr(out), batch, per_sample, stream()), "rho_normal_kl")
+    return out
+
+
+def discretized_gaussian_ll(operands, out: Tensor, batch: int, per_sample: int) -> Tensor:
+    ps = [ptr(o[0]) for o in operands]
+    modes = sum(o[1] << (2 * k) for k, o in enumerate(operands))
+    check(hip.lib().rho_discretized_gaussian_ll(*ps, *[float(o[2]) for o in operands], modes, ptr(out), batch, per_sample, stream()),
+          "rho_discretized_gaussian_ll")
+    return out
+
+
+def approx_normal_cdf(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    _f32c(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    check(hip.lib().rho_approx_normal_cdf(ptr(x), ptr(out), x.numel(), stream()), "rho_approx_normal_cdf")
+    return out
+
+
 def step_advance(t_dev: Optional[Tensor], offset_dev: Optional[Tensor], delta: int) -> None:
     check(hip.lib().rho_step_advance(ptr(t_dev), ptr(offset_dev), delta, stream()), "rho_step_advance")
 
