@@ -35,9 +35,10 @@ extern "C" {
 #define RHO_E_SHAPE (-3)    /* tile / shape constraint violated */
 
 /* ABI version: bumped on ANY signature / struct-layout change (2: table_len in rho_q_sample(_coef), fmt in rho_gn_bwd_finalize,
- * rho_conv_desc grew; 3: round-3 additions; 9: the rho_gd_* / metrics entry points of csrc/gaussian.hip).  A loader must compare rho_abi_version() with the header it was written against
+ * rho_conv_desc grew; 3: round-3 additions; 9: the rho_gd_* / metrics entry points of csrc/gaussian.hip;
+ * 10: learned variances - RHO_GD_LOG_BETA, the *_lv / strided / hybrid-loss entry points).  A loader must compare rho_abi_version() with the header it was written against
  * before calling anything else (hip.py does; a build with all symbols but older signatures would be called with shifted arguments). */
-#define RHO_ABI_VERSION 9
+#define RHO_ABI_VERSION 10
 int rho_abi_version(void);
 /* static string: target arch + build flags */
 const char* rho_build_info(void);
@@ -508,6 +509,8 @@ int rho_gn_apply(const void* x1, int64_t c1, const void* x2, int64_t c2, int dty
  * rho_abs_quantile_workspace_bytes(batch) bytes of device memory (contents undefined on entry). */
 int64_t rho_abs_quantile_workspace_bytes(int64_t batch);
 int rho_abs_quantile(const float* x, int64_t batch, int64_t n, double q, void* workspace, float* out, void* stream);
+/* The same over rows that start stride >= n elements apart (ABI 10: the mean half of a learned-variance output, stride = 2n). */
+int rho_abs_quantile_strided(const float* x, int64_t batch, int64_t n, int64_t stride, double q, void* workspace, float* out, void* stream);
 
 /* q_sample with explicit float32 coefficient tables: x_t = a[t_b] * x0 + b[t_b] * eps  (GaussianDiffusionPipeline.q_sample,
  * gaussian_diffusion.py:294-312, a = float(sqrt(abar)), b = float(sqrt(1-abar)) as _extract_into_tensor casts them).
@@ -554,9 +557,12 @@ int rho_ddpm_sched_step(const float* x_t, const float* model_out, const float* n
 #define RHO_GD_LOG_1M_ABAR 11    /* log(1 - abar) */
 #define RHO_GD_1M_ABAR 12        /* 1 - abar */
 #define RHO_GD_POST_VAR 13       /* posterior_variance */
-#define RHO_GD_ROWS 14
+#define RHO_GD_LOG_BETA 14       /* log(betas): LEARNED_RANGE's max_log (its min_log is RHO_GD_POST_LOGVAR) */
+#define RHO_GD_ROWS 15
 #define RHO_GD_START_X 0
 #define RHO_GD_EPSILON 1
+#define RHO_GD_LEARNED 0         /* var_type of the *_lv / hybrid entry points: logvar = v */
+#define RHO_GD_LEARNED_RANGE 1   /* frac = (v + 1)/2, logvar = frac*max_log + (1 - frac)*min_log */
 
 /* Table-coefficient elementwise forms, a = tab[row_a][t_b], b = tab[row_b][t_b]:
  *   op 0: out = a*x                q_mean_variance's mean (:277-292)
@@ -586,7 +592,25 @@ int rho_gd_ddim_step(const float* x_t, const float* model_out, const int64_t* t,
                      int mean_type, const float* quantile, const float* grad, const float* noise, float eta, int reverse,
                      float* sample, float* pred_xstart, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);
 
-/* Scratch of the per-sample reductions (rho_gd_vlb_terms, rho_gd_mse_per_sample), bytes. */
+/* The same reading sample b's model output at model_out + b*model_stride (model_stride >= per_sample): the mean half of a
+ * learned-variance [B, 2C, ...] output in place, model_stride = 2*per_sample (ABI 10). */
+int rho_gd_ddim_step_strided(const float* x_t, const float* model_out, int64_t model_stride, const int64_t* t, const float* tab,
+                             int64_t table_len, int mean_type, const float* quantile, const float* grad, const float* noise, float eta,
+                             int reverse, float* sample, float* pred_xstart, int64_t batch, int64_t per_sample, int32_t* err_flag,
+                             void* stream);
+
+/* Learned variances (:368-383, ABI 10).  The mean half of sample b is read at model_out + b*mean_stride, its variance values v at
+ * var_values + b*var_stride (an output [B, 2C, ...] read in place: var_values = model_out + per_sample, both strides 2*per_sample).
+ *   var_type RHO_GD_LEARNED: logvar = v;  RHO_GD_LEARNED_RANGE: frac = (v + 1)/2, logvar = frac*log_beta + (1 - frac)*post_logvar
+ * p_mean_variance / condition_mean / p_sample, one pass: x0 as rho_gd_posterior_step,
+ *   out = coef1*x0 + coef2*x_t  (+ exp(logvar)*grad)  (+ ((t != 0) * exp(0.5*logvar)) * noise)
+ * variance = exp(logvar), log_variance = logvar [batch, per_sample].  Every output may be NULL (not all of them). */
+int rho_gd_posterior_step_lv(const float* x_t, const float* model_out, int64_t mean_stride, const float* var_values, int64_t var_stride,
+                             const int64_t* t, const float* tab, int64_t table_len, int mean_type, int var_type, const float* quantile,
+                             const float* grad, const float* noise, float* out, float* pred_xstart, float* variance, float* log_variance,
+                             int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);
+
+/* Scratch of the per-sample reductions (rho_gd_vlb_terms(_lv), rho_gd_mse_per_sample, rho_gd_hybrid_loss), bytes. */
 int64_t rho_gd_reduce_workspace_bytes(int64_t batch, int64_t per_sample);
 
 /* _vb_terms_bpd (:826-859) and the per-timestep statistics of calc_bpd_loop (:936-1009), fused; per sample b, written at b*out_stride:
@@ -600,6 +624,28 @@ int rho_gd_vlb_terms(const float* x_start, const float* x_t, const float* model_
                      int64_t table_len, int mean_type, const float* quantile, const float* noise, int prior, float* vb,
                      float* xstart_mse, float* mse, int64_t out_stride, float* raw_kl, float* raw_nll, float* pred_xstart,
                      void* workspace, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);
+
+/* rho_gd_vlb_terms (prior = 0) with the per-element model log-variance of rho_gd_posterior_step_lv: the KL against post_logvar and
+ * the decoder NLL with log_scales = 0.5*logvar; same outputs and reduction (ABI 10). */
+int rho_gd_vlb_terms_lv(const float* x_start, const float* x_t, const float* model_out, int64_t mean_stride, const float* var_values,
+                        int64_t var_stride, const int64_t* t, const float* tab, int64_t table_len, int mean_type, int var_type,
+                        const float* quantile, const float* noise, float* vb, float* xstart_mse, float* mse, int64_t out_stride,
+                        float* raw_kl, float* raw_nll, float* pred_xstart, void* workspace, int64_t batch, int64_t per_sample,
+                        int32_t* err_flag, void* stream);
+
+/* training_losses (:893-930), MSE / RESCALED_MSE with a learned variance; model_out [batch, 2*per_sample] (mean half, variance half):
+ *   mse[b] = mean((target - m)^2);  vb[b] = _vb_terms_bpd on the frozen m and v, clip_denoised = False (* vb_scale if rescaled)
+ *   loss[b] = mse[b] + vb[b]        (mse, vb may be NULL; fixed-order two-stage reduction, bit-reproducible)
+ * Backward, grad [batch, 2*per_sample]: the mean half -((g_m/n) * (2*(target - m))) with g_m = g_loss + g_mse (the VLB sees a detached
+ * mean: exactly 0 there), the variance half (g_v*scale/ln2/n) * d term/d logvar * d logvar/d v with g_v = g_loss + g_vb; at t == 0
+ * through the tanh CDF, zero where a 1e-12 clamp cuts the path.  g_loss / g_mse / g_vb [batch], each may be NULL (= 0). */
+int rho_gd_hybrid_loss(const float* x_start, const float* x_t, const float* target, const float* model_out, const int64_t* t,
+                       const float* tab, int64_t table_len, int mean_type, int var_type, int rescaled, float vb_scale, float* loss,
+                       float* mse, float* vb, void* workspace, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);
+int rho_gd_hybrid_loss_bwd(const float* x_start, const float* x_t, const float* target, const float* model_out, const int64_t* t,
+                           const float* tab, int64_t table_len, int mean_type, int var_type, int rescaled, float vb_scale,
+                           const float* g_loss, const float* g_mse, const float* g_vb, float* grad, int64_t batch, int64_t per_sample,
+                           int32_t* err_flag, void* stream);
 
 /* training_losses' MSE term (:861-934): loss[b] = mean_flat((target - out)^2), fixed-order two-stage reduction; and its backward
  * grad = -((g[b] / per_sample) * (2 * (target - out))). */

@@ -72,3 +72,30 @@ class PerSampleMSEFunction(torch.autograd.Function):
 
 def mse_per_sample(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return PerSampleMSEFunction.apply(pred, target)
+
+
+class HybridLossFunction(torch.autograd.Function):
+    """training_losses with a learned variance (gaussian_diffusion.py:893-930): per-sample (loss, mse, vb) from the [N, 2C, ...] model
+    output in one fused HIP reduction; the backward writes the whole output gradient in one pass (the VLB term sees the mean half
+    detached, as the reference's ``frozen_out``)."""
+
+    @staticmethod
+    def forward(ctx, model_out, x_start, x_t, target, t, tab, mean_type, var_type, vb_scale, err_flag):
+        model_out = model_out.contiguous().float()
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(model_out, x_start, x_t, target, t, tab)
+        ctx.meta = (mean_type, var_type, vb_scale, err_flag)
+        loss, mse, vb = ops.gd_hybrid_loss(x_start, x_t, target, model_out, t, tab, mean_type, var_type, vb_scale, err_flag=err_flag)
+        return loss, mse, vb
+
+    @staticmethod
+    def backward(ctx, g_loss, g_mse, g_vb):
+        model_out, x_start, x_t, target, t, tab = ctx.saved_tensors
+        mean_type, var_type, vb_scale, err_flag = ctx.meta
+        gs = [None if g is None else g.contiguous().float() for g in (g_loss, g_mse, g_vb)]
+        grad = ops.gd_hybrid_loss_bwd(x_start, x_t, target, model_out, t, tab, mean_type, var_type, vb_scale, *gs, err_flag=err_flag)
+        return (grad,) + (None,) * 9
+
+
+def hybrid_loss(model_out, x_start, x_t, target, t, tab, mean_type: int, var_type: int, vb_scale: Optional[float], err_flag=None):
+    return HybridLossFunction.apply(model_out, x_start, x_t, target, t, tab, mean_type, var_type, vb_scale, err_flag)

@@ -222,7 +222,8 @@ extern "C" int rho_gd_posterior_step(const float* x_t, const float* model_out, c
 __global__ __launch_bounds__(GD_THREADS) void k_gd_ddim(const float* __restrict__ xt, const float* __restrict__ mo, const int64_t* __restrict__ t,
                                                         const float* __restrict__ tab, int64_t len, int eps_mode, const float* __restrict__ quant,
                                                         const float* __restrict__ grad, const float* __restrict__ noise, float eta, int reverse,
-                                                        float* __restrict__ sample, float* __restrict__ pred_x0, int64_t n, int32_t* err_flag) {
+                                                        float* __restrict__ sample, float* __restrict__ pred_x0, int64_t n, int64_t mo_stride,
+                                                        int32_t* err_flag) {
     const int b = blockIdx.y;
     const int64_t tb = gd_row_index(t, b, len, err_flag);
     const float sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb), srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
@@ -243,9 +244,10 @@ __global__ __launch_bounds__(GD_THREADS) void k_gd_ddim(const float* __restrict_
     }
     const float s = quant != nullptr ? fmaxf(quant[b], 1.0f) : 1.0f;
     const int64_t off = (int64_t)b * n;
+    const float* mob = mo + (int64_t)b * mo_stride - off;
     for (int64_t i = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x; i < off + n; i += (int64_t)gridDim.x * GD_THREADS) {
         const float x = xt[i];
-        float x0 = gd_x0(x, mo[i], eps_mode, sr, srm1);
+        float x0 = gd_x0(x, mob[i], eps_mode, sr, srm1);
         if (quant != nullptr) x0 = gd_threshold(x0, s);
         const float ax = sr * x;
         if (grad != nullptr) {
@@ -267,18 +269,39 @@ __global__ __launch_bounds__(GD_THREADS) void k_gd_ddim(const float* __restrict_
     }
 }
 
-extern "C" int rho_gd_ddim_step(const float* x_t, const float* model_out, const int64_t* t, const float* tab, int64_t table_len,
-                                int mean_type, const float* quantile, const float* grad, const float* noise, float eta, int reverse,
-                                float* sample, float* pred_xstart, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream) {
+namespace {
+int gd_ddim_step(const float* x_t, const float* model_out, int64_t model_stride, const int64_t* t, const float* tab, int64_t table_len,
+                 int mean_type, const float* quantile, const float* grad, const float* noise, float eta, int reverse, float* sample,
+                 float* pred_xstart, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream) {
     if (!x_t || !model_out || !t || !tab || !sample || batch <= 0 || per_sample <= 0 || table_len <= 0) return RHO_E_ARG;
+    if (model_stride < per_sample) return RHO_E_ARG;
     if (mean_type != RHO_GD_START_X && mean_type != RHO_GD_EPSILON) return RHO_E_ARG;
     if (reverse && (eta != 0.0f || noise || grad)) return RHO_E_ARG;
     if (batch > 65535) return RHO_E_SHAPE;
     dim3 grid((unsigned)gd_chunks(batch, per_sample), (unsigned)batch);
     hipLaunchKernelGGL(k_gd_ddim, grid, dim3(GD_THREADS), 0, as_stream(stream), x_t, model_out, t, tab, table_len,
-                       mean_type == RHO_GD_EPSILON ? 1 : 0, quantile, grad, noise, eta, reverse, sample, pred_xstart, per_sample, err_flag);
+                       mean_type == RHO_GD_EPSILON ? 1 : 0, quantile, grad, noise, eta, reverse, sample, pred_xstart, per_sample, model_stride,
+                       err_flag);
     RHO_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace
+
+extern "C" int rho_gd_ddim_step(const float* x_t, const float* model_out, const int64_t* t, const float* tab, int64_t table_len,
+                                int mean_type, const float* quantile, const float* grad, const float* noise, float eta, int reverse,
+                                float* sample, float* pred_xstart, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream) {
+    return gd_ddim_step(x_t, model_out, per_sample, t, tab, table_len, mean_type, quantile, grad, noise, eta, reverse, sample, pred_xstart,
+                        batch, per_sample, err_flag, stream);
+}
+
+// the same reading sample b's model output at model_out + b*model_stride: the mean half of a learned-variance [B, 2C, ...] output in
+// place (model_stride = 2*per_sample); DDIM ignores the variance half, as the reference does
+extern "C" int rho_gd_ddim_step_strided(const float* x_t, const float* model_out, int64_t model_stride, const int64_t* t, const float* tab,
+                                        int64_t table_len, int mean_type, const float* quantile, const float* grad, const float* noise,
+                                        float eta, int reverse, float* sample, float* pred_xstart, int64_t batch, int64_t per_sample,
+                                        int32_t* err_flag, void* stream) {
+    return gd_ddim_step(x_t, model_out, model_stride, t, tab, table_len, mean_type, quantile, grad, noise, eta, reverse, sample, pred_xstart,
+                        batch, per_sample, err_flag, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- variational bound
@@ -388,6 +411,417 @@ extern "C" int rho_gd_vlb_terms(const float* x_start, const float* x_t, const fl
                        per_sample, err_flag);
     hipLaunchKernelGGL(k_gd_vlb_final, dim3((unsigned)batch), dim3(GD_THREADS), 0, st, (const double*)workspace, chunks, t, prior,
                        per_sample, vb, xstart_mse, mse, out_stride, raw_kl, raw_nll);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- learned variances
+// p_mean_variance with model_var_type LEARNED / LEARNED_RANGE (:368-383).  The model output is [B, 2C, ...]: the mean half of sample b
+// at model_out + b*mean_stride, the variance values v at var_values + b*var_stride (for an output read in place: the same base + C*S,
+// both strides 2*C*S).  Per element, float32 in the reference's order:
+//   LEARNED:        logvar = v
+//   LEARNED_RANGE:  frac = (v + 1) / 2;  logvar = frac*max_log + (1 - frac)*min_log   (max_log = log(betas), min_log = post_logvar)
+//   var = exp(logvar)
+namespace {
+__device__ __forceinline__ float gd_learned_logvar(float v, int range, float min_log, float max_log) {
+    if (!range) return v;
+    const float frac = (v + 1.0f) / 2.0f;
+    const float p0 = frac * max_log, p1 = (1.0f - frac) * min_log;
+    return p0 + p1;
+}
+
+// d logvar / d v (autograd's order: d frac = g*max_log + -(g*min_log), d v = d frac / 2)
+__device__ __forceinline__ float gd_learned_dlogvar(float g, int range, float min_log, float max_log) {
+    if (!range) return g;
+    const float p0 = g * max_log, p1 = g * min_log;
+    return (p0 + -p1) / 2.0f;
+}
+
+int gd_lv_args(int mean_type, int var_type) {
+    if (mean_type != RHO_GD_START_X && mean_type != RHO_GD_EPSILON) return RHO_E_ARG;
+    if (var_type != RHO_GD_LEARNED && var_type != RHO_GD_LEARNED_RANGE) return RHO_E_ARG;
+    return 0;
+}
+}  // namespace
+
+// mean = coef1*x0 + coef2*x (+ var*grad) (+ ((t != 0) * exp(0.5*logvar)) * noise), var / logvar per element
+__global__ __launch_bounds__(GD_THREADS) void k_gd_posterior_lv(const float* __restrict__ xt, const float* __restrict__ mo, int64_t mo_stride,
+                                                                const float* __restrict__ vv, int64_t v_stride, const int64_t* __restrict__ t,
+                                                                const float* __restrict__ tab, int64_t len, int eps_mode, int range,
+                                                                const float* __restrict__ quant, const float* __restrict__ grad,
+                                                                const float* __restrict__ noise, float* __restrict__ out,
+                                                                float* __restrict__ pred_x0, float* __restrict__ var_out,
+                                                                float* __restrict__ logvar_out, int64_t n, int32_t* err_flag) {
+    const int b = blockIdx.y;
+    const int64_t tb = gd_row_index(t, b, len, err_flag);
+    const float sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb), srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
+    const float c1 = gd_tab(tab, len, RHO_GD_COEF1, tb), c2 = gd_tab(tab, len, RHO_GD_COEF2, tb);
+    const float min_log = gd_tab(tab, len, RHO_GD_POST_LOGVAR, tb), max_log = gd_tab(tab, len, RHO_GD_LOG_BETA, tb);
+    const float nmask = t[b] != 0 ? 1.0f : 0.0f;
+    const float s = quant != nullptr ? fmaxf(quant[b], 1.0f) : 1.0f;
+    const int64_t off = (int64_t)b * n;
+    const float* mob = mo + (int64_t)b * mo_stride - off;
+    const float* vb = vv + (int64_t)b * v_stride - off;
+    for (int64_t i = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x; i < off + n; i += (int64_t)gridDim.x * GD_THREADS) {
+        const float x = xt[i];
+        float x0 = gd_x0(x, mob[i], eps_mode, sr, srm1);
+        if (quant != nullptr) x0 = gd_threshold(x0, s);
+        const float lv = gd_learned_logvar(vb[i], range, min_log, max_log);
+        const float p0 = c1 * x0, p1 = c2 * x;
+        float v = p0 + p1;
+        if (grad != nullptr) {
+            const float p2 = expf(lv) * grad[i];
+            v = v + p2;
+        }
+        if (noise != nullptr) {
+            const float h = 0.5f * lv;
+            const float p3 = (nmask * expf(h)) * noise[i];
+            v = v + p3;
+        }
+        if (out != nullptr) out[i] = v;
+        if (pred_x0 != nullptr) pred_x0[i] = x0;
+        if (var_out != nullptr) var_out[i] = expf(lv);
+        if (logvar_out != nullptr) logvar_out[i] = lv;
+    }
+}
+
+extern "C" int rho_gd_posterior_step_lv(const float* x_t, const float* model_out, int64_t mean_stride, const float* var_values,
+                                        int64_t var_stride, const int64_t* t, const float* tab, int64_t table_len, int mean_type, int var_type,
+                                        const float* quantile, const float* grad, const float* noise, float* out, float* pred_xstart,
+                                        float* variance, float* log_variance, int64_t batch, int64_t per_sample, int32_t* err_flag,
+                                        void* stream) {
+    if (!x_t || !model_out || !var_values || !t || !tab || batch <= 0 || per_sample <= 0 || table_len <= 0) return RHO_E_ARG;
+    if (!out && !pred_xstart && !variance && !log_variance) return RHO_E_ARG;
+    if (mean_stride < per_sample || var_stride < per_sample || gd_lv_args(mean_type, var_type)) return RHO_E_ARG;
+    if (batch > 65535) return RHO_E_SHAPE;
+    dim3 grid((unsigned)gd_chunks(batch, per_sample), (unsigned)batch);
+    hipLaunchKernelGGL(k_gd_posterior_lv, grid, dim3(GD_THREADS), 0, as_stream(stream), x_t, model_out, mean_stride, var_values, var_stride, t,
+                       tab, table_len, mean_type == RHO_GD_EPSILON ? 1 : 0, var_type == RHO_GD_LEARNED_RANGE ? 1 : 0, quantile, grad, noise,
+                       out, pred_xstart, variance, log_variance, per_sample, err_flag);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
+// _vb_terms_bpd / calc_bpd_loop statistics with a learned variance: as k_gd_vlb_partial with the model log-variance per element
+__global__ __launch_bounds__(GD_THREADS) void k_gd_vlb_lv_partial(const float* __restrict__ xs, const float* __restrict__ xt,
+                                                                  const float* __restrict__ mo, int64_t mo_stride, const float* __restrict__ vv,
+                                                                  int64_t v_stride, const int64_t* __restrict__ t, const float* __restrict__ tab,
+                                                                  int64_t len, int eps_mode, int range, const float* __restrict__ quant,
+                                                                  const float* __restrict__ noise, float* __restrict__ pred_x0,
+                                                                  double* __restrict__ ws, int64_t n, int32_t* err_flag) {
+    const int b = blockIdx.y;
+    double acc[GD_VLB_K] = {0.0, 0.0, 0.0, 0.0};
+    const int64_t off = (int64_t)b * n;
+    const int64_t tb = gd_row_index(t, b, len, err_flag);
+    const float sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb), srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
+    const float c1 = gd_tab(tab, len, RHO_GD_COEF1, tb), c2 = gd_tab(tab, len, RHO_GD_COEF2, tb);
+    const float lv1 = gd_tab(tab, len, RHO_GD_POST_LOGVAR, tb), max_log = gd_tab(tab, len, RHO_GD_LOG_BETA, tb);
+    const float s = quant != nullptr ? fmaxf(quant[b], 1.0f) : 1.0f;
+    const float* mob = mo + (int64_t)b * mo_stride - off;
+    const float* vb = vv + (int64_t)b * v_stride - off;
+    for (int64_t i = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x; i < off + n; i += (int64_t)gridDim.x * GD_THREADS) {
+        const float x = xt[i], x_start = xs[i];
+        float x0 = gd_x0(x, mob[i], eps_mode, sr, srm1);
+        if (quant != nullptr) x0 = gd_threshold(x0, s);
+        if (pred_x0 != nullptr) pred_x0[i] = x0;
+        const float lv2 = gd_learned_logvar(vb[i], range, lv1, max_log);
+        const float cx = c2 * x;
+        const float tm = (c1 * x_start) + cx;
+        const float mm = (c1 * x0) + cx;
+        acc[0] += (double)gd_normal_kl(tm, lv1, mm, lv2);
+        acc[1] -= (double)gd_dgll(x_start, mm, 0.5f * lv2);
+        const float dx = x0 - x_start;
+        acc[2] += (double)(dx * dx);
+        if (noise != nullptr) {
+            const float eps = ((sr * x) - x0) / srm1;
+            const float de = eps - noise[i];
+            acc[3] += (double)(de * de);
+        }
+    }
+    gd_block_sum<GD_VLB_K>(acc);
+    if (threadIdx.x == 0) {
+        double* w = ws + ((int64_t)b * gridDim.x + blockIdx.x) * GD_VLB_K;
+#pragma unroll
+        for (int k = 0; k < GD_VLB_K; ++k) w[k] = acc[k];
+    }
+}
+
+extern "C" int rho_gd_vlb_terms_lv(const float* x_start, const float* x_t, const float* model_out, int64_t mean_stride, const float* var_values,
+                                   int64_t var_stride, const int64_t* t, const float* tab, int64_t table_len, int mean_type, int var_type,
+                                   const float* quantile, const float* noise, float* vb, float* xstart_mse, float* mse, int64_t out_stride,
+                                   float* raw_kl, float* raw_nll, float* pred_xstart, void* workspace, int64_t batch, int64_t per_sample,
+                                   int32_t* err_flag, void* stream) {
+    if (!x_start || !x_t || !model_out || !var_values || !t || !tab || !vb || !workspace || (mse && !noise)) return RHO_E_ARG;
+    if (batch <= 0 || per_sample <= 0 || table_len <= 0 || out_stride < 1) return RHO_E_ARG;
+    if (mean_stride < per_sample || var_stride < per_sample || gd_lv_args(mean_type, var_type)) return RHO_E_ARG;
+    if (batch > 65535) return RHO_E_SHAPE;
+    const int64_t chunks = gd_chunks(batch, per_sample);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(k_gd_vlb_lv_partial, dim3((unsigned)chunks, (unsigned)batch), dim3(GD_THREADS), 0, st, x_start, x_t, model_out,
+                       mean_stride, var_values, var_stride, t, tab, table_len, mean_type == RHO_GD_EPSILON ? 1 : 0,
+                       var_type == RHO_GD_LEARNED_RANGE ? 1 : 0, quantile, noise, pred_xstart, (double*)workspace, per_sample, err_flag);
+    hipLaunchKernelGGL(k_gd_vlb_final, dim3((unsigned)batch), dim3(GD_THREADS), 0, st, (const double*)workspace, chunks, t, 0, per_sample, vb,
+                       xstart_mse, mse, out_stride, raw_kl, raw_nll);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- hybrid loss
+// training_losses (:893-930), MSE / RESCALED_MSE with a learned variance, model output mo [B, 2C, ...] read in place:
+//   mse[b]  = mean((target - m)^2)
+//   vb[b]   = _vb_terms_bpd(frozen m, v; clip_denoised=False) (* vb_scale = T/1000 for RESCALED_MSE);  loss = mse + vb
+// Only the term where(t == 0, nll, kl) selects is evaluated.  Backward: the mean half gets the MSE gradient only (the reference
+// detaches m for the VLB), the variance half g_vb / ln2 / n * d term / d logvar * d logvar / d v.
+// Pure streaming passes: 16-byte loads when per_sample % 4 == 0 (then every row of both halves is 16-byte aligned).
+namespace {
+constexpr int GD_HYB_K = 2;
+
+struct GdHybCoef {
+    float sr, srm1, c1, c2, lv1, max_log;
+    int eps_mode, range, t0;
+};
+
+__device__ __forceinline__ GdHybCoef gd_hyb_coef(const int64_t* __restrict__ t, const float* __restrict__ tab, int64_t len, int b, int eps_mode,
+                                                 int range, int32_t* err_flag) {
+    const int64_t tb = gd_row_index(t, b, len, err_flag);
+    GdHybCoef c;
+    c.sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb);
+    c.srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
+    c.c1 = gd_tab(tab, len, RHO_GD_COEF1, tb);
+    c.c2 = gd_tab(tab, len, RHO_GD_COEF2, tb);
+    c.lv1 = gd_tab(tab, len, RHO_GD_POST_LOGVAR, tb);
+    c.max_log = gd_tab(tab, len, RHO_GD_LOG_BETA, tb);
+    c.eps_mode = eps_mode;
+    c.range = range;
+    c.t0 = t[b] == 0;
+    return c;
+}
+
+// the means of one element: (true mean, frozen model mean)
+__device__ __forceinline__ void gd_hyb_means(const GdHybCoef& c, float x, float xs, float m, float& tm, float& mm) {
+    const float x0 = gd_x0(x, m, c.eps_mode, c.sr, c.srm1);
+    const float cx = c.c2 * x;
+    tm = (c.c1 * xs) + cx;
+    mm = (c.c1 * x0) + cx;
+}
+
+// backward of gd_cdf in autograd's order (MulBackward 0.5, TanhBackward, MulBackward sqrt(2/pi), AddBackward + PowBackward):
+// d u of an upstream gradient g at cdf(u)
+__device__ __forceinline__ float gd_cdf_bwd(float g, float u, float& cdf) {
+    const float x3 = (u * u) * u;
+    const float w = 0.7978845608028654f * (u + 0.044715f * x3);
+    const float th = tanhf(w);
+    cdf = 0.5f * (1.0f + th);
+    const float gw = (g * 0.5f) * (1.0f - th * th);
+    const float gin = gw * 0.7978845608028654f;
+    return gin + (gin * 0.044715f) * (3.0f * (u * u));
+}
+
+// d logvar of -discretized_gaussian_log_likelihood(x, mean, 0.5*logvar) for an upstream gradient g_nll, as torch autograd evaluates
+// the reference expression: zero where a 1e-12 clamp or a where-branch cuts the path
+__device__ __forceinline__ float gd_nll_bwd(float g_nll, float x, float mean, float lv) {
+    const float log_scale = 0.5f * lv;
+    const float centered = x - mean;
+    const float inv_stdv = expf(-log_scale);
+    const float bin = (float)(1.0 / 255.0);
+    const float cpb = centered + bin, cmb = centered - bin;
+    const float plus_in = inv_stdv * cpb, min_in = inv_stdv * cmb;
+    float cdf_plus, cdf_min;
+    gd_cdf_bwd(0.0f, plus_in, cdf_plus);
+    gd_cdf_bwd(0.0f, min_in, cdf_min);
+    const float g_lp = -g_nll;
+    float g_cp = 0.0f, g_cm = 0.0f;
+    if (x < -0.999f) {
+        if (cdf_plus >= 1e-12f) g_cp = g_lp / cdf_plus;
+    } else if (x > 0.999f) {
+        const float r = 1.0f - cdf_min;
+        if (r >= 1e-12f) g_cm = -(g_lp / r);
+    } else {
+        const float d = cdf_plus - cdf_min;
+        if (d >= 1e-12f) {
+            g_cp = g_lp / d;
+            g_cm = -g_cp;
+        }
+    }
+    float c;
+    const float g_inv = gd_cdf_bwd(g_cp, plus_in, c) * cpb + gd_cdf_bwd(g_cm, min_in, c) * cmb;
+    const float g_ls = -(g_inv * inv_stdv);
+    return g_ls * 0.5f;
+}
+
+// d lv2 of normal_kl(m1, lv1, m2, lv2) for an upstream gradient g, autograd's order:
+//   g1 = g*0.5;  g1 + -(g1*exp(lv1 - lv2)) + -((g1*(m1 - m2)^2)*exp(-lv2))
+__device__ __forceinline__ float gd_kl_bwd(float g, float m1, float lv1, float m2, float lv2) {
+    const float g1 = g * 0.5f;
+    const float d = m1 - m2;
+    const float a = g1 + -(g1 * expf(lv1 - lv2));
+    return a + -((g1 * (d * d)) * expf(-lv2));
+}
+
+// mean((target - m)^2) and the selected VLB term of one element pair
+__device__ __forceinline__ void gd_hyb_fwd_elem(const GdHybCoef& c, float x, float xs, float tg, float m, float v, double (&acc)[GD_HYB_K]) {
+    const float d = tg - m;
+    acc[0] += (double)(d * d);
+    float tm, mm;
+    gd_hyb_means(c, x, xs, m, tm, mm);
+    const float lv2 = gd_learned_logvar(v, c.range, c.lv1, c.max_log);
+    if (c.t0) acc[1] -= (double)gd_dgll(xs, mm, 0.5f * lv2);
+    else acc[1] += (double)gd_normal_kl(tm, c.lv1, mm, lv2);
+}
+
+// (d mean-half, d variance-half) of one element pair; gm = d loss / d mse[b] / n, gv = d loss / d vb[b] * scale / ln2 / n
+__device__ __forceinline__ void gd_hyb_bwd_elem(const GdHybCoef& c, float x, float xs, float tg, float m, float v, float gm, float gv, float& dm,
+                                                float& dv) {
+    const float d = tg - m;
+    const float p = gm * (2.0f * d);
+    dm = -p;
+    float tm, mm;
+    gd_hyb_means(c, x, xs, m, tm, mm);
+    const float lv2 = gd_learned_logvar(v, c.range, c.lv1, c.max_log);
+    const float dlv = c.t0 ? gd_nll_bwd(gv, xs, mm, lv2) : gd_kl_bwd(gv, tm, c.lv1, mm, lv2);
+    dv = gd_learned_dlogvar(dlv, c.range, c.lv1, c.max_log);
+}
+}  // namespace
+
+template <int V>
+__global__ __launch_bounds__(GD_THREADS) void k_gd_hybrid_partial(const float* __restrict__ xs, const float* __restrict__ xt,
+                                                                  const float* __restrict__ tgt, const float* __restrict__ mo,
+                                                                  const int64_t* __restrict__ t, const float* __restrict__ tab, int64_t len,
+                                                                  int eps_mode, int range, double* __restrict__ ws, int64_t n, int32_t* err_flag) {
+    const int b = blockIdx.y;
+    const GdHybCoef c = gd_hyb_coef(t, tab, len, b, eps_mode, range, err_flag);
+    double acc[GD_HYB_K] = {0.0, 0.0};
+    const int64_t off = (int64_t)b * n;
+    const float* mb = mo + 2 * off;
+    const float* vb = mb + n;
+    const float* xsb = xs + off;
+    const float* xtb = xt + off;
+    const float* tgb = tgt + off;
+    for (int64_t i = ((int64_t)blockIdx.x * GD_THREADS + threadIdx.x) * V; i < n; i += (int64_t)gridDim.x * GD_THREADS * V) {
+        if constexpr (V == 4) {
+            const float4 x = *reinterpret_cast<const float4*>(xtb + i), s = *reinterpret_cast<const float4*>(xsb + i);
+            const float4 g = *reinterpret_cast<const float4*>(tgb + i), m = *reinterpret_cast<const float4*>(mb + i);
+            const float4 v = *reinterpret_cast<const float4*>(vb + i);
+            gd_hyb_fwd_elem(c, x.x, s.x, g.x, m.x, v.x, acc);
+            gd_hyb_fwd_elem(c, x.y, s.y, g.y, m.y, v.y, acc);
+            gd_hyb_fwd_elem(c, x.z, s.z, g.z, m.z, v.z, acc);
+            gd_hyb_fwd_elem(c, x.w, s.w, g.w, m.w, v.w, acc);
+        } else {
+            gd_hyb_fwd_elem(c, xtb[i], xsb[i], tgb[i], mb[i], vb[i], acc);
+        }
+    }
+    gd_block_sum<GD_HYB_K>(acc);
+    if (threadIdx.x == 0) {
+        double* w = ws + ((int64_t)b * gridDim.x + blockIdx.x) * GD_HYB_K;
+        w[0] = acc[0];
+        w[1] = acc[1];
+    }
+}
+
+// stage 2: mse = mean, vb = mean / ln 2 (* vb_scale), loss = mse + vb (float32, as the reference's tensors)
+__global__ __launch_bounds__(GD_THREADS) void k_gd_hybrid_final(const double* __restrict__ ws, int64_t chunks, int64_t n, int rescale,
+                                                                float vb_scale, float* __restrict__ loss, float* __restrict__ mse,
+                                                                float* __restrict__ vb) {
+    const int b = blockIdx.x;
+    double acc[GD_HYB_K];
+    gd_sum_partials<GD_HYB_K>(ws, chunks, b, acc);
+    if (threadIdx.x != 0) return;
+    const float ln2 = (float)0.69314718055994530942;
+    const float m = (float)(acc[0] / (double)n);
+    float v = (float)(acc[1] / (double)n) / ln2;
+    if (rescale) v = v * vb_scale;
+    loss[b] = m + v;
+    if (mse != nullptr) mse[b] = m;
+    if (vb != nullptr) vb[b] = v;
+}
+
+template <int V>
+__global__ __launch_bounds__(GD_THREADS) void k_gd_hybrid_bwd(const float* __restrict__ xs, const float* __restrict__ xt,
+                                                              const float* __restrict__ tgt, const float* __restrict__ mo,
+                                                              const int64_t* __restrict__ t, const float* __restrict__ tab, int64_t len,
+                                                              int eps_mode, int range, int rescale, float vb_scale,
+                                                              const float* __restrict__ g_loss, const float* __restrict__ g_mse,
+                                                              const float* __restrict__ g_vb, float* __restrict__ grad, int64_t n,
+                                                              int32_t* err_flag) {
+    const int b = blockIdx.y;
+    const GdHybCoef c = gd_hyb_coef(t, tab, len, b, eps_mode, range, err_flag);
+    // autograd: loss = mse + vb hands g_loss to both; the reference's ops in order: (vb * scale), / ln2, mean over n
+    const float gl = g_loss != nullptr ? g_loss[b] : 0.0f;
+    const float gms = g_mse != nullptr ? gl + g_mse[b] : gl;
+    float gvs = g_vb != nullptr ? gl + g_vb[b] : gl;
+    if (rescale) gvs = gvs * vb_scale;
+    const float gm = gms / (float)n;
+    const float gv = (gvs / (float)0.69314718055994530942) / (float)n;
+    const int64_t off = (int64_t)b * n;
+    const float* mb = mo + 2 * off;
+    const float* vb = mb + n;
+    float* dmb = grad + 2 * off;
+    float* dvb = dmb + n;
+    const float* xsb = xs + off;
+    const float* xtb = xt + off;
+    const float* tgb = tgt + off;
+    for (int64_t i = ((int64_t)blockIdx.x * GD_THREADS + threadIdx.x) * V; i < n; i += (int64_t)gridDim.x * GD_THREADS * V) {
+        if constexpr (V == 4) {
+            const float4 x = *reinterpret_cast<const float4*>(xtb + i), s = *reinterpret_cast<const float4*>(xsb + i);
+            const float4 g = *reinterpret_cast<const float4*>(tgb + i), m = *reinterpret_cast<const float4*>(mb + i);
+            const float4 v = *reinterpret_cast<const float4*>(vb + i);
+            float4 dm, dv;
+            gd_hyb_bwd_elem(c, x.x, s.x, g.x, m.x, v.x, gm, gv, dm.x, dv.x);
+            gd_hyb_bwd_elem(c, x.y, s.y, g.y, m.y, v.y, gm, gv, dm.y, dv.y);
+            gd_hyb_bwd_elem(c, x.z, s.z, g.z, m.z, v.z, gm, gv, dm.z, dv.z);
+            gd_hyb_bwd_elem(c, x.w, s.w, g.w, m.w, v.w, gm, gv, dm.w, dv.w);
+            *reinterpret_cast<float4*>(dmb + i) = dm;
+            *reinterpret_cast<float4*>(dvb + i) = dv;
+        } else {
+            gd_hyb_bwd_elem(c, xtb[i], xsb[i], tgb[i], mb[i], vb[i], gm, gv, dmb[i], dvb[i]);
+        }
+    }
+}
+
+namespace {
+int64_t gd_hyb_chunks(int64_t batch, int64_t per_sample, int v) { return gd_chunks(batch, (per_sample + v - 1) / v); }
+}  // namespace
+
+extern "C" int rho_gd_hybrid_loss(const float* x_start, const float* x_t, const float* target, const float* model_out, const int64_t* t,
+                                  const float* tab, int64_t table_len, int mean_type, int var_type, int rescaled, float vb_scale, float* loss,
+                                  float* mse, float* vb, void* workspace, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream) {
+    if (!x_start || !x_t || !target || !model_out || !t || !tab || !loss || !workspace) return RHO_E_ARG;
+    if (batch <= 0 || per_sample <= 0 || table_len <= 0 || gd_lv_args(mean_type, var_type)) return RHO_E_ARG;
+    if (batch > 65535) return RHO_E_SHAPE;
+    const int v = (per_sample & 3) == 0 ? 4 : 1;
+    const int64_t chunks = gd_hyb_chunks(batch, per_sample, v);      // <= gd_chunks(batch, per_sample): the workspace of the VLB pass fits
+    hipStream_t st = as_stream(stream);
+    dim3 grid((unsigned)chunks, (unsigned)batch);
+    const int em = mean_type == RHO_GD_EPSILON ? 1 : 0, rg = var_type == RHO_GD_LEARNED_RANGE ? 1 : 0;
+    if (v == 4)
+        hipLaunchKernelGGL(k_gd_hybrid_partial<4>, grid, dim3(GD_THREADS), 0, st, x_start, x_t, target, model_out, t, tab, table_len, em, rg,
+                           (double*)workspace, per_sample, err_flag);
+    else
+        hipLaunchKernelGGL(k_gd_hybrid_partial<1>, grid, dim3(GD_THREADS), 0, st, x_start, x_t, target, model_out, t, tab, table_len, em, rg,
+                           (double*)workspace, per_sample, err_flag);
+    hipLaunchKernelGGL(k_gd_hybrid_final, dim3((unsigned)batch), dim3(GD_THREADS), 0, st, (const double*)workspace, chunks, per_sample,
+                       rescaled ? 1 : 0, vb_scale, loss, mse, vb);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int rho_gd_hybrid_loss_bwd(const float* x_start, const float* x_t, const float* target, const float* model_out, const int64_t* t,
+                                      const float* tab, int64_t table_len, int mean_type, int var_type, int rescaled, float vb_scale,
+                                      const float* g_loss, const float* g_mse, const float* g_vb, float* grad, int64_t batch, int64_t per_sample,
+                                      int32_t* err_flag, void* stream) {
+    if (!x_start || !x_t || !target || !model_out || !t || !tab || !grad) return RHO_E_ARG;
+    if (batch <= 0 || per_sample <= 0 || table_len <= 0 || gd_lv_args(mean_type, var_type)) return RHO_E_ARG;
+    if (batch > 65535) return RHO_E_SHAPE;
+    const int v = (per_sample & 3) == 0 ? 4 : 1;
+    dim3 grid((unsigned)gd_hyb_chunks(batch, per_sample, v), (unsigned)batch);
+    hipStream_t st = as_stream(stream);
+    const int em = mean_type == RHO_GD_EPSILON ? 1 : 0, rg = var_type == RHO_GD_LEARNED_RANGE ? 1 : 0;
+    if (v == 4)
+        hipLaunchKernelGGL(k_gd_hybrid_bwd<4>, grid, dim3(GD_THREADS), 0, st, x_start, x_t, target, model_out, t, tab, table_len, em, rg,
+                           rescaled ? 1 : 0, vb_scale, g_loss, g_mse, g_vb, grad, per_sample, err_flag);
+    else
+        hipLaunchKernelGGL(k_gd_hybrid_bwd<1>, grid, dim3(GD_THREADS), 0, st, x_start, x_t, target, model_out, t, tab, table_len, em, rg,
+                           rescaled ? 1 : 0, vb_scale, g_loss, g_mse, g_vb, grad, per_sample, err_flag);
     RHO_LAUNCH_CHECK();
     return 0;
 }

@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void k_sel_init(uint32_t* __restrict__ ws, int
 }
 
 template <int PASS>
-__global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ x, int64_t N, int64_t B, uint32_t* __restrict__ ws) {
+__global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ x, int64_t N, int64_t stride, int64_t B, uint32_t* __restrict__ ws) {
     constexpr int SHIFT = 24 - 8 * PASS;
     __shared__ uint32_t h[2][SEL_BINS];
     const int b = blockIdx.y;
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ x, i
     const uint32_t p0 = st[0], p1 = st[1];
     const bool same = (PASS == 0) || ((p0 >> (SHIFT + 8)) == (p1 >> (SHIFT + 8)));   // both ranks still in one bucket
     __syncthreads();
-    const float* xb = x + (size_t)b * N;
+    const float* xb = x + (size_t)b * stride;
     auto tally = [&](float f) {
         const uint32_t key = __float_as_uint(f) & 0x7FFFFFFFu;
         const uint32_t bin = (key >> SHIFT) & 0xFFu;
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ x, i
     };
     const int64_t per = (N + gridDim.x - 1) / gridDim.x;
     int64_t i0 = (int64_t)blockIdx.x * per, i1 = i0 + per < N ? i0 + per : N;
-    if ((N & 3) == 0 && (per & 3) == 0) {                   // 16-byte pieces (rows are 16-byte aligned when N % 4 == 0)
+    if ((N & 3) == 0 && (stride & 3) == 0 && (per & 3) == 0) {     // 16-byte pieces (rows are 16-byte aligned when N, stride % 4 == 0)
         for (int64_t i = i0 + 4 * tid; i < i1; i += 4 * 256) {
             const float4 v = *reinterpret_cast<const float4*>(xb + i);
             tally(v.x); tally(v.y); tally(v.z); tally(v.w);
@@ -117,8 +117,9 @@ extern "C" int64_t rho_abs_quantile_workspace_bytes(int64_t batch) {
     return batch > 0 ? (int64_t)((sel_hist_words(batch) + (size_t)batch * 4) * sizeof(uint32_t)) : 0;
 }
 
-extern "C" int rho_abs_quantile(const float* x, int64_t batch, int64_t n, double q, void* workspace, float* out, void* stream) {
-    if (!x || !workspace || !out || batch <= 0 || n <= 0 || !(q >= 0.0 && q <= 1.0)) return RHO_E_ARG;
+namespace {
+int abs_quantile(const float* x, int64_t batch, int64_t n, int64_t stride, double q, void* workspace, float* out, void* stream) {
+    if (!x || !workspace || !out || batch <= 0 || n <= 0 || stride < n || !(q >= 0.0 && q <= 1.0)) return RHO_E_ARG;
     if (batch > 65535 || n >= (1LL << 32)) return RHO_E_SHAPE;
     // torch.quantile: ranks = q * (n - 1) evaluated in the tensor's dtype (float32), floor / ceil, weight = frac
     const float rank_f = (float)q * (float)(n - 1);
@@ -138,7 +139,7 @@ extern "C" int rho_abs_quantile(const float* x, int64_t batch, int64_t n, double
     if (nblk < 1) nblk = 1;
     dim3 gh((unsigned)nblk, (unsigned)batch), gp((unsigned)batch);
 #define RHO_SEL_PASS(P)                                                                      \
-    hipLaunchKernelGGL(k_sel_hist<P>, gh, dim3(256), 0, st, x, n, batch, ws);                \
+    hipLaunchKernelGGL(k_sel_hist<P>, gh, dim3(256), 0, st, x, n, stride, batch, ws);          \
     hipLaunchKernelGGL(k_sel_pick<P>, gp, dim3(256), 0, st, ws, batch, weight, out);
     RHO_SEL_PASS(0)
     RHO_SEL_PASS(1)
@@ -147,6 +148,17 @@ extern "C" int rho_abs_quantile(const float* x, int64_t batch, int64_t n, double
 #undef RHO_SEL_PASS
     RHO_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace
+
+extern "C" int rho_abs_quantile(const float* x, int64_t batch, int64_t n, double q, void* workspace, float* out, void* stream) {
+    return abs_quantile(x, batch, n, n, q, workspace, out, stream);
+}
+
+// the same over rows that start stride elements apart (the mean half of a learned-variance [B, 2C, ...] output: stride = 2n)
+extern "C" int rho_abs_quantile_strided(const float* x, int64_t batch, int64_t n, int64_t stride, double q, void* workspace, float* out,
+                                        void* stream) {
+    return abs_quantile(x, batch, n, stride, q, workspace, out, stream);
 }
 
 // DDIM update (gaussian_diffusion.py:654-702 with p_mean_variance :400-415 and _predict_eps_from_xstart :462-466),

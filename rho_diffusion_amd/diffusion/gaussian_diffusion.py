@@ -17,7 +17,8 @@ The per-step scalars (four table entries) are kernel arguments computed on the h
 noise (:1186 then :877) and the backbone output is regressed on the once-noised data.
 
 The rest of the reference class's public API (guided-diffusion's) is built on csrc/gaussian.hip, for the mean types START_X /
-EPSILON and the fixed variances: the distribution helpers (:277-510), ancestral sampling (:512-652), the DDIM loop with eta and
+EPSILON, the fixed variances and the learned ones (LEARNED / LEARNED_RANGE with a 2C-channel backbone, :368-383, whose output
+halves the kernels read in place; training_losses then returns the hybrid loss mse + vb, :893-930): the distribution helpers (:277-510), ancestral sampling (:512-652), the DDIM loop with eta and
 ``cond_fn`` (:654-702, :742-824), DDIM inversion (:704-740), the variational bound in bits per dimension (:826-859, :936-1009)
 and ``training_losses`` (:861-934).  Every kernel gathers per-sample rows of one packed float32 table (``_gd_table``) at a
 device ``t[B]``; the loops never synchronise with the host and poll the error flag once at the end.
@@ -71,7 +72,7 @@ class LossType(enum.Enum):
 
 
 def model_variance_tables(tables: Mapping[str, np.ndarray], var_type: ModelVarType):
-    """float64 (variance, log_variance) of a fixed variance type (:385-398); the learned types are not built."""
+    """float64 (variance, log_variance) of a fixed variance type (:385-398); a learned variance has no per-t table."""
     if var_type == ModelVarType.FIXED_LARGE:
         v = np.append(tables["posterior_variance"][1], tables["betas"][1:])
         return v, np.log(v)
@@ -90,8 +91,15 @@ def gd_table_rows(tables: Mapping[str, np.ndarray], var_type: ModelVarType) -> n
             "coef1": tables["posterior_mean_coef1"], "coef2": tables["posterior_mean_coef2"], "model_var": var, "model_logvar": logvar,
             "post_logvar": tables["posterior_log_variance_clipped"], "abar": ac, "abar_prev": tables["alphas_cumprod_prev"],
             "abar_next": tables["alphas_cumprod_next"], "sqrt_abar": tables["sqrt_alphas_cumprod"],
-            "log_1m_abar": tables["log_one_minus_alphas_cumprod"], "1m_abar": 1.0 - ac, "post_var": tables["posterior_variance"]}
+            "log_1m_abar": tables["log_one_minus_alphas_cumprod"], "1m_abar": 1.0 - ac, "post_var": tables["posterior_variance"],
+            "log_beta": np.log(tables["betas"])}
     return np.stack([np.asarray(rows[k], dtype=np.float64).astype(np.float32) for k in ops.GD_ROWS])
+
+
+def gd_table_rows_learned(tables: Mapping[str, np.ndarray]) -> np.ndarray:
+    """The packed table of the learned variances (:368-383): their rows are post_logvar (min_log) and log_beta (max_log); the
+    model_var / model_logvar rows are FIXED_LARGE's and unused there (a learned variance has no per-t table)."""
+    return gd_table_rows(tables, ModelVarType.FIXED_LARGE)
 
 
 def betas_for_alpha_bar(num_diffusion_timesteps: int, alpha_bar, max_beta: float = 0.999) -> np.ndarray:
@@ -254,6 +262,7 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         cc = self._preembed_conditions(cc)
 
         engine = self.backbone.engine() if hasattr(self.backbone, "engine") else None
+        learned, C = self._learned(), x_T.shape[1]
         t_dev = torch.full((1,), denoise_steps - 1, dtype=torch.int32, device=dev)
         quant = torch.empty(batch_size, dtype=torch.float32, device=dev)
         need = hip.lib().rho_abs_quantile_workspace_bytes(batch_size)
@@ -265,6 +274,8 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
                 x0_hat = engine.forward(x_t, None, cc, t_scalar_dev=t_dev)
             else:
                 x0_hat = self.backbone(x_t, torch.full((batch_size,), t, device=dev, dtype=torch.long), cc)
+            if learned:                   # rho_abs_quantile / rho_ddim_step read C channels: the mean half, one copy per step
+                x0_hat = x0_hat[:, :C]
             x0_hat = x0_hat.contiguous()
             c_recip, c_recipm1, sqrt_abp, coef_eps, sig = self.ddim_coefficients(t, eta)
             z = self.noise(x_t) if sig != 0.0 else None          # the reference draws it always; with eta = 0 it is multiplied by 0
@@ -294,6 +305,23 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         if key not in self._gd_tables:
             self._gd_tables[key] = torch.from_numpy(gd_table_rows(self.tables, self.model_var_type)).to(device).contiguous()
         return self._gd_tables[key]
+
+    def _learned(self) -> bool:
+        return self.model_var_type in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE)
+
+    def _var_code(self) -> int:
+        return ops.GD_LEARNED_RANGE if self.model_var_type == ModelVarType.LEARNED_RANGE else ops.GD_LEARNED
+
+    def _gd_table_learned(self, device) -> Tensor:
+        """Packed float32 table of the learned variances (min_log = post_logvar, max_log = log_beta rows)."""
+        key = (str(device), "learned")
+        if key not in self._gd_tables:
+            self._gd_tables[key] = torch.from_numpy(gd_table_rows_learned(self.tables)).to(device).contiguous()
+        return self._gd_tables[key]
+
+    def _tab(self, device) -> Tensor:
+        """The table every gd kernel of the current configuration reads."""
+        return self._gd_table_learned(device) if self._learned() else self._gd_table(device)
 
     def _gd_flag(self, device) -> Tensor:
         if self._gd_err is None or self._gd_err.device != torch.device(device):
@@ -342,11 +370,19 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
             out = model.engine().forward(x, None, kw.get("y"), t_scalar_dev=t_dev)
         else:
             out = model(x, self._scale_timesteps(t), **kw)
-        if tuple(out.shape) != tuple(x.shape):
-            raise NotImplementedError(f"model output {tuple(out.shape)} for x {tuple(x.shape)}: a learned-variance (2C-channel) backbone "
-                                      "(gaussian_diffusion.py:368-383) is not built")
+        self._check_output(out, x)
         hip.require_gpu(out, "model output")
         return out.float().contiguous()
+
+    def _check_output(self, out: Tensor, x: Tensor) -> None:
+        if self._learned():
+            want = (x.shape[0], 2 * x.shape[1], *x.shape[2:])
+            if tuple(out.shape) != want:                           # the reference asserts it (:369)
+                raise AssertionError(f"model output {tuple(out.shape)}: model_var_type {self.model_var_type.name} needs the 2C-channel "
+                                     f"output {want} (gaussian_diffusion.py:368-383)")
+        elif tuple(out.shape) != tuple(x.shape):
+            raise NotImplementedError(f"model output {tuple(out.shape)} for x {tuple(x.shape)}: a 2C-channel output needs a learned "
+                                      f"model_var_type (gaussian_diffusion.py:368-383), not {self.model_var_type.name}")
 
     def _scale_timesteps(self, t):
         """:468-471."""
@@ -376,6 +412,31 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         x0 = self._gd_x(denoised_fn(mo), "denoised_fn output")
         return x0, ops.GD_START_X, (self._quantile(x0) if clip_denoised else None)
 
+    def _x0_source_lv(self, x: Tensor, mo: Tensor, t: Tensor, tab: Tensor, clip_denoised: bool, denoised_fn):
+        """``_x0_source`` for a learned variance: (x0 source, variance values, mean code, quantile).  The two halves of the [B, 2C, ...]
+        output are read in place (views); x0 is materialised only where the reference needs it first (EPSILON with thresholding,
+        denoised_fn)."""
+        C = x.shape[1]
+        mean, var = mo[:, :C], mo[:, C:]
+        code = self._mean_code()
+        n = x.numel() // x.shape[0]
+        if denoised_fn is None and not (clip_denoised and code == ops.GD_EPSILON):
+            return mean, var, code, (self._quantile_rows(mean, n) if clip_denoised else None)
+        if code == ops.GD_EPSILON:
+            x0 = torch.empty_like(x)
+            ops.gd_posterior_step_lv(x, mean, var, t, tab, code, self._var_code(), None, None, None, None, x0, err_flag=self._gd_flag(x.device))
+            mean = x0
+        if denoised_fn is not None:
+            mean = self._gd_x(denoised_fn(mean), "denoised_fn output")
+        return mean, var, ops.GD_START_X, (self._quantile_rows(mean, n) if clip_denoised else None)
+
+    def _quantile_rows(self, x: Tensor, n: int) -> Tensor:
+        B = x.shape[0]
+        need = hip.lib().rho_abs_quantile_workspace_bytes(B)
+        if self._quant_ws is None or self._quant_ws.device != x.device or self._quant_ws.numel() * 4 < need:
+            self._quant_ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=x.device)
+        return ops.abs_quantile_rows(x, self.dynamic_thresholding_percentile, n, workspace=self._quant_ws)
+
     def _cond_grad(self, cond_fn, x: Tensor, t: Tensor, model_kwargs) -> Tensor:
         g = cond_fn(x, self._scale_timesteps(t), **(model_kwargs or {}))
         return self._gd_x(g, "cond_fn output")
@@ -385,7 +446,7 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         """:277-292: (mean, variance, log_variance) of q(x_t | x_0)."""
         x = self._gd_x(x_start, "x_start")
         t = self._gd_t(t, x.shape[0], x.device)
-        tab = self._gd_table(x.device)
+        tab = self._tab(x.device)
         mean = ops.gd_affine(x, None, t, tab, "sqrt_abar", None, "ax", err_flag=self._gd_flag(x.device))
         return mean, self._gd_view(tab, "1m_abar", t, x.shape), self._gd_view(tab, "log_1m_abar", t, x.shape)
 
@@ -394,7 +455,7 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         assert x_start.shape == x_t.shape
         xs, xt = self._gd_x(x_start, "x_start"), self._gd_x(x_t, "x_t")
         t = self._gd_t(t, xs.shape[0], xs.device)
-        tab = self._gd_table(xs.device)
+        tab = self._tab(xs.device)
         mean = ops.gd_affine(xs, xt, t, tab, "coef1", "coef2", "ax+by", err_flag=self._gd_flag(xs.device))
         return mean, self._gd_view(tab, "post_var", t, xs.shape), self._gd_view(tab, "post_logvar", t, xs.shape)
 
@@ -403,14 +464,14 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         assert x_t.shape == eps.shape
         x = self._gd_x(x_t, "x_t")
         t = self._gd_t(t, x.shape[0], x.device)
-        return ops.gd_affine(x, self._gd_x(eps, "eps"), t, self._gd_table(x.device), "sqrt_recip", "sqrt_recipm1", "ax-by",
+        return ops.gd_affine(x, self._gd_x(eps, "eps"), t, self._tab(x.device), "sqrt_recip", "sqrt_recipm1", "ax-by",
                              err_flag=self._gd_flag(x.device))
 
     def _predict_eps_from_xstart(self, x_t: Tensor, t: Tensor, pred_xstart: Tensor) -> Tensor:
         """:462-466."""
         x = self._gd_x(x_t, "x_t")
         t = self._gd_t(t, x.shape[0], x.device)
-        return ops.gd_affine(x, self._gd_x(pred_xstart, "pred_xstart"), t, self._gd_table(x.device), "sqrt_recip", "sqrt_recipm1",
+        return ops.gd_affine(x, self._gd_x(pred_xstart, "pred_xstart"), t, self._tab(x.device), "sqrt_recip", "sqrt_recipm1",
                              "(ax-y)/b", err_flag=self._gd_flag(x.device))
 
     def p_mean_variance(self, model, x: Tensor, t: Tensor, clip_denoised: bool = True, denoised_fn=None, model_kwargs=None) -> dict:
@@ -419,8 +480,14 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         x = self._gd_x(x, "x")
         B = x.shape[0]
         t = self._gd_t(t, B, x.device)
-        tab = self._gd_table(x.device)
+        tab = self._tab(x.device)
         mo = self._gd_model(model, x, t, self._gd_model_kwargs(model_kwargs))
+        if self._learned():
+            src, var, code, q = self._x0_source_lv(x, mo, t, tab, clip_denoised, denoised_fn)
+            mean, px, v, lv = (torch.empty_like(x) for _ in range(4))
+            ops.gd_posterior_step_lv(x, src, var, t, tab, code, self._var_code(), q, None, None, mean, px, v, lv,
+                                     err_flag=self._gd_flag(x.device))
+            return {"mean": mean, "variance": v, "log_variance": lv, "pred_xstart": px}
         src, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
         mean, px = torch.empty_like(x), torch.empty_like(x)
         ops.gd_posterior_step(x, src, t, tab, code, q, None, None, mean, px, err_flag=self._gd_flag(x.device))
@@ -432,9 +499,14 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         (bit-equal to the "mean" p_mean_variance returns for it)."""
         x = self._gd_x(x, "x")
         t = self._gd_t(t, x.shape[0], x.device)
-        tab = self._gd_table(x.device)
+        tab = self._tab(x.device)
         g = self._cond_grad(cond_fn, x, t, model_kwargs)
         out = torch.empty_like(x)
+        if self._learned():                  # variance per element: exp of p_mean_var's log_variance (bit-equal to its "variance")
+            ops.gd_posterior_step_lv(x, self._gd_x(p_mean_var["pred_xstart"], "pred_xstart"), self._gd_x(p_mean_var["log_variance"],
+                                     "log_variance"), t, tab, ops.GD_START_X, ops.GD_LEARNED, None, g, None, out, None,
+                                     err_flag=self._gd_flag(x.device))
+            return out
         ops.gd_posterior_step(x, self._gd_x(p_mean_var["pred_xstart"], "pred_xstart"), t, tab, ops.GD_START_X, None, g, None, out, None,
                               err_flag=self._gd_flag(x.device))
         return out
@@ -443,7 +515,7 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         """:488-510: eps = eps(pred_xstart) - sqrt(1 - abar) * cond_fn(x, t); pred_xstart and mean re-derived from it."""
         x = self._gd_x(x, "x")
         t = self._gd_t(t, x.shape[0], x.device)
-        tab = self._gd_table(x.device)
+        tab = self._tab(x.device)
         g = self._cond_grad(cond_fn, x, t, model_kwargs)
         px, scratch = torch.empty_like(x), torch.empty_like(x)
         flag = self._gd_flag(x.device)
@@ -456,8 +528,14 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
 
     # ---- ancestral sampling
     def _p_step(self, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, kw, sample, px, t_dev=None) -> dict:
-        tab = self._gd_table(x.device)
+        tab = self._tab(x.device)
         mo = self._gd_model(model, x, t, kw, t_dev)
+        if self._learned():
+            src, var, code, q = self._x0_source_lv(x, mo, t, tab, clip_denoised, denoised_fn)
+            noise = self.noise(x)
+            g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
+            ops.gd_posterior_step_lv(x, src, var, t, tab, code, self._var_code(), q, g, noise, sample, px, err_flag=self._gd_flag(x.device))
+            return {"sample": sample, "pred_xstart": px}
         src, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
         noise = self.noise(x)                                                  # :545, drawn before cond_fn runs
         g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
@@ -530,8 +608,14 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
 
     # ---- DDIM
     def _ddim_step(self, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, kw, eta, reverse, sample, px, t_dev=None) -> dict:
-        tab = self._gd_table(x.device)
+        tab = self._tab(x.device)
         mo = self._gd_model(model, x, t, kw, t_dev)
+        if self._learned():                  # the variance half is ignored, as the reference's ddim_sample does
+            src, _, code, q = self._x0_source_lv(x, mo, t, tab, clip_denoised, denoised_fn)
+            g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
+            noise = self.noise(x) if (not reverse and eta != 0.0) else None
+            ops.gd_ddim_step_strided(x, src, t, tab, code, q, g, noise, eta, reverse, sample, px, err_flag=self._gd_flag(x.device))
+            return {"sample": sample, "pred_xstart": px}
         src, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
         g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
         # :685: the reference draws the noise at every step; with eta = 0 it is multiplied by 0 and no used draw follows it
@@ -583,10 +667,15 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
     # ---- variational bound
     def _vb_step(self, model, x_start, x_t, t, clip_denoised, kw, vb, xstart_mse=None, mse=None, noise=None, raw_kl=None, raw_nll=None,
                  px=None, t_dev=None):
-        tab = self._gd_table(x_start.device)
+        tab = self._tab(x_start.device)
         mo = self._gd_model(model, x_t, t, kw, t_dev)
-        src, code, q = self._x0_source(x_t, mo, t, tab, clip_denoised, None)
         self._gd_ws = ops.gd_workspace(x_start.shape[0], x_start.numel() // x_start.shape[0], x_start.device, self._gd_ws)
+        if self._learned():
+            src, var, code, q = self._x0_source_lv(x_t, mo, t, tab, clip_denoised, None)
+            ops.gd_vlb_terms_lv(x_start, x_t, src, var, t, tab, code, self._var_code(), q, noise, vb, xstart_mse, mse, raw_kl, raw_nll, px,
+                                workspace=self._gd_ws, err_flag=self._gd_flag(x_start.device))
+            return
+        src, code, q = self._x0_source(x_t, mo, t, tab, clip_denoised, None)
         ops.gd_vlb_terms(x_start, x_t, src, t, tab, code, q, noise, vb, xstart_mse, mse, raw_kl, raw_nll, px, workspace=self._gd_ws,
                          err_flag=self._gd_flag(x_start.device))
 
@@ -616,7 +705,7 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         xs = self._gd_x(x_start, "x_start")
         out = torch.empty(xs.shape[0], dtype=torch.float32, device=xs.device)
         self._gd_ws = ops.gd_workspace(xs.shape[0], xs.numel() // xs.shape[0], xs.device, self._gd_ws)
-        ops.gd_vlb_terms(xs, None, None, None, self._gd_table(xs.device), ops.GD_START_X, None, None, out, prior=True, workspace=self._gd_ws)
+        ops.gd_vlb_terms(xs, None, None, None, self._tab(xs.device), ops.GD_START_X, None, None, out, prior=True, workspace=self._gd_ws)
         return out
 
     @torch.no_grad()
@@ -646,13 +735,16 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
     # ---- training loss
     def training_losses(self, model, x_start: Tensor, t: Tensor, model_kwargs={}, noise: Tensor = None) -> dict:
         """:861-934 for MSE / RESCALED_MSE (equal without a learned variance): {"loss", "mse"}, [N] each, differentiable through
-        the backbone.  The target is x_start (START_X) or the noise (EPSILON)."""
+        the backbone.  The target is x_start (START_X) or the noise (EPSILON).  With a learned variance (2C-channel output) also "vb"
+        and loss = mse + vb: the hybrid objective, the VLB reaching only the variance half."""
         if self.loss_type.is_vb():
             raise NotImplementedError(f"loss_type {self.loss_type}: the variational-bound training loss (gaussian_diffusion.py:877-889) "
                                       "is not built; the pipeline's fixed configuration (:211-216) uses MSE")
         if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE):
             raise NotImplementedError(self.loss_type)
-        model_variance_tables(self.tables, self.model_var_type)                    # refuses the learned variances (:368-383)
+        learned = self._learned()
+        if not learned:
+            model_variance_tables(self.tables, self.model_var_type)
         code = self._mean_code()
         xs = self._gd_x(x_start, "x_start")
         t = self._gd_t(t, xs.shape[0], xs.device)
@@ -662,10 +754,16 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         noise = self._gd_x(noise, "noise")
         x_t = self.q_sample(xs, t, noise=noise)
         out = model(x_t, self._scale_timesteps(t), **(model_kwargs or {}))
-        if tuple(out.shape) != tuple(xs.shape):
-            raise NotImplementedError(f"model output {tuple(out.shape)} for x {tuple(xs.shape)}: learned variances (:368-383) are not built")
-        from ..autograd import mse_per_sample
+        self._check_output(out, xs)
         target = xs if code == ops.GD_START_X else noise
+        if learned:
+            # :893-930: mse on the mean half, vb = _vb_terms_bpd on (mean.detach(), variance), clip_denoised=False; one fused pass
+            from ..autograd import hybrid_loss
+            hip.require_gpu(out, "model output")
+            scale = self.timesteps / 1000.0 if self.loss_type == LossType.RESCALED_MSE else None
+            loss, mse, vb = hybrid_loss(out, xs, x_t, target, t, self._tab(xs.device), code, self._var_code(), scale, self._gd_flag(xs.device))
+            return {"vb": vb, "mse": mse, "loss": loss}
+        from ..autograd import mse_per_sample
         mse = mse_per_sample(out, target)
         return {"mse": mse, "loss": mse}
 
@@ -678,7 +776,9 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
             shape = [int(x) for x in self.data_shape]
             shape[0] = self.sampling_batch_size
         else:
-            shape = [self.sampling_batch_size, self.backbone_kwargs["out_channels"]] + list(self.backbone_kwargs["data_shape"])
+            # the reference takes out_channels (:1113), which is 2C with a learned variance: the samples have in_channels
+            ch = self.backbone_kwargs["in_channels" if self._learned() else "out_channels"]
+            shape = [self.sampling_batch_size, ch] + list(self.backbone_kwargs["data_shape"])
             self.data_dtype = torch.float32
         dev = next(self.backbone.parameters()).device
         if parameter_space is None:
@@ -705,6 +805,13 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         self.data_dtype = data.dtype
         t = self.random_timesteps(data.size(0)).to(data.device)
         x_data, noise = self.forward_process(data, t)
+        if self._learned():
+            # learned variance: the reference as written (:1186-1197), training_losses on the noised data ["loss"].mean()
+            self._tick_error_poll()
+            kw = {"y": labels} if labels is not None else {}
+            loss = self.training_losses(self.backbone, x_data, t, kw, noise)["loss"].mean()
+            self.log("train_loss", loss, prog_bar=True)
+            return loss
         x_t = self.q_sample(x_data, t, noise=noise)
         self._tick_error_poll()
         if labels is not None:

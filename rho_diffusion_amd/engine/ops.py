@@ -95,9 +95,10 @@ def ddim_step(x_t: Tensor, model_out: Tensor, quantile: Tensor, noise: Optional[
 
 # GaussianDiffusionPipeline API (csrc/gaussian.hip): rows of the packed per-timestep table (include/rho_hip.h RHO_GD_*)
 GD_ROWS = ("sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "model_var", "model_logvar", "post_logvar", "abar", "abar_prev", "abar_next",
-           "sqrt_abar", "log_1m_abar", "1m_abar", "post_var")
+           "sqrt_abar", "log_1m_abar", "1m_abar", "post_var", "log_beta")
 GD_ROW = {k: i for i, k in enumerate(GD_ROWS)}
 GD_START_X, GD_EPSILON = 0, 1
+GD_LEARNED, GD_LEARNED_RANGE = 0, 1         # var_type of the learned-variance entry points
 GD_AFFINE_OPS = {"ax": 0, "ax+by": 1, "ax-by": 2, "(ax-y)/b": 3}
 
 
@@ -217,6 +218,125 @@ def gd_mse_per_sample_bwd(target: Tensor, out: Tensor, g: Tensor) -> Tensor:
         raise RhoHipError("g must be float32 [B]")
     grad = torch.empty_like(out)
     check(hip.lib().rho_gd_mse_per_sample_bwd(ptr(target), ptr(out), ptr(g), ptr(grad), B, n, stream()), "rho_gd_mse_per_sample_bwd")
+    return grad
+
+
+def _gd_rows(v: Tensor, name: str, batch: int, n: int) -> int:
+    """Per-sample stride of ``v``: a float32 GPU tensor whose sample b is the contiguous block of n elements at v[b] (a contiguous
+    tensor, or one half of a contiguous [B, 2C, ...] learned-variance output sliced along dim 1)."""
+    hip.require_gpu(v, name)
+    if v.dtype != torch.float32 or v.dim() < 1 or v.shape[0] != batch or v[0].numel() != n or not v[0].is_contiguous():
+        raise RhoHipError(f"{name} must be float32 [{batch}, ...] with {n} contiguous elements per sample, got {v.dtype} {tuple(v.shape)} "
+                          f"strides {v.stride()}")
+    return v.stride(0) if batch > 1 else n
+
+
+def abs_quantile_rows(x: Tensor, q: float, n: int, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """abs_quantile over the n-element rows of a strided per-sample view (the mean half of a learned-variance output), in place."""
+    B = x.shape[0]
+    stride = _gd_rows(x, "x", B, n)
+    need = hip.lib().rho_abs_quantile_workspace_bytes(B)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty((need + 3) // 4, dtype=torch.int32, device=x.device)
+    out = torch.empty(B, dtype=torch.float32, device=x.device) if out is None else out
+    check(hip.lib().rho_abs_quantile_strided(ptr(x), B, n, stride, float(q), ptr(workspace), ptr(out), stream()), "rho_abs_quantile_strided")
+    return out
+
+
+def gd_ddim_step_strided(x_t: Tensor, model_out: Tensor, t: Tensor, tab: Tensor, mean_type: int, quantile: Optional[Tensor],
+                         grad: Optional[Tensor], noise: Optional[Tensor], eta: float, reverse: bool, sample: Tensor,
+                         pred_xstart: Optional[Tensor], err_flag: Optional[Tensor] = None) -> Tensor:
+    """gd_ddim_step with ``model_out`` any per-sample view of x_t's per-sample size (rho_gd_ddim_step_strided)."""
+    _f32c(x_t, "x_t")
+    _same(x_t, ("grad", grad), ("noise", noise), ("sample", sample), ("pred_xstart", pred_xstart))
+    B, n = x_t.shape[0], x_t.numel() // x_t.shape[0]
+    stride = _gd_rows(model_out, "model_out", B, n)
+    if quantile is not None and (_f32c(quantile, "quantile").numel() != B):
+        raise RhoHipError("quantile must be float32 [B]")
+    check(hip.lib().rho_gd_ddim_step_strided(ptr(x_t), ptr(model_out), stride, ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab), mean_type,
+                                             ptr(quantile), ptr(grad), ptr(noise), float(eta), 1 if reverse else 0, ptr(sample),
+                                             ptr(pred_xstart), B, n, ptr(err_flag), stream()), "rho_gd_ddim_step_strided")
+    return sample
+
+
+def gd_posterior_step_lv(x_t: Tensor, model_out: Tensor, var_values: Tensor, t: Tensor, tab: Tensor, mean_type: int, var_type: int,
+                         quantile: Optional[Tensor], grad: Optional[Tensor], noise: Optional[Tensor], out: Optional[Tensor],
+                         pred_xstart: Optional[Tensor], variance: Optional[Tensor] = None, log_variance: Optional[Tensor] = None,
+                         err_flag: Optional[Tensor] = None) -> Optional[Tensor]:
+    """p_mean_variance / condition_mean / p_sample with a learned variance, one pass (rho_gd_posterior_step_lv).  ``model_out`` (the
+    mean half or an x0) and ``var_values`` are per-sample views read in place."""
+    _f32c(x_t, "x_t")
+    _same(x_t, ("grad", grad), ("noise", noise), ("out", out), ("pred_xstart", pred_xstart), ("variance", variance),
+          ("log_variance", log_variance))
+    B, n = x_t.shape[0], x_t.numel() // x_t.shape[0]
+    ms, vs = _gd_rows(model_out, "model_out", B, n), _gd_rows(var_values, "var_values", B, n)
+    if quantile is not None and (_f32c(quantile, "quantile").numel() != B):
+        raise RhoHipError("quantile must be float32 [B]")
+    check(hip.lib().rho_gd_posterior_step_lv(ptr(x_t), ptr(model_out), ms, ptr(var_values), vs, ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab),
+                                             mean_type, var_type, ptr(quantile), ptr(grad), ptr(noise), ptr(out), ptr(pred_xstart),
+                                             ptr(variance), ptr(log_variance), B, n, ptr(err_flag), stream()), "rho_gd_posterior_step_lv")
+    return out
+
+
+def gd_vlb_terms_lv(x_start: Tensor, x_t: Tensor, model_out: Tensor, var_values: Tensor, t: Tensor, tab: Tensor, mean_type: int,
+                    var_type: int, quantile: Optional[Tensor], noise: Optional[Tensor], vb: Tensor, xstart_mse: Optional[Tensor] = None,
+                    mse: Optional[Tensor] = None, raw_kl: Optional[Tensor] = None, raw_nll: Optional[Tensor] = None,
+                    pred_xstart: Optional[Tensor] = None, workspace: Optional[Tensor] = None, err_flag: Optional[Tensor] = None) -> Tensor:
+    """gd_vlb_terms with a learned variance (rho_gd_vlb_terms_lv); ``model_out`` / ``var_values`` per-sample views read in place."""
+    _f32c(x_start, "x_start")
+    _same(x_start, ("x_t", x_t), ("noise", noise), ("pred_xstart", pred_xstart))
+    B, n = x_start.shape[0], x_start.numel() // x_start.shape[0]
+    ms, vs = _gd_rows(model_out, "model_out", B, n), _gd_rows(var_values, "var_values", B, n)
+    stride = vb.stride(0) if vb.dim() == 1 else 1
+    for name, o in (("vb", vb), ("xstart_mse", xstart_mse), ("mse", mse)):
+        if o is not None and (o.dtype != torch.float32 or not o.is_cuda or o.dim() != 1 or o.numel() != B or (B > 1 and o.stride(0) != stride)):
+            raise RhoHipError(f"{name} must be float32 [B] on the GPU with vb's stride")
+    for name, o in (("raw_kl", raw_kl), ("raw_nll", raw_nll), ("quantile", quantile)):
+        if o is not None and (_f32c(o, name).numel() != B):
+            raise RhoHipError(f"{name} must be float32 [B]")
+    ws = gd_workspace(B, n, x_start.device, workspace)
+    check(hip.lib().rho_gd_vlb_terms_lv(ptr(x_start), ptr(x_t), ptr(model_out), ms, ptr(var_values), vs, ptr(_gd_t(t, B)), ptr(tab),
+                                        _gd_tab(tab), mean_type, var_type, ptr(quantile), ptr(noise), ptr(vb), ptr(xstart_mse), ptr(mse),
+                                        max(stride, 1), ptr(raw_kl), ptr(raw_nll), ptr(pred_xstart), ptr(ws), B, n, ptr(err_flag),
+                                        stream()), "rho_gd_vlb_terms_lv")
+    return vb
+
+
+def _gd_hybrid_args(x_start: Tensor, x_t: Tensor, target: Tensor, model_out: Tensor):
+    _f32c(x_start, "x_start")
+    _same(x_start, ("x_t", x_t), ("target", target))
+    _f32c(model_out, "model_out")
+    B, n = x_start.shape[0], x_start.numel() // x_start.shape[0]
+    if model_out.shape[0] != B or model_out.numel() != 2 * B * n:
+        raise RhoHipError(f"model_out must be float32 [B, 2C, ...] for x_start {tuple(x_start.shape)}, got {tuple(model_out.shape)}")
+    return B, n
+
+
+def gd_hybrid_loss(x_start: Tensor, x_t: Tensor, target: Tensor, model_out: Tensor, t: Tensor, tab: Tensor, mean_type: int, var_type: int,
+                   vb_scale: Optional[float], workspace: Optional[Tensor] = None, err_flag: Optional[Tensor] = None):
+    """training_losses' hybrid objective with a learned variance (rho_gd_hybrid_loss): (loss, mse, vb), float32 [B] each.
+    ``vb_scale``: T/1000 for RESCALED_MSE, None for MSE."""
+    B, n = _gd_hybrid_args(x_start, x_t, target, model_out)
+    loss, mse, vb = (torch.empty(B, dtype=torch.float32, device=x_start.device) for _ in range(3))
+    ws = gd_workspace(B, n, x_start.device, workspace)
+    check(hip.lib().rho_gd_hybrid_loss(ptr(x_start), ptr(x_t), ptr(target), ptr(model_out), ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab),
+                                       mean_type, var_type, 0 if vb_scale is None else 1, float(vb_scale or 0.0), ptr(loss), ptr(mse),
+                                       ptr(vb), ptr(ws), B, n, ptr(err_flag), stream()), "rho_gd_hybrid_loss")
+    return loss, mse, vb
+
+
+def gd_hybrid_loss_bwd(x_start: Tensor, x_t: Tensor, target: Tensor, model_out: Tensor, t: Tensor, tab: Tensor, mean_type: int,
+                       var_type: int, vb_scale: Optional[float], g_loss: Optional[Tensor], g_mse: Optional[Tensor], g_vb: Optional[Tensor],
+                       err_flag: Optional[Tensor] = None) -> Tensor:
+    """d(loss, mse, vb) / d model_out [B, 2C, ...] (rho_gd_hybrid_loss_bwd); an upstream gradient of None counts as 0."""
+    B, n = _gd_hybrid_args(x_start, x_t, target, model_out)
+    for name, o in (("g_loss", g_loss), ("g_mse", g_mse), ("g_vb", g_vb)):
+        if o is not None and _f32c(o, name).numel() != B:
+            raise RhoHipError(f"{name} must be float32 [B]")
+    grad = torch.empty_like(model_out)
+    check(hip.lib().rho_gd_hybrid_loss_bwd(ptr(x_start), ptr(x_t), ptr(target), ptr(model_out), ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab),
+                                           mean_type, var_type, 0 if vb_scale is None else 1, float(vb_scale or 0.0), ptr(g_loss),
+                                           ptr(g_mse), ptr(g_vb), ptr(grad), B, n, ptr(err_flag), stream()), "rho_gd_hybrid_loss_bwd")
     return grad
 
 
