@@ -393,6 +393,37 @@ int64_t rho_sph_harm_workspace_bytes(int64_t batch, int64_t grid);
 int rho_sph_harm_fields(const int32_t* lm, int64_t batch, int64_t grid, float* out, void* workspace, const double* minmax_in,
                         double* minmax_out, void* stream);
 
+/* ------------------------------------------------------------------ image datasets */
+
+/* Storage dtypes of rho_crop_resize's raw images besides RHO_F32 (additive: the engine dtype codes above are unchanged). */
+#define RHO_U8 2
+#define RHO_F64 3
+
+/* HOST function (host arrays, no device memory, no stream): the taps of one axis of CenterCrop(crop) followed by a bilinear
+ * resize to out_size - torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=antialias), what
+ * torchvision's tensor Resize calls (antialias: the triangle filter of _upsample_bilinear2d_aa).  The index and weight arithmetic is
+ * torch's CPU kernels' for a float32 image (float32 scale and source index), so every weight equals torch's.  The crop follows
+ * torchvision: offset int(round((in - crop) / 2)) (half to even), or a zero padding of (crop - in) // 2 in front when the crop is
+ * larger.  Output o reads pixels start[o] .. start[o] + k - 1 with weights weight[o * k + j]; taps on the padding are dropped (a
+ * padded pixel is 0), every window lies inside [0, in_size) and start[] is non-decreasing.  start == weight == NULL: returns k
+ * only; else fills start[out_size] and weight[out_size * k] and returns k.  RHO_E_ARG on bad sizes. */
+int64_t rho_crop_resize_taps(int64_t in_size, int64_t crop, int64_t out_size, int antialias, int32_t* start, float* weight);
+
+/* DeepGalaxyDataset's default per-item transform for a batch, one launch (rho_diffusion/data/deep_galaxy.py:79-89 CenterCrop(256),
+ * Resize((128, 128)), 2 t - 1; :126 swapaxes(1, 3) + float32; :283-289 images / np.max(images)):
+ *   v(y, x) = raw[index[b], x, y, ch] / rowmax[index[b]]    numpy's promotion: RHO_U8 / RHO_F64 divide in float64 and round to
+ *             float32 once, RHO_F32 divides in float32 (IEEE division, no reciprocal)
+ *   out[b, ch, oy, ox] = 2 * sum_j wx[ox * kx + j] * sum_i wy[oy * ky + i] * v(ys[oy] + i, xs[ox] + j) - 1
+ * raw: [n, h, w, c] contiguous and 16-byte aligned, dtype RHO_U8 / RHO_F32 / RHO_F64, c <= 4.  After the swap the image rows y
+ * run along the w axis and its columns x along the h axis.  index: int64 [batch] on the device; rowmax: float64 [n], the maximum
+ * of the camera dataset each row came from.  (ys, wy, ky) = rho_crop_resize_taps(w, crop_h, out_h, aa, ...) and (xs, wx, kx) =
+ * rho_crop_resize_taps(h, crop_w, out_w, aa, ...), copied to the device; crop_h / crop_w only bound the tile windows.  out: float32
+ * [batch, c, out_h, out_w].  An index outside [0, n) sets *err_flag |= 4 (optional flag) and leaves that item's output unwritten;
+ * tables wider than crop_h allows set *err_flag |= 8 and leave the tile unwritten. */
+int rho_crop_resize(const void* raw, int dtype, int64_t n, int64_t h, int64_t w, int64_t c, const int64_t* index, int64_t batch,
+                    const double* rowmax, const int32_t* ys, const float* wy, int64_t ky, const int32_t* xs, const float* wx, int64_t kx,
+                    int64_t crop_h, int64_t crop_w, int64_t out_h, int64_t out_w, float* out, int32_t* err_flag, void* stream);
+
 /* ------------------------------------------------------------------ attention */
 
 /* Flash-style self attention, fp32 online softmax (QKVAttentionLegacy / QKVAttention,

@@ -12,10 +12,10 @@ from typing import List, Sequence, Tuple
 
 import torch
 
-from . import hip
-from .engine import ops
-from .registry import registry
-from .utils import calculate_sha512_embedding
+from .. import hip
+from ..engine import ops
+from ..registry import registry
+from ..utils import calculate_sha512_embedding
 
 __all__ = ["spherical_harmonic_fields", "spherical_harmonic_field", "SphericalHarmonicPool", "SphericalHarmonicDataset"]
 
@@ -114,7 +114,7 @@ class SphericalHarmonicDataset(torch.utils.data.Dataset):
 
     def __len__(self) -> int:
         if self.h5_path:
-            from . import h5io
+            from .. import h5io
             return h5io.shape(self.h5_path, "density")[0]
         return self.length
 
@@ -126,7 +126,7 @@ class SphericalHarmonicDataset(torch.utils.data.Dataset):
 
     def _replay(self, index) -> Tuple[torch.Tensor, list]:
         """Rows ``index`` (int or unit-stride slice) of the file: densities [n, 1, G, G, G] on the device + their (l, m)."""
-        from . import h5io
+        from .. import h5io
         import numpy as np
         d = h5io.read(self.h5_path, "density", index)
         l = np.atleast_1d(h5io.read(self.h5_path, "l", index))
@@ -163,7 +163,7 @@ class SphericalHarmonicDataset(torch.utils.data.Dataset):
         indexes its item tuples by string and cannot run; this is the file its reader :285-289 expects.)"""
         from pathlib import Path
         import numpy as np
-        from . import h5io
+        from .. import h5io
         path = Path(h5_path).with_suffix(".h5")
         n = self.length if not self.h5_path else len(self)
         dens, ls, ms = [], [], []

@@ -469,6 +469,83 @@ def sph_harm_fields(lm: Tensor, grid: int, out: Optional[Tensor] = None, minmax_
     return out
 
 
+# ----------------------------------------------------------------------------- image datasets
+RAW_DTYPES = {torch.float32: 0, torch.uint8: 2, torch.float64: 3}          # RHO_F32 / RHO_U8 / RHO_F64 of include/rho_hip.h
+
+
+def _pair(v) -> Tuple[int, int]:
+    return (int(v), int(v)) if isinstance(v, (int,)) else (int(v[0]), int(v[1]))
+
+
+def crop_resize_axis_taps(in_size: int, crop: int, out_size: int, antialias: bool):
+    """(start int32 [out_size], weight float32 [out_size, k]) of one axis: CenterCrop + bilinear resize (rho_crop_resize_taps, host)."""
+    import numpy as np
+    L = hip.lib()
+    k = int(L.rho_crop_resize_taps(int(in_size), int(crop), int(out_size), int(bool(antialias)), None, None))
+    if k <= 0:
+        raise RhoHipError(f"rho_crop_resize_taps(in={in_size}, crop={crop}, out={out_size}) failed: {k}")
+    start = np.empty(int(out_size), dtype=np.int32)
+    weight = np.empty((int(out_size), k), dtype=np.float32)
+    L.rho_crop_resize_taps(int(in_size), int(crop), int(out_size), int(bool(antialias)), start.ctypes.data, weight.ctypes.data)
+    return torch.from_numpy(start), torch.from_numpy(weight)
+
+
+def crop_resize_taps(h: int, w: int, crop, size, antialias: bool = True, device=None) -> dict:
+    """Device tap tables of CenterCrop(crop) + Resize(size) for raw images [N, h, w, C] (image rows = the w axis after
+    swapaxes(1, 3)): build once per geometry and pass to ``crop_resize``."""
+    (ch, cw), (oh, ow) = _pair(crop), _pair(size)
+    ys, wy = crop_resize_axis_taps(w, ch, oh, antialias)
+    xs, wx = crop_resize_axis_taps(h, cw, ow, antialias)
+    return dict(hw=(int(h), int(w)), crop=(ch, cw), size=(oh, ow), antialias=bool(antialias),
+                y=(ys.to(device), wy.to(device), wy.shape[1]), x=(xs.to(device), wx.to(device), wx.shape[1]))
+
+
+def crop_resize_check(flag: Tensor) -> None:
+    """Host poll of rho_crop_resize's error flag (one synchronisation)."""
+    v = int(flag.item())
+    if v:
+        flag.zero_()
+        if v & 4:
+            raise RhoHipError("crop_resize: an index lies outside [0, N) (rho_crop_resize err_flag bit 2)")
+        raise RhoHipError(f"crop_resize: the tap tables do not match the launch geometry (err_flag {v})")
+
+
+def crop_resize(raw: Tensor, rowmax: Tensor, index: Tensor, crop, size, antialias: bool = True, taps: Optional[dict] = None,
+                out: Optional[Tensor] = None, err_flag: Optional[Tensor] = None) -> Tensor:
+    """Rows ``index`` of the resident raw images [N, H, W, C] (uint8 / float32 / float64) -> float32 [B, C, size[0], size[1]]:
+    rows / rowmax in numpy's promotion, swapaxes to [C, W, H], CenterCrop(crop), bilinear Resize(size) (antialias: torch's
+    triangle filter), 2 t - 1 - one launch (rho_crop_resize).  ``rowmax``: float64 [N] on the device.  Without ``err_flag`` the
+    call polls its own flag and raises on an index outside [0, N); with one, the caller polls (``crop_resize_check``)."""
+    hip.require_gpu(raw, "raw")
+    if raw.dtype not in RAW_DTYPES or raw.dim() != 4 or not raw.is_contiguous():
+        raise RhoHipError(f"raw must be a contiguous uint8 / float32 / float64 [N, H, W, C] tensor, got {raw.dtype} {tuple(raw.shape)}")
+    N, H, W, Cc = raw.shape
+    if rowmax.dtype != torch.float64 or tuple(rowmax.shape) != (N,) or not rowmax.is_cuda or not rowmax.is_contiguous():
+        raise RhoHipError(f"rowmax must be a contiguous float64 [{N}] GPU tensor")
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_cuda or not index.is_contiguous():
+        raise RhoHipError("index must be a contiguous int64 [B] GPU tensor")
+    (ch, cw), (oh, ow) = _pair(crop), _pair(size)
+    if taps is None:
+        taps = crop_resize_taps(H, W, (ch, cw), (oh, ow), antialias, raw.device)
+    elif taps["hw"] != (H, W) or taps["crop"] != (ch, cw) or taps["size"] != (oh, ow) or taps["antialias"] != bool(antialias):
+        raise RhoHipError(f"crop_resize: taps were built for {taps['hw']} crop {taps['crop']} size {taps['size']} antialias "
+                          f"{taps['antialias']}, the call asks for {(H, W)} crop {(ch, cw)} size {(oh, ow)} antialias {bool(antialias)}")
+    B = index.numel()
+    if out is None:
+        out = torch.empty(B, Cc, oh, ow, dtype=torch.float32, device=raw.device)
+    elif _f32c(out, "out").shape != (B, Cc, oh, ow):
+        raise RhoHipError(f"out must be float32 [{B}, {Cc}, {oh}, {ow}], got {tuple(out.shape)}")
+    if B == 0:
+        return out
+    (ys, wy, ky), (xs, wx, kx) = taps["y"], taps["x"]
+    flag = torch.zeros(1, dtype=torch.int32, device=raw.device) if err_flag is None else err_flag
+    check(hip.lib().rho_crop_resize(ptr(raw), RAW_DTYPES[raw.dtype], N, H, W, Cc, ptr(index), B, ptr(rowmax), ptr(ys), ptr(wy), ky,
+                                    ptr(xs), ptr(wx), kx, ch, cw, oh, ow, ptr(out), ptr(flag), stream()), "rho_crop_resize")
+    if err_flag is None:
+        crop_resize_check(flag)
+    return out
+
+
 def linear(x: Tensor, w: Tensor, bias: Optional[Tensor], add: Optional[Tensor] = None, act_in: bool = False,
            act_out: bool = False, out: Optional[Tensor] = None) -> Tensor:
     _f32c(x, "x"), _f32c(w, "w")

@@ -9,6 +9,7 @@ creation properties, native little-endian types).  Host-side I/O only: nothing h
     write("samples.h5", {"data": array})                      # h5py: f["data"] = array
     read("cache.h5", "density", index=7)                      # h5py: f["density"][7]
     shape("cache.h5", "density"); read_attr("cache.h5", "seed")
+    write("dg.h5", {"s_1_m_1/images_camera_00": a}); read("dg.h5", "/s_1_m_1/images_camera_00"); datasets("dg.h5", group="s_1_m_1")
 """
 from __future__ import annotations
 
@@ -92,6 +93,9 @@ def _load() -> C.CDLL:
             "H5Gget_num_objs": (C.c_int, [hid_t, C.POINTER(hsize_t)]),
             "H5Gget_objname_by_idx": (C.c_ssize_t, [hid_t, hsize_t, C.c_char_p, C.c_size_t]),
             "H5Eset_auto2": (C.c_int, [hid_t, C.c_void_p, C.c_void_p]),
+            "H5Gopen2": (hid_t, [hid_t, C.c_char_p, hid_t]), "H5Gclose": (C.c_int, [hid_t]),
+            "H5Pcreate": (hid_t, [hid_t]), "H5Pclose": (C.c_int, [hid_t]),
+            "H5Pset_create_intermediate_group": (C.c_int, [hid_t, C.c_uint]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -148,19 +152,28 @@ class _File:
 
 
 def write(path, arrays: Dict[str, np.ndarray], attrs: Optional[Dict[str, Union[int, float]]] = None, mode: str = "w") -> None:
-    """Create ``path`` with one contiguous dataset per entry (``h5f[name] = array``) and scalar root attributes."""
+    """Create ``path`` with one contiguous dataset per entry (``h5f[name] = array``) and scalar root attributes.  A name with slashes
+    ("grp/images") creates the groups on its path as h5py does."""
     L = _load()
     with _File(path, mode) as f:
-        for name, arr in arrays.items():
-            a = np.ascontiguousarray(arr)
-            tid = _native(a.dtype)
-            dims = (hsize_t * max(a.ndim, 1))(*a.shape)
-            sid = _chk(L.H5Screate_simple(a.ndim, dims, None) if a.ndim else L.H5Screate(H5S_SCALAR), "H5Screate")
-            did = _chk(L.H5Dcreate2(f.id, name.encode(), tid, sid, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT), f"creating dataset {name}")
-            rc = L.H5Dwrite(did, tid, H5S_ALL, H5S_ALL, H5P_DEFAULT, a.ctypes.data)
-            L.H5Dclose(did)
-            L.H5Sclose(sid)
-            _chk(rc, f"writing dataset {name}")
+        lcpl = _chk(L.H5Pcreate(hid_t.in_dll(L, "H5P_CLS_LINK_CREATE_ID_g").value), "H5Pcreate")
+        try:
+            _chk(L.H5Pset_create_intermediate_group(lcpl, 1), "H5Pset_create_intermediate_group")
+            for name, arr in arrays.items():
+                a = np.ascontiguousarray(arr)
+                tid = _native(a.dtype)
+                dims = (hsize_t * max(a.ndim, 1))(*a.shape)
+                sid = _chk(L.H5Screate_simple(a.ndim, dims, None) if a.ndim else L.H5Screate(H5S_SCALAR), "H5Screate")
+                did = L.H5Dcreate2(f.id, name.encode(), tid, sid, lcpl, H5P_DEFAULT, H5P_DEFAULT)
+                if did < 0:
+                    L.H5Sclose(sid)
+                    raise H5Error(f"creating dataset {name} failed")
+                rc = L.H5Dwrite(did, tid, H5S_ALL, H5S_ALL, H5P_DEFAULT, a.ctypes.data)
+                L.H5Dclose(did)
+                L.H5Sclose(sid)
+                _chk(rc, f"writing dataset {name}")
+        finally:
+            L.H5Pclose(lcpl)
         for name, val in (attrs or {}).items():
             v = np.asarray(val)
             if v.dtype.kind in "iu":
@@ -187,9 +200,17 @@ def _np_dtype_of(tid: int) -> np.dtype:
     raise H5Error(f"unsupported stored type (class {cls}, {size} bytes)")
 
 
+def _exists(fid: int, name: str) -> bool:
+    """Every link on the path "a/b/c" (or "/a/b/c") exists: H5Lexists itself fails when an intermediate group is missing."""
+    L = _load()
+    parts = [p for p in name.split("/") if p]
+    lead = "/" if name.startswith("/") else ""
+    return bool(parts) and all(L.H5Lexists(fid, (lead + "/".join(parts[:k])).encode(), H5P_DEFAULT) > 0 for k in range(1, len(parts) + 1))
+
+
 def _open_dataset(f: _File, name: str):
     L = _load()
-    if L.H5Lexists(f.id, name.encode(), H5P_DEFAULT) <= 0:
+    if not _exists(f.id, name):
         raise KeyError(f"Unable to open object (object '{name}' doesn't exist)")       # h5py's wording
     did = _chk(L.H5Dopen2(f.id, name.encode(), H5P_DEFAULT), f"opening dataset {name}")
     sid = _chk(L.H5Dget_space(did), "H5Dget_space")
@@ -266,15 +287,24 @@ def read_attr(path, name: str):
         return buf[0].item()
 
 
-def datasets(path) -> Sequence[str]:
-    """Names of the root group's members."""
+def datasets(path, group: Optional[str] = None) -> Sequence[str]:
+    """Names of the root group's members, or of ``group``'s ("s_1_m_1" or a nested path), in name order (h5py's ``keys()``)."""
     L = _load()
     with _File(path, "r") as f:
-        n = hsize_t()
-        _chk(L.H5Gget_num_objs(f.id, C.byref(n)), "H5Gget_num_objs")
-        out = []
-        for i in range(int(n.value)):
-            buf = C.create_string_buffer(256)
-            L.H5Gget_objname_by_idx(f.id, i, buf, 256)
-            out.append(buf.value.decode())
-        return out
+        gid = f.id
+        if group is not None:
+            if not _exists(f.id, group):
+                raise KeyError(f"Unable to open object (object '{group}' doesn't exist)")
+            gid = _chk(L.H5Gopen2(f.id, group.encode(), H5P_DEFAULT), f"opening group {group}")
+        try:
+            n = hsize_t()
+            _chk(L.H5Gget_num_objs(gid, C.byref(n)), "H5Gget_num_objs")
+            out = []
+            for i in range(int(n.value)):
+                buf = C.create_string_buffer(256)
+                L.H5Gget_objname_by_idx(gid, i, buf, 256)
+                out.append(buf.value.decode())
+            return out
+        finally:
+            if gid != f.id:
+                L.H5Gclose(gid)
