@@ -424,6 +424,25 @@ int rho_crop_resize(const void* raw, int dtype, int64_t n, int64_t h, int64_t w,
                     const double* rowmax, const int32_t* ys, const float* wy, int64_t ky, const int32_t* xs, const float* wx, int64_t kx,
                     int64_t crop_h, int64_t crop_w, int64_t out_h, int64_t out_w, float* out, int32_t* err_flag, void* stream);
 
+/* ------------------------------------------------------------------ spectra */
+
+/* SpectroscopyDataset's item path for a batch (rho_diffusion/data/spectroscopy.py:111-189: simulate_lineprofile :142-189 with the
+ * inclusive range mask of :179-181, and the division by the row maximum of :130), float32 throughout:
+ *   S_b[j]    = sum over the lines k of item index[b] with min(grid) <= c_k <= max(grid):  I_k * exp(-(grid[j] - c_k)^2 / (2 w^2))
+ *   out[b, j] = S_b[j] / max_j S_b[j]        (rowmax != NULL)        or S_b[j]        (rowmax == NULL)
+ * grid: float32 [grid_size] on the device, monotone (numpy's linspace, uploaded).  The lines of all n_items items are packed in CSR
+ * form on the device: centers / intensity float32 [total] (intensity = 10 ** clip(log10 I, -10, -2), already applied, >= 0 when the
+ * row is normalised), offsets int64 [n_items + 1], and inside an item the lines are sorted by centre - the kernel visits only the
+ * lines within 13.25 w of a tile of grid points (beyond that the exponent is below -87 and the term below 1.7e-38 * I).
+ * w = widths[b] (float32 [batch]); with line_width (optional, float32 [total]) each line has its own width, widths[] is ignored and
+ * the window uses the item's largest.  index: int64 [batch] on the device.  out: float32 [batch, grid_size].  rowmax: float32
+ * [batch] scratch that receives the row maxima (zeroed by the call; a second launch divides), NULL to skip the normalisation.  A
+ * row without a line in range is 0 / 0 = NaN, as in the reference.  An index outside [0, n_items) sets *err_flag |= 4 (optional
+ * flag) and leaves that row unwritten; offsets outside [0, total] set *err_flag |= 8. */
+int rho_line_profile(const float* grid, int64_t grid_size, const float* centers, const float* intensity, const float* line_width,
+                     int64_t total, const int64_t* offsets, int64_t n_items, const int64_t* index, const float* widths, int64_t batch,
+                     float* out, float* rowmax, int32_t* err_flag, void* stream);
+
 /* ------------------------------------------------------------------ attention */
 
 /* Flash-style self attention, fp32 online softmax (QKVAttentionLegacy / QKVAttention,

@@ -546,6 +546,60 @@ def crop_resize(raw: Tensor, rowmax: Tensor, index: Tensor, crop, size, antialia
     return out
 
 
+# ----------------------------------------------------------------------------- spectra
+def line_profile_check(flag: Tensor) -> None:
+    """Host poll of rho_line_profile's error flag (one synchronisation)."""
+    v = int(flag.item())
+    if v:
+        flag.zero_()
+        if v & 4:
+            raise RhoHipError("line_profile: an index lies outside [0, N) (rho_line_profile err_flag bit 2)")
+        raise RhoHipError(f"line_profile: offsets do not describe lines inside [0, total] (err_flag {v})")
+
+
+def line_profile(grid: Tensor, centers: Tensor, intensity: Tensor, offsets: Tensor, index: Tensor, widths: Tensor,
+                 line_width: Optional[Tensor] = None, out: Optional[Tensor] = None, err_flag: Optional[Tensor] = None,
+                 normalise: bool = True) -> Tensor:
+    """Gaussian line profiles float32 [B, G] of items ``index`` (int64 [B]) on the monotone float32 ``grid`` [G] (rho_line_profile):
+    the lines of all N items packed in CSR form (``centers`` / ``intensity`` float32 [total], ``offsets`` int64 [N + 1]), sorted by
+    centre inside an item; ``widths`` float32 [B], or one width per line in ``line_width`` float32 [total].  Lines outside
+    [grid.min(), grid.max()] are masked; ``normalise`` divides every row by its maximum (a row without a line in range is NaN, as
+    in the reference), else the plain sums are returned.  Without ``err_flag`` the call polls its own flag and raises on an index
+    outside [0, N); with one, the caller polls (``line_profile_check``)."""
+    hip.require_gpu(grid, "grid")
+    _f32c(grid, "grid")
+    if grid.dim() != 1 or grid.numel() == 0:
+        raise RhoHipError(f"grid must be a non-empty float32 [G] tensor, got {tuple(grid.shape)}")
+    G = grid.numel()
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_cuda or not offsets.is_contiguous():
+        raise RhoHipError("offsets must be a contiguous int64 [N + 1] GPU tensor")
+    N = offsets.numel() - 1
+    total = centers.numel()
+    for name, t in (("centers", centers), ("intensity", intensity), ("line_width", line_width)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != total or not t.is_cuda or not t.is_contiguous():
+            raise RhoHipError(f"{name} must be a contiguous float32 [{total}] GPU tensor")
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_cuda or not index.is_contiguous():
+        raise RhoHipError("index must be a contiguous int64 [B] GPU tensor")
+    B = index.numel()
+    if widths.dtype != torch.float32 or tuple(widths.shape) != (B,) or not widths.is_cuda or not widths.is_contiguous():
+        raise RhoHipError(f"widths must be a contiguous float32 [{B}] GPU tensor")
+    if out is None:
+        out = torch.empty(B, G, dtype=torch.float32, device=grid.device)
+    elif _f32c(out, "out").shape != (B, G):
+        raise RhoHipError(f"out must be float32 [{B}, {G}], got {tuple(out.shape)}")
+    if B == 0:
+        return out
+    rowmax = torch.empty(B, dtype=torch.float32, device=grid.device) if normalise else None
+    flag = torch.zeros(1, dtype=torch.int32, device=grid.device) if err_flag is None else err_flag
+    check(hip.lib().rho_line_profile(ptr(grid), G, ptr(centers), ptr(intensity), ptr(line_width), total, ptr(offsets), N, ptr(index),
+                                     ptr(widths), B, ptr(out), ptr(rowmax), ptr(flag), stream()), "rho_line_profile")
+    if err_flag is None:
+        line_profile_check(flag)
+    return out
+
+
 def linear(x: Tensor, w: Tensor, bias: Optional[Tensor], add: Optional[Tensor] = None, act_in: bool = False,
            act_out: bool = False, out: Optional[Tensor] = None) -> Tensor:
     _f32c(x, "x"), _f32c(w, "w")
