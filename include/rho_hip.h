@@ -36,7 +36,9 @@ extern "C" {
 
 /* ABI version: bumped on ANY signature / struct-layout change (2: table_len in rho_q_sample(_coef), fmt in rho_gn_bwd_finalize,
  * rho_conv_desc grew; 3: round-3 additions; 9: the rho_gd_* / metrics entry points of csrc/gaussian.hip;
- * 10: learned variances - RHO_GD_LOG_BETA, the *_lv / strided / hybrid-loss entry points).  A loader must compare rho_abi_version() with the header it was written against
+ * 10: learned variances - RHO_GD_LOG_BETA, the *_lv / strided / hybrid-loss entry points; the dataset entry points added since -
+ * rho_crop_resize, rho_line_profile, rho_pil_resize_taps, rho_u8_image_batch - change no existing signature or struct, so by this
+ * rule they leave it at 10: a binding that lacks them fails on the missing symbol).  A loader must compare rho_abi_version() with the header it was written against
  * before calling anything else (hip.py does; a build with all symbols but older signatures would be called with shifted arguments). */
 #define RHO_ABI_VERSION 10
 int rho_abi_version(void);
@@ -423,6 +425,37 @@ int64_t rho_crop_resize_taps(int64_t in_size, int64_t crop, int64_t out_size, in
 int rho_crop_resize(const void* raw, int dtype, int64_t n, int64_t h, int64_t w, int64_t c, const int64_t* index, int64_t batch,
                     const double* rowmax, const int32_t* ys, const float* wy, int64_t ky, const int32_t* xs, const float* wx, int64_t kx,
                     int64_t crop_h, int64_t crop_w, int64_t out_h, int64_t out_w, float* out, int32_t* err_flag, void* stream);
+
+/* HOST function (host arrays, no device memory, no stream): the integer tap table of one axis of PIL.Image.resize(size, BILINEAR) on
+ * an 8-bit image - what torchvision's Resize runs on the PIL.Image that MNIST / CIFAR10 hand it (rho_diffusion/data/wrappers.py:108-116
+ * Resize((32, 32)), ToTensor(), 2 t - 1).  Restates Pillow's precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c) for
+ * the bilinear filter (triangle, support 1.0) over the whole axis, in C double: scale = in / out, filterscale = max(scale, 1), support =
+ * filterscale, ksize = ceil(support) * 2 + 1; output o has center = (o + 0.5) * scale and reads pixels start[o] .. start[o] +
+ * count[o] - 1 with start = max((int)(center - support + 0.5), 0), start + count = min((int)(center + support + 0.5), in); weight j =
+ * tri((j + start - center + 0.5) * (1 / filterscale)) normalised by the window's sum; coef[o * ksize + j] = (int)(0.5 + weight * 2^22)
+ * (PRECISION_BITS = 32 - 8 - 2), 0 for j >= count[o].  Every window lies inside [0, in_size).  start == count == coef == NULL: returns
+ * ksize only; else fills start[out_size], count[out_size], coef[out_size * ksize] and returns ksize.  RHO_E_ARG on bad sizes. */
+int64_t rho_pil_resize_taps(int64_t in_size, int64_t out_size, int32_t* start, int32_t* count, int32_t* coef);
+
+/* The default per-item transform of MNISTDataset / CIFAR10Dataset for a batch, one launch (wrappers.py:67-75, :108-116: the PIL.Image
+ * that torchvision builds per item through Resize (MNIST) -> ToTensor -> 2 t - 1), as Pillow's ImagingResample orders it for 8-bit
+ * images - horizontal pass first, each pass rounded to uint8:
+ *   tmp[y, ox, ch] = clip8((2^21 + sum_j raw[index[b], y, xs[ox] + j, ch] * kx[ox * ksx + j]) >> 22)        j < xn[ox]
+ *   u[oy, ox, ch]  = clip8((2^21 + sum_i tmp[ys[oy] + i, ox, ch] * ky[oy * ksy + i]) >> 22)                 i < yn[oy]
+ *   out[b, ch, oy, ox] = lut[u[oy, ox, ch]]
+ * raw: uint8 [n, h, w, c] contiguous, c <= 4.  index: int64 [batch] on the device.  (ys, yn, ky, ksy) and (xs, xn, kx, ksx) are
+ * rho_pil_resize_taps(h, out_h, ...) and rho_pil_resize_taps(w, out_w, ...) copied to the device.  An axis that keeps its size passes
+ * NULL tables and ks = 0 and its pass is skipped, as Pillow skips it (RHO_E_ARG if the sizes differ); with both skipped the call is
+ * a gather, HWC -> CHW and the table lookup (CIFAR-10).  lut: float32 [256] on the device - (arange(256) / 255) * 2 - 1 for the
+ * reference's transforms; the kernel itself does no floating-point arithmetic.  out: float32 [batch, c, out_h, out_w].
+ * Limit: one item is staged in LDS, 1 KiB + 4 (2 + ksx) out_w + 4 (2 + ksy) out_h + h w c + h out_w c bytes (each term rounded up to
+ * 16; the last only with an x pass) must not exceed 64 KiB, else RHO_E_SHAPE (MNIST: 5 KiB, CIFAR-10: 4 KiB).
+ * An index outside [0, n) sets *err_flag |= 4 (optional flag) and leaves that item's output unwritten; a table window outside its
+ * axis sets *err_flag |= 8 and nothing is written. */
+int rho_u8_image_batch(const uint8_t* raw, int64_t n, int64_t h, int64_t w, int64_t c, const int64_t* index, int64_t batch,
+                       const int32_t* ys, const int32_t* yn, const int32_t* ky, int64_t ksy, const int32_t* xs, const int32_t* xn,
+                       const int32_t* kx, int64_t ksx, int64_t out_h, int64_t out_w, const float* lut, float* out, int32_t* err_flag,
+                       void* stream);
 
 /* ------------------------------------------------------------------ spectra */
 

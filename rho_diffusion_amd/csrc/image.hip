@@ -292,3 +292,242 @@ extern "C" int rho_crop_resize(const void* raw, int dtype, int64_t n, int64_t h,
     RHO_LAUNCH_CHECK();
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// MNISTDataset / CIFAR10Dataset (rho_diffusion/data/wrappers.py:37-116): torchvision builds a PIL.Image per item and runs
+// Resize((32, 32)) (MNIST only) -> ToTensor() -> 2 t - 1 on it.  Resize of a PIL image is Image.resize(size, BILINEAR): Pillow's
+// two-pass fixed-point resample (src/libImaging/Resample.c), integer arithmetic on uint8 with a uint8 intermediate, so the whole
+// transform is integers plus a 256-entry table and is restated here bit for bit.
+//
+// rho_pil_resize_taps (host) is precompute_coeffs + normalize_coeffs_8bpc for the bilinear filter.  k_u8_image_batch walks the items
+// with a capped grid, one item per workgroup and turn: the tap tables and the LUT go to LDS once per workgroup, then per item the raw
+// bytes are staged (16-byte loads where the item size allows), resampled along x into a second uint8 LDS image, and resampled along
+// y on the way out; each thread produces four consecutive floats of the [C, oh, ow] item, so the stores run along ox.  An item is
+// hundreds of bytes in and a few KiB out: the kernel is bound by launch and memory latency, not by bandwidth.
+namespace {
+
+constexpr int UI_THREADS = 256;
+constexpr int UI_MAX_WGS = 2048;                            // 8 workgroups on each of 256 CUs; larger batches take turns
+constexpr int64_t UI_LDS_BUDGET = 64 * 1024;
+constexpr int UI_PRECISION_BITS = 32 - 8 - 2;               // Resample.c PRECISION_BITS
+
+struct U8K {
+    const unsigned char* raw;
+    const int64_t* index;
+    const int32_t* ys; const int32_t* yn; const int32_t* ky;
+    const int32_t* xs; const int32_t* xn; const int32_t* kx;
+    const float* lut;
+    float* out;
+    int32_t* err_flag;
+    int64_t n, batch;
+    int h, w, c, ksy, ksx, out_h, out_w;
+    int vec_in, vec_out;            // 16-byte loads of the item / 16-byte stores of the output are possible
+    int o_x, o_y, o_raw, o_tmp;     // byte offsets of the LDS regions (the LUT is at 0)
+};
+
+// Resample.c clip8: (in >> PRECISION_BITS) clamped to [0, 255].  The sum is kept unsigned (tables from rho_pil_resize_taps never
+// overflow it: 255 * (2^22 + ksize) + 2^21 < 2^31) and read back as int32.
+__device__ __forceinline__ unsigned char ui_clip8(uint32_t acc) {
+    const int v = (int)acc >> UI_PRECISION_BITS;
+    return (unsigned char)min(max(v, 0), 255);
+}
+
+// one axis' tables -> LDS; returns 1 if a window does not lie inside [0, in_size) or is longer than ks
+__device__ __forceinline__ int ui_load_taps(const int32_t* gs, const int32_t* gn, const int32_t* gk, int32_t* s, int32_t* nn, int32_t* k,
+                                            int out_size, int ks, int in_size) {
+    int bad = 0;
+    for (int i = threadIdx.x; i < out_size; i += UI_THREADS) {
+        const int32_t a = gs[i], cnt = gn[i];
+        bad |= (a < 0 || cnt < 0 || cnt > ks || a > in_size - cnt) ? 1 : 0;
+        s[i] = a;
+        nn[i] = cnt;
+    }
+    for (int i = threadIdx.x; i < out_size * ks; i += UI_THREADS) k[i] = gk[i];
+    return bad;
+}
+
+__global__ __launch_bounds__(UI_THREADS) void k_u8_image_batch(const U8K p) {
+    extern __shared__ float4 lds4[];
+    unsigned char* lds = reinterpret_cast<unsigned char*>(lds4);
+    float* lut = reinterpret_cast<float*>(lds);
+    int32_t* xs = reinterpret_cast<int32_t*>(lds + p.o_x);
+    int32_t* xn = xs + p.out_w;
+    int32_t* kx = xn + p.out_w;
+    int32_t* ys = reinterpret_cast<int32_t*>(lds + p.o_y);
+    int32_t* yn = ys + p.out_h;
+    int32_t* ky = yn + p.out_h;
+    unsigned char* rawL = lds + p.o_raw;
+    unsigned char* tmpL = lds + p.o_tmp;
+    const int tid = threadIdx.x;
+    const int C = p.c, W = p.w, OW = p.out_w, OH = p.out_h;
+    const int isz = p.h * W * C, tsz = p.h * OW * C, osz = C * OH * OW;
+
+    int bad = 0;
+    for (int i = tid; i < 256; i += UI_THREADS) lut[i] = p.lut[i];
+    if (p.ksx > 0) bad |= ui_load_taps(p.xs, p.xn, p.kx, xs, xn, kx, OW, p.ksx, W);
+    if (p.ksy > 0) bad |= ui_load_taps(p.ys, p.yn, p.ky, ys, yn, ky, OH, p.ksy, p.h);
+    if (__syncthreads_or(bad)) {                            // tables built for another geometry: nothing is read through them
+        if (tid == 0 && p.err_flag != nullptr) atomicOr(p.err_flag, 8);
+        return;
+    }
+
+    for (int64_t b = blockIdx.x; b < p.batch; b += gridDim.x) {
+        const int64_t row = p.index[b];
+        if (row < 0 || row >= p.n) {                        // uniform over the workgroup
+            if (tid == 0 && p.err_flag != nullptr) atomicOr(p.err_flag, 4);
+            continue;
+        }
+        // 1. the item's bytes
+        const unsigned char* src = p.raw + row * (int64_t)isz;
+        if (p.vec_in) {
+            for (int i = tid; i < isz / 16; i += UI_THREADS)
+                reinterpret_cast<uint4*>(rawL)[i] = reinterpret_cast<const uint4*>(src)[i];
+        } else {
+            for (int i = tid; i < isz; i += UI_THREADS) rawL[i] = src[i];
+        }
+        __syncthreads();
+        // 2. ImagingResampleHorizontal_8bpc: every row, [h, w, c] -> uint8 [h, ow, c]
+        const unsigned char* P = rawL;
+        if (p.ksx > 0) {
+            for (int i = tid; i < tsz; i += UI_THREADS) {
+                const int ch = i % C, t = i / C, ox = t % OW, y = t / OW;
+                const int cnt = xn[ox];
+                const int32_t* k = kx + ox * p.ksx;
+                const unsigned char* r = rawL + (y * W + xs[ox]) * C + ch;
+                uint32_t acc = 1u << (UI_PRECISION_BITS - 1);
+                for (int j = 0; j < cnt; ++j) acc += (uint32_t)r[j * C] * (uint32_t)k[j];
+                tmpL[i] = ui_clip8(acc);
+            }
+            __syncthreads();
+            P = tmpL;
+        }
+        // 3. ImagingResampleVertical_8bpc (or the copy of an axis that keeps its size), the LUT, HWC -> CHW: four consecutive
+        //    outputs per thread in the order of the output's memory
+        float* o = p.out + b * (int64_t)osz;
+        const int sy = OW * C;                              // bytes between two rows of P
+        for (int k0 = tid * 4; k0 < osz; k0 += UI_THREADS * 4) {
+            int ox = k0 % OW, t = k0 / OW;
+            int oy = t % OH, ch = t / OH;
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = 0.0f;
+                if (k0 + e < osz) {
+                    unsigned char u;
+                    if (p.ksy > 0) {
+                        const int cnt = yn[oy];
+                        const int32_t* k = ky + oy * p.ksy;
+                        const unsigned char* r = P + (ys[oy] * OW + ox) * C + ch;
+                        uint32_t acc = 1u << (UI_PRECISION_BITS - 1);
+                        for (int i = 0; i < cnt; ++i) acc += (uint32_t)r[i * sy] * (uint32_t)k[i];
+                        u = ui_clip8(acc);
+                    } else {
+                        u = P[(oy * OW + ox) * C + ch];
+                    }
+                    v[e] = lut[u];
+                }
+                if (++ox == OW) {
+                    ox = 0;
+                    if (++oy == OH) {
+                        oy = 0;
+                        ++ch;
+                    }
+                }
+            }
+            if (p.vec_out) {                                // osz is a multiple of 4 then: all four are inside the item
+                *reinterpret_cast<float4*>(o + k0) = make_float4(v[0], v[1], v[2], v[3]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (k0 + e < osz) o[k0 + e] = v[e];
+            }
+        }
+        __syncthreads();                                    // the next item overwrites the staged images
+    }
+}
+
+double ui_bilinear(double x) {                              // Resample.c bilinear_filter, support 1.0
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+}  // namespace
+
+extern "C" int64_t rho_pil_resize_taps(int64_t in_size, int64_t out_size, int32_t* start, int32_t* count, int32_t* coef) {
+    if (in_size <= 0 || out_size <= 0 || in_size > (1 << 24) || out_size > (1 << 24)) return RHO_E_ARG;
+    const int given = (start != nullptr) + (count != nullptr) + (coef != nullptr);
+    if (given != 0 && given != 3) return RHO_E_ARG;
+    // precompute_coeffs, in0 = 0 and in1 = in_size (the whole image), all in double
+    const double scale = (double)in_size / (double)out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = 1.0 * filterscale;
+    const int64_t ksize = (int64_t)std::ceil(support) * 2 + 1;
+    if (given == 0) return ksize;
+    const double ss = 1.0 / filterscale;                    // Pillow multiplies by the reciprocal, it does not divide
+    std::vector<double> k((size_t)ksize);
+    for (int64_t xx = 0; xx < out_size; ++xx) {
+        const double center = 0.0 + ((double)xx + 0.5) * scale;
+        double ww = 0.0;
+        int64_t xmin = (int64_t)(int)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int64_t xmax = (int64_t)(int)(center + support + 0.5);
+        if (xmax > in_size) xmax = in_size;
+        xmax -= xmin;
+        for (int64_t x = 0; x < xmax; ++x) {
+            const double w = ui_bilinear(((double)(x + xmin) - center + 0.5) * ss);
+            k[(size_t)x] = w;
+            ww += w;
+        }
+        for (int64_t x = 0; x < xmax; ++x)
+            if (ww != 0.0) k[(size_t)x] /= ww;
+        for (int64_t x = xmax; x < ksize; ++x) k[(size_t)x] = 0.0;
+        start[xx] = (int32_t)xmin;
+        count[xx] = (int32_t)xmax;
+        // normalize_coeffs_8bpc: (int)(0.5 + w * 2^22).  Its (int)(-0.5 + ...) branch is for negative weights, which the
+        // triangle filter never produces.
+        for (int64_t x = 0; x < ksize; ++x) coef[xx * ksize + x] = (int32_t)(0.5 + k[(size_t)x] * (double)(1 << UI_PRECISION_BITS));
+    }
+    return ksize;
+}
+
+extern "C" int rho_u8_image_batch(const uint8_t* raw, int64_t n, int64_t h, int64_t w, int64_t c, const int64_t* index, int64_t batch,
+                                  const int32_t* ys, const int32_t* yn, const int32_t* ky, int64_t ksy, const int32_t* xs,
+                                  const int32_t* xn, const int32_t* kx, int64_t ksx, int64_t out_h, int64_t out_w, const float* lut,
+                                  float* out, int32_t* err_flag, void* stream) {
+    if (!raw || !index || !lut || !out) return RHO_E_ARG;
+    if (n <= 0 || h <= 0 || w <= 0 || c <= 0 || c > CR_CMAX || batch <= 0 || batch > INT32_MAX || out_h <= 0 || out_w <= 0 || ksy < 0 ||
+        ksx < 0)
+        return RHO_E_ARG;
+    // an axis without tables keeps its size (Pillow skips that pass); one with tables has all three
+    if (ksy == 0 ? (ys || yn || ky || out_h != h) : (!ys || !yn || !ky)) return RHO_E_ARG;
+    if (ksx == 0 ? (xs || xn || kx || out_w != w) : (!xs || !xn || !kx)) return RHO_E_ARG;
+    if (reinterpret_cast<uintptr_t>(lut) % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 4 != 0) return RHO_E_ALIGN;
+    // LDS: LUT | x tables | y tables | item | x-resampled item, each region 16-byte aligned.  Every term is bounded before it is
+    // multiplied, so nothing overflows.
+    const int64_t lim = UI_LDS_BUDGET;
+    if (h > lim || w > lim || out_h > lim || out_w > lim || ksy > lim || ksx > lim) return RHO_E_SHAPE;
+    auto up16 = [](int64_t v) { return (v + 15) / 16 * 16; };
+    const int64_t isz = h * w * c, tsz = ksx > 0 ? h * out_w * c : 0;
+    const int64_t o_x = 256 * 4, o_y = o_x + up16(ksx > 0 ? (2 + ksx) * out_w * 4 : 0);
+    const int64_t o_raw = o_y + up16(ksy > 0 ? (2 + ksy) * out_h * 4 : 0), o_tmp = o_raw + up16(isz), shm = o_tmp + up16(tsz);
+    if (shm > UI_LDS_BUDGET) return RHO_E_SHAPE;
+    U8K p{};
+    p.raw = raw;
+    p.index = index;
+    p.ys = ys; p.yn = yn; p.ky = ky;
+    p.xs = xs; p.xn = xn; p.kx = kx;
+    p.lut = lut;
+    p.out = out;
+    p.err_flag = err_flag;
+    p.n = n;
+    p.batch = batch;
+    p.h = (int)h; p.w = (int)w; p.c = (int)c;
+    p.ksy = (int)ksy; p.ksx = (int)ksx; p.out_h = (int)out_h; p.out_w = (int)out_w;
+    p.vec_in = (isz % 16 == 0 && reinterpret_cast<uintptr_t>(raw) % 16 == 0) ? 1 : 0;
+    p.vec_out = ((c * out_h * out_w) % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0) ? 1 : 0;
+    p.o_x = (int)o_x; p.o_y = (int)o_y; p.o_raw = (int)o_raw; p.o_tmp = (int)o_tmp;
+    const dim3 grid((unsigned)std::min<int64_t>(batch, UI_MAX_WGS));
+    hipLaunchKernelGGL(k_u8_image_batch, grid, dim3(UI_THREADS), (size_t)shm, as_stream(stream), p);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}

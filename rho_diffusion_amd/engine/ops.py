@@ -546,6 +546,88 @@ def crop_resize(raw: Tensor, rowmax: Tensor, index: Tensor, crop, size, antialia
     return out
 
 
+def pil_resize_taps(in_size: int, out_size: int):
+    """(start int32 [out_size], count int32 [out_size], coef int32 [out_size, ksize]) of one axis of PIL.Image.resize(BILINEAR) on
+    an 8-bit image: Pillow's fixed-point tap table (rho_pil_resize_taps, host)."""
+    import numpy as np
+    L = hip.lib()
+    k = int(L.rho_pil_resize_taps(int(in_size), int(out_size), None, None, None))
+    if k <= 0:
+        raise RhoHipError(f"rho_pil_resize_taps(in={in_size}, out={out_size}) failed: {k}")
+    start = np.empty(int(out_size), dtype=np.int32)
+    count = np.empty(int(out_size), dtype=np.int32)
+    coef = np.empty((int(out_size), k), dtype=np.int32)
+    L.rho_pil_resize_taps(int(in_size), int(out_size), start.ctypes.data, count.ctypes.data, coef.ctypes.data)
+    return torch.from_numpy(start), torch.from_numpy(count), torch.from_numpy(coef)
+
+
+def u8_image_lut(device=None) -> Tensor:
+    """float32 [256]: ToTensor() then 2 t - 1 for every uint8 value, in torch's own arithmetic (byte -> float32, / 255, * 2, - 1)."""
+    return ((torch.arange(256, dtype=torch.float32) / 255) * 2 - 1).to(device)
+
+
+def u8_image_taps(h: int, w: int, size, device=None) -> dict:
+    """Device tap tables of Image.resize((size[1], size[0]), BILINEAR) for raw images [N, h, w, C]; an axis that keeps its size has
+    none (Pillow skips that pass).  Build once per geometry and pass to ``u8_image_batch``."""
+    oh, ow = _pair(size)
+
+    def axis(n_in, n_out):
+        if n_in == n_out:
+            return None
+        s, n, k = pil_resize_taps(n_in, n_out)
+        return s.to(device), n.to(device), k.to(device), k.shape[1]
+
+    return dict(hw=(int(h), int(w)), size=(oh, ow), y=axis(int(h), oh), x=axis(int(w), ow))
+
+
+def u8_image_check(flag: Tensor) -> None:
+    """Host poll of rho_u8_image_batch's error flag (one synchronisation)."""
+    v = int(flag.item())
+    if v:
+        flag.zero_()
+        if v & 4:
+            raise RhoHipError("u8_image_batch: an index lies outside [0, N) (rho_u8_image_batch err_flag bit 2)")
+        raise RhoHipError(f"u8_image_batch: the tap tables do not match the launch geometry (err_flag {v})")
+
+
+def u8_image_batch(raw: Tensor, index: Tensor, size=None, lut: Optional[Tensor] = None, taps: Optional[dict] = None,
+                   out: Optional[Tensor] = None, err_flag: Optional[Tensor] = None) -> Tensor:
+    """Rows ``index`` of the resident uint8 images [N, H, W, C] -> float32 [B, C, size[0], size[1]] as torchvision makes them from a
+    PIL.Image: Image.resize(BILINEAR) in Pillow's integer arithmetic (``size`` None: no resize), ToTensor and 2 t - 1 through ``lut``
+    (default ``u8_image_lut``) - one launch (rho_u8_image_batch), bit-equal to the host path.  Without ``err_flag`` the call polls its
+    own flag and raises on an index outside [0, N); with one, the caller polls (``u8_image_check``)."""
+    hip.require_gpu(raw, "raw")
+    if raw.dtype != torch.uint8 or raw.dim() != 4 or not raw.is_contiguous():
+        raise RhoHipError(f"raw must be a contiguous uint8 [N, H, W, C] tensor, got {raw.dtype} {tuple(raw.shape)}")
+    N, H, W, Cc = raw.shape
+    if index.dtype != torch.int64 or index.dim() != 1 or not index.is_cuda or not index.is_contiguous():
+        raise RhoHipError("index must be a contiguous int64 [B] GPU tensor")
+    oh, ow = (H, W) if size is None else _pair(size)
+    if taps is None:
+        taps = u8_image_taps(H, W, (oh, ow), raw.device)
+    elif taps["hw"] != (H, W) or taps["size"] != (oh, ow):
+        raise RhoHipError(f"u8_image_batch: taps were built for {taps['hw']} -> {taps['size']}, the call asks for {(H, W)} -> {(oh, ow)}")
+    if lut is None:
+        lut = u8_image_lut(raw.device)
+    elif lut.dtype != torch.float32 or tuple(lut.shape) != (256,) or not lut.is_cuda or not lut.is_contiguous():
+        raise RhoHipError("lut must be a contiguous float32 [256] GPU tensor")
+    B = index.numel()
+    if out is None:
+        out = torch.empty(B, Cc, oh, ow, dtype=torch.float32, device=raw.device)
+    elif _f32c(out, "out").shape != (B, Cc, oh, ow):
+        raise RhoHipError(f"out must be float32 [{B}, {Cc}, {oh}, {ow}], got {tuple(out.shape)}")
+    if B == 0:
+        return out
+    ys, yn, ky, ksy = taps["y"] or (None, None, None, 0)
+    xs, xn, kx, ksx = taps["x"] or (None, None, None, 0)
+    flag = torch.zeros(1, dtype=torch.int32, device=raw.device) if err_flag is None else err_flag
+    check(hip.lib().rho_u8_image_batch(ptr(raw), N, H, W, Cc, ptr(index), B, ptr(ys), ptr(yn), ptr(ky), ksy, ptr(xs), ptr(xn), ptr(kx),
+                                       ksx, oh, ow, ptr(lut), ptr(out), ptr(flag), stream()), "rho_u8_image_batch")
+    if err_flag is None:
+        u8_image_check(flag)
+    return out
+
+
 # ----------------------------------------------------------------------------- spectra
 def line_profile_check(flag: Tensor) -> None:
     """Host poll of rho_line_profile's error flag (one synchronisation)."""
