@@ -76,13 +76,14 @@ int rho_step_advance(int32_t* t_dev, uint64_t* offset_dev, uint64_t delta, void*
 int rho_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t offset,
                       const uint64_t* offset_dev, void* stream);
 
-/* mean((a-b)^2) -> loss[0] (float32, zeroed by this call) and optionally grad_a = 2(a-b)/n.
- * replaces nn.MSELoss at ddpm.py:280 (+ its backward). */
+/* mean((a-b)^2) -> loss[0] (float32, written by this call) and optionally grad_a = 2(a-b)/n.
+ * replaces nn.MSELoss at ddpm.py:280 (+ its backward).  rho_mse_ws with its scratch allocated and freed in stream order
+ * (hipMallocAsync) by the call itself. */
 int rho_mse(const float* a, const float* b, float* loss, float* grad_a, int64_t n, void* stream);
 
 /* The same with an ORDERED reduction (ABI 7): block partials go to partials[n_partials] (scratch, >= 1; 1024 is plenty) and are added
- * in index order, so the loss value is bit-reproducible run to run (rho_mse adds its blocks with an fp32 atomic, in arrival order).
- * grad_a is identical in both.  The Python binding always uses this form. */
+ * in index order, so the loss value is bit-reproducible run to run (rho_mse used to add its blocks with an fp32 atomic, in arrival
+ * order).  loss and grad_a are identical in both.  The Python binding always uses this form. */
 int rho_mse_ws(const float* a, const float* b, float* loss, float* grad_a, int64_t n, float* partials, int64_t n_partials, void* stream);
 
 /* mean over all non-batch axes of a float32 [batch, per_sample] tensor -> out[batch]: mean_flat of layers.py:105-110 (ABI 7). */

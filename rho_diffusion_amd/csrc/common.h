@@ -68,7 +68,7 @@ __device__ __forceinline__ float dact_other_f(float u, int act) {
     }
 }
 
-// ---- counter-based RNG shared by rho_philox_normal and the dropout masks of the GroupNorm passes
+// ---- counter-based RNG shared by rho_philox_normal, rho_randint and the dropout masks of the GroupNorm passes
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
     const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
     const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];

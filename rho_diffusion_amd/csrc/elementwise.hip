@@ -40,6 +40,9 @@ extern "C" const char* rho_build_info(void) {
 
 // ----------------------------------------------------------------------------- q_sample
 // ddpm.py:122-129: x_t = sqrt(abar_t)*x0 + sqrt(1-abar_t)*eps, abar gathered per batch element.
+// The contraction is written out (left to the compiler, the 16-byte kernel fused sa * x0 into the sum and the scalar kernel did
+// not): the scalar kernel that serves ragged or 4-byte-aligned operands gives the bits of the 16-byte one.
+__device__ __forceinline__ float q_mix(float sa, float x, float sb, float e) { return __fmaf_rn(sa, x, sb * e); }
 __global__ __launch_bounds__(256) void k_q_sample(const float4* __restrict__ x0, const float4* __restrict__ eps,
                                                   float4* __restrict__ xt, const float* __restrict__ abar,
                                                   const int64_t* __restrict__ t, int64_t per4, int64_t total4,
@@ -53,10 +56,10 @@ __global__ __launch_bounds__(256) void k_q_sample(const float4* __restrict__ x0,
         const float sa = sqrtf(ab), sb = sqrtf(1.0f - ab);
         const float4 a = x0[i], e = eps[i];
         float4 r;
-        r.x = sa * a.x + sb * e.x;
-        r.y = sa * a.y + sb * e.y;
-        r.z = sa * a.z + sb * e.z;
-        r.w = sa * a.w + sb * e.w;
+        r.x = q_mix(sa, a.x, sb, e.x);
+        r.y = q_mix(sa, a.y, sb, e.y);
+        r.z = q_mix(sa, a.z, sb, e.z);
+        r.w = q_mix(sa, a.w, sb, e.w);
         bad |= (r.x != r.x) | (r.y != r.y) | (r.z != r.z) | (r.w != r.w);
         xt[i] = r;
     }
@@ -76,7 +79,7 @@ __global__ void k_q_sample_tail(const float* x0, const float* eps, float* xt, co
             tb = tb < 0 ? 0 : table_len - 1;
         }
         const float ab = abar[tb];
-        const float r = sqrtf(ab) * x0[i] + sqrtf(1.0f - ab) * eps[i];
+        const float r = q_mix(sqrtf(ab), x0[i], sqrtf(1.0f - ab), eps[i]);
         if (r != r && nan_flag) atomicOr(nan_flag, 1);
         xt[i] = r;
     }
@@ -100,6 +103,10 @@ extern "C" int rho_q_sample(const float* x0, const float* eps, float* x_t, const
 // ----------------------------------------------------------------------------- p_sample_step
 // ddpm.py:210-218.  coef row = {1/sqrt(alpha), beta/sqrt(1-abar), 0.8*sqrt(beta)}; t read on device so
 // that one captured graph serves every step; t == 0 => no update (q3), t <= 1 => z ignored.
+// One written-out contraction for the 16-byte body, its tail and the 4-byte-aligned fallback: all three round alike.
+__device__ __forceinline__ float p_update(float c0, float c1, float c2, float x, float e, float z) {
+    return fminf(fmaxf(__fmaf_rn(c0, __fmaf_rn(-c1, e, x), c2 * z), -1.0f), 1.0f);
+}
 __global__ __launch_bounds__(256) void k_p_sample(float* __restrict__ x, const float* __restrict__ eh,
                                                   const float* __restrict__ z, const float* __restrict__ coef,
                                                   const int32_t* __restrict__ t_dev, int64_t n) {
@@ -119,20 +126,20 @@ __global__ __launch_bounds__(256) void k_p_sample(float* __restrict__ x, const f
             const float4 e = e4[i];
             float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
             if (c2 != 0.0f) zz = z4[i];
-            a.x = fminf(fmaxf(c0 * (a.x - c1 * e.x) + c2 * zz.x, -1.0f), 1.0f);
-            a.y = fminf(fmaxf(c0 * (a.y - c1 * e.y) + c2 * zz.y, -1.0f), 1.0f);
-            a.z = fminf(fmaxf(c0 * (a.z - c1 * e.z) + c2 * zz.z, -1.0f), 1.0f);
-            a.w = fminf(fmaxf(c0 * (a.w - c1 * e.w) + c2 * zz.w, -1.0f), 1.0f);
+            a.x = p_update(c0, c1, c2, a.x, e.x, zz.x);
+            a.y = p_update(c0, c1, c2, a.y, e.y, zz.y);
+            a.z = p_update(c0, c1, c2, a.z, e.z, zz.z);
+            a.w = p_update(c0, c1, c2, a.w, e.w, zz.w);
             x4[i] = a;
         }
         for (int64_t i = (n4 << 2) + tid; i < n; i += stride) {
             const float zz = (c2 != 0.0f) ? z[i] : 0.0f;
-            x[i] = fminf(fmaxf(c0 * (x[i] - c1 * eh[i]) + c2 * zz, -1.0f), 1.0f);
+            x[i] = p_update(c0, c1, c2, x[i], eh[i], zz);
         }
     } else {
         for (int64_t i = tid; i < n; i += stride) {
             const float zz = (c2 != 0.0f) ? z[i] : 0.0f;
-            x[i] = fminf(fmaxf(c0 * (x[i] - c1 * eh[i]) + c2 * zz, -1.0f), 1.0f);
+            x[i] = p_update(c0, c1, c2, x[i], eh[i], zz);
         }
     }
 }
@@ -199,32 +206,7 @@ extern "C" int rho_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t 
 }
 
 // ----------------------------------------------------------------------------- MSE (+grad)
-__global__ __launch_bounds__(256) void k_mse(const float* __restrict__ a, const float* __restrict__ b, float* loss,
-                                             float* __restrict__ grad, int64_t n, float inv_n) {
-    __shared__ float red[4];
-    float acc = 0.0f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float d = a[i] - b[i];
-        acc += d * d;
-        if (grad) grad[i] = 2.0f * d * inv_n;
-    }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss, (red[0] + red[1] + red[2] + red[3]) * inv_n);
-}
-
-extern "C" int rho_mse(const float* a, const float* b, float* loss, float* grad_a, int64_t n, void* stream) {
-    if (!a || !b || !loss || n <= 0) return RHO_E_ARG;
-    hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), as_stream(stream));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_mse, dim3(grid_for(n, 256 * 8)), dim3(256), 0, as_stream(stream), a, b, loss, grad_a, n, 1.0f / (float)n);
-    RHO_LAUNCH_CHECK();
-    return 0;
-}
-
-// Ordered form: block b stores its partial to partials[b]; one wave adds them in index order -> the loss is bit-reproducible
-// (the atomic form above adds the blocks in arrival order).  grad is the same either way.
+// Block b stores its partial to partials[b]; one wave adds them in index order -> the loss is bit-reproducible.
 __global__ __launch_bounds__(256) void k_mse_part(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ partials,
                                                   float* __restrict__ grad, int64_t n, float inv_n, int vec) {
     __shared__ float red[4];
@@ -272,6 +254,20 @@ extern "C" int rho_mse_ws(const float* a, const float* b, float* loss, float* gr
     hipLaunchKernelGGL(k_mse_final, dim3(1), dim3(64), 0, as_stream(stream), partials, (int)g, loss);
     RHO_LAUNCH_CHECK();
     return 0;
+}
+
+// The same reduction with the partials allocated and freed in stream order.  (Until ABI 7's rho_mse_ws this entry added one fp32
+// atomic per block in arrival order: from about a thousand blocks on - two million elements - the half-ulp lost by each atomic
+// summed to more than 1e-6 of a loss near 2, differently from run to run.)
+extern "C" int rho_mse(const float* a, const float* b, float* loss, float* grad_a, int64_t n, void* stream) {
+    if (!a || !b || !loss || n <= 0) return RHO_E_ARG;
+    const int64_t g = grid_for(n, 256 * 8);
+    float* partials = nullptr;
+    hipError_t e = hipMallocAsync((void**)&partials, (size_t)g * sizeof(float), as_stream(stream));
+    if (e != hipSuccess) return (int)e;
+    const int rc = rho_mse_ws(a, b, loss, grad_a, n, partials, g, stream);
+    e = hipFreeAsync(partials, as_stream(stream));
+    return rc != 0 ? rc : (int)e;
 }
 
 // mean over all non-batch axes (layers.py:105-110, mean_flat): one workgroup per sample, fp32 in a fixed order

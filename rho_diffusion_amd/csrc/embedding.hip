@@ -165,32 +165,15 @@ extern "C" int rho_multi_embed_bwd(const float* demb, const int32_t* idx, float*
 }
 
 // ----------------------------------------------------------------------------- random timesteps
-// Philox4x32-10 (same generator as rho_philox_normal, elementwise.hip): counter = offset + (i >> 2), word i & 3;
+// philox4x32_10 of common.h (the generator of rho_philox_normal and the dropout masks): counter = offset + (i >> 2), word i & 3;
 // t = floor(u32 * high / 2^32): uniform on [0, high) up to a bias of high / 2^32 (< 2.4e-7 for high <= 1000).
-__device__ __forceinline__ void philox_round_e(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
 __global__ void k_randint(int64_t* __restrict__ out, int64_t n, int64_t high, uint64_t seed, uint64_t offset,
                           const uint64_t* __restrict__ offset_dev) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint64_t ctr = (offset_dev ? *offset_dev : offset) + (uint64_t)(i >> 2);
-    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round_e(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[i] = (int64_t)(((uint64_t)c[i & 3] * (uint64_t)high) >> 32);
+    uint32_t r[4];
+    philox4x32_10((offset_dev ? *offset_dev : offset) + (uint64_t)(i >> 2), seed, r);
+    out[i] = (int64_t)(((uint64_t)r[i & 3] * (uint64_t)high) >> 32);
 }
 
 extern "C" int rho_randint(int64_t* out, int64_t n, int64_t high, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
