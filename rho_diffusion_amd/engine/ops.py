@@ -870,6 +870,20 @@ def gn_coeffs(x1: Tensor, x2: Optional[Tensor], gamma: Tensor, beta: Tensor, sca
     return a, b, stats
 
 
+def gn_apply_launch(x1: Tensor, x2: Optional[Tensor], pre: dict, act: int, out: Tensor, drop=None, drop_ctr: Optional[Tensor] = None):
+    """Launch closure (stream -> rc) of out = act(a * concat(x1, x2) + b) with the folded affine of ``pre`` (rho_gn_apply), or,
+    with ``drop`` = (p, seed, ...), the same pass under the Philox mask keyed by (seed, drop_ctr) (rho_gn_apply_drop)."""
+    c1 = x1.shape[-1]
+    c2 = x2.shape[-1] if x2 is not None else 0
+    a = (ptr(x1), c1, ptr(x2), c2, dtype_code(x1.dtype), x1.shape[0], x1.shape[1] * x1.shape[2] * x1.shape[3], ptr(pre["a"]),
+         ptr(pre["b"]), int(act), ptr(out))
+    L = hip.lib()
+    if drop is None:
+        return lambda s: L.rho_gn_apply(*a, s)
+    ad = a + (float(drop[0]), int(drop[1]), ptr(drop_ctr))
+    return lambda s: L.rho_gn_apply_drop(*ad, s)
+
+
 # ----------------------------------------------------------------------------- convolution
 def make_conv_desc(x1: Tensor, x2: Optional[Tensor], w: Tensor, bias: Tensor, *, kernel: Tuple[int, int, int],
                    cout: int, split: int, y: Optional[Tensor], y2: Optional[Tensor], stride_hw=(1, 1), up_hw=(0, 0),

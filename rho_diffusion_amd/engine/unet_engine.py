@@ -24,7 +24,8 @@ buffer is aliased (identity skips, residuals) or accumulated in the producing ke
 the choice is made once, when the plan is built.
 
 A plan (all descriptors + all buffers) is built once per (batch, spatial shape, mode) and replayed;
-buffer addresses are stable.  PyTorch supplies memory and streams only.
+buffer addresses are stable.  PyTorch supplies memory and streams only.  ``_Plan.__init__`` lowers the forward;
+the backward launches of a training plan are appended by ``backward_plan.BackwardBuilder``.
 """
 from __future__ import annotations
 
@@ -38,6 +39,7 @@ from torch import nn
 from .. import hip
 from ..hip import check, ptr
 from . import ops
+from .backward_plan import BackwardBuilder
 
 Tensor = torch.Tensor
 
@@ -98,6 +100,10 @@ class _ConvW:
             self.wphd = [((a, b), ops.prep_conv_weight_phase(self._source(), self.dtype, (a, b), dgrad=True)) for a in hs for b in ws]
             if self.zero_bias is None:
                 self.zero_bias = torch.zeros(((self.cin + 31) // 32) * 32, dtype=torch.float32, device=self.w.device)
+
+    def phase_kernel(self, ph) -> Tuple[int, int, int]:
+        """Kernel shape of the sub-pixel phase ``ph`` = (phase_h, phase_w): 2 taps along every upsampled axis."""
+        return (self.kernel[0], 2 if ph[0] else self.kernel[1], 2 if ph[1] else self.kernel[2])
 
     S2_FWD = {0: (1,), 1: (0, 2)}        # taps of the stride-2 forward on the even / odd input rows of a strided axis
     S2_BWD = {0: (1,), 1: (2, 0)}        # taps of its data gradient on the even / odd rows of dX
@@ -195,21 +201,6 @@ class _HeadAsGemm(_ConvW):
     """Head conv with cout == 1 viewed as a 1x1x1 conv cin -> taps (rows = taps, padded to 32 output channels) whose
     result rho_tap_gather_sum folds over the taps; the bias is added there."""
 
-    # its source is a transposed, zero-padded copy of the parameter, not a view: batched as a gather (RHO_PREP_VEC) through an
-    # index table built once - w[0][r = tap][c] = weight[0][c][r]
-    def prep_into(self, table: "ops.PrepTable") -> bool:
-        if not self.weight.is_contiguous():
-            return False
-        if getattr(self, "_perm", None) is None:
-            r = torch.arange(self.w.shape[1]).view(-1, 1)
-            c = torch.arange(self.w.shape[2]).view(1, -1)
-            idx = torch.where((r < self.taps3) & (c < self.cin), c * self.taps3 + r, torch.full_like(r + c, -1))
-            self._perm = idx.reshape(-1).to(torch.int32).to(self.w.device)
-        table.add_vec(self.weight.detach().reshape(-1), self.w, perm=self._perm, n=self.w.numel())
-        return True                                  # (b stays zero: the bias is added by the kernel that folds the taps)
-
-
-
     def __init__(self, weight: nn.Parameter, bias: nn.Parameter, dtype):
         self.taps3 = int(weight[0, 0].numel())
         self.kernel3 = tuple([1] * (3 - (weight.dim() - 2)) + [int(v) for v in weight.shape[2:]])
@@ -227,6 +218,19 @@ class _HeadAsGemm(_ConvW):
 
     def _bias_source(self) -> Tensor:
         return torch.zeros(32, dtype=torch.float32, device=self.weight.device)
+
+    # its source is a transposed, zero-padded copy of the parameter, not a view: batched as a gather (RHO_PREP_VEC) through an
+    # index table built once - w[0][r = tap][c] = weight[0][c][r]
+    def prep_into(self, table: "ops.PrepTable") -> bool:
+        if not self.weight.is_contiguous():
+            return False
+        if getattr(self, "_perm", None) is None:
+            r = torch.arange(self.w.shape[1]).view(-1, 1)
+            c = torch.arange(self.w.shape[2]).view(1, -1)
+            idx = torch.where((r < self.taps3) & (c < self.cin), c * self.taps3 + r, torch.full_like(r + c, -1))
+            self._perm = idx.reshape(-1).to(torch.int32).to(self.w.device)
+        table.add_vec(self.weight.detach().reshape(-1), self.w, perm=self._perm, n=self.w.numel())
+        return True                                  # (b stays zero: the bias is added by the kernel that folds the taps)
 
     def enable_dgrad(self) -> None:
         """A forward-only re-reading of the parameter ([1, C, taps] read as 32 rows x C): the generic data-gradient preparation
@@ -268,27 +272,6 @@ class _HeadDgradW:
         src = self.weight.detach().reshape(-1).float()
         g = torch.where(self._perm >= 0, src[self._perm.clamp(min=0).long()], torch.zeros((), device=src.device))   # (data movement only)
         self.w.copy_(g.view_as(self.w))
-
-
-class _Pool:
-    """Exact-size buffer pool for backward temporaries (emission order == stream order)."""
-
-    def __init__(self, device):
-        self.device = device
-        self.free: Dict[tuple, List[Tensor]] = {}
-        self.all: List[Tensor] = []
-
-    def get(self, shape, dtype) -> Tensor:
-        key = (int(torch.Size(shape).numel()), dtype)
-        lst = self.free.get(key)
-        if lst:
-            return lst.pop().view(*shape)
-        t = torch.empty(*shape, dtype=dtype, device=self.device)
-        self.all.append(t)
-        return t
-
-    def put(self, t: Tensor) -> None:
-        self.free.setdefault((t.numel(), t.dtype), []).append(t)
 
 
 class UNetEngine:
@@ -411,36 +394,24 @@ class UNetEngine:
         v = self._versions()
         if not force and v == self._param_version:
             return
-        if os.environ.get("RHO_BATCH_PREP", "1") != "0":
-            # ONE launch (rho_prep_batch) re-packs every layout of every conv, the padded biases and the FiLM matrix; the table is
-            # rebuilt when a layout is added (first training plan, phases, parity splits) or parameter storage moves
-            allw = self._convs + self._aux_weights
-            lsig = tuple(cw.layout_signature() for cw in allw) + tuple(blk.emb_layers[1].weight.data_ptr() for blk in self._film_blocks)
-            if self._prep_table is None or self._prep_sig != lsig:
-                table = ops.PrepTable(self.device)
-                self._prep_eager = [cw for cw in allw if not cw.prep_into(table)]
-                off = 0
-                for blk in self._film_blocks:
-                    lin = blk.emb_layers[1]
-                    n = lin.weight.shape[0]
-                    table.add_vec(lin.weight.detach().reshape(-1), self.film_w[off:off + n].reshape(-1))
-                    table.add_vec(lin.bias.detach(), self.film_b[off:off + n])
-                    off += n
-                self._prep_table, self._prep_sig = table, lsig
-            self._prep_table.launch()
-            for cw in self._prep_eager:
-                cw.refresh()
-            self._param_version = v
-            return
-        for cw in self._convs + self._aux_weights:
+        # ONE launch (rho_prep_batch) re-packs every layout of every conv, the padded biases and the FiLM matrix; the table is
+        # rebuilt when a layout is added (first training plan, phases, parity splits) or parameter storage moves
+        allw = self._convs + self._aux_weights
+        lsig = tuple(cw.layout_signature() for cw in allw) + tuple(blk.emb_layers[1].weight.data_ptr() for blk in self._film_blocks)
+        if self._prep_table is None or self._prep_sig != lsig:
+            table = ops.PrepTable(self.device)
+            self._prep_eager = [cw for cw in allw if not cw.prep_into(table)]
+            off = 0
+            for blk in self._film_blocks:
+                lin = blk.emb_layers[1]
+                n = lin.weight.shape[0]
+                table.add_vec(lin.weight.detach().reshape(-1), self.film_w[off:off + n].reshape(-1))
+                table.add_vec(lin.bias.detach(), self.film_b[off:off + n])
+                off += n
+            self._prep_table, self._prep_sig = table, lsig
+        self._prep_table.launch()
+        for cw in self._prep_eager:
             cw.refresh()
-        off = 0
-        for blk in self._film_blocks:
-            lin = blk.emb_layers[1]
-            n = lin.weight.shape[0]
-            self.film_w[off:off + n].copy_(lin.weight.detach())
-            self.film_b[off:off + n].copy_(lin.bias.detach())
-            off += n
         self._param_version = v
 
     def omega(self) -> Tensor:
@@ -521,9 +492,10 @@ class UNetEngine:
         return plan.run(x, timesteps, y, t_scalar_dev)
 
     # environment switches a plan reads while it is built (A/B knobs): part of the plan key, so flipping one rebuilds the plan
+    # (exactly the names this package's engine modules read - tests/test_host_logic.py holds the two lists together; the library's
+    #  own RHO_CONV_SPLITK is latched at its first launch, so no rebuild could follow it and it is not part of the key)
     _PLAN_ENV = ("RHO_TRAIN_MATERIALIZE", "RHO_MATERIALIZE_MIN_COUT", "RHO_PHASE_UPSAMPLE", "RHO_PHASE_UPSAMPLE_BWD", "RHO_PHASE_MIN_WGS",
-                 "RHO_FOLD_SKIP", "RHO_FOLD_SKIP_TRAIN", "RHO_S2_SPLIT", "RHO_S2_SPLIT_BWD", "RHO_FUSE_GN_BWD", "RHO_GEMM_ENDS",
-                 "RHO_DIRECT_ENDS", "RHO_CONV_SPLITK", "RHO_BATCH_PREP", "RHO_DW_ARENA", "RHO_FOLD_ADD", "RHO_FIN_BATCH_MB", "RHO_BWD_OVERLAP", "RHO_DIRECT_ENDS_TRAIN",
+                 "RHO_FOLD_SKIP", "RHO_S2_SPLIT", "RHO_S2_SPLIT_BWD", "RHO_FUSE_GN_BWD", "RHO_GEMM_ENDS", "RHO_DIRECT_ENDS",
                  "RHO_FUSE_SKIP_DGRAD")
 
     def _plan_signature(self) -> tuple:
@@ -567,8 +539,7 @@ class _Plan:
         self.phase_min_wgs = int(os.environ.get("RHO_PHASE_MIN_WGS", "256"))
         # bf16 engine: the ResBlock's 1x1x1 skip convolution inside its out-conv's forward launch (A/B switches)
         # (training plans: the forward launch only - backward keeps the skip branch's own data / weight-gradient launches)
-        self.fold_skip = (eng.dtype == torch.bfloat16 and os.environ.get("RHO_FOLD_SKIP", "1") != "0"
-                          and (not train or os.environ.get("RHO_FOLD_SKIP_TRAIN", "1") != "0"))
+        self.fold_skip = eng.dtype == torch.bfloat16 and os.environ.get("RHO_FOLD_SKIP", "1") != "0"
         self.s2_split = os.environ.get("RHO_S2_SPLIT", "1") != "0"
         self.s2_split_bwd = os.environ.get("RHO_S2_SPLIT_BWD", "1") != "0"
         # backward: GroupNorm's reductions (sum dz, sum dz * x) in the epilogue of the dgrad launch that produces dz (A/B switch)
@@ -723,15 +694,10 @@ class _Plan:
                 c1_ = x1.shape[-1]
                 c2_ = x2.shape[-1] if x2 is not None else 0
                 xact = (buf if keep_act else scratch)(*x1.shape[:4], c1_ + c2_)
-                Sx = x1.shape[1] * x1.shape[2] * x1.shape[3]
-                ga = (ptr(x1), c1_, ptr(x2), c2_, dtc, x1.shape[0], Sx, ptr(pre["a"]), ptr(pre["b"]), int(pre_silu), ptr(xact))
+                self.ops.append(ops.gn_apply_launch(x1, x2, pre, pre_silu, xact, drop, self.drop_ctr))
                 if drop is not None:
-                    gd = ga + (float(drop[0]), int(drop[1]), ptr(self.drop_ctr))
-                    self.ops.append(lambda s, a=gd: L.rho_gn_apply_drop(*a, s))
                     self.drop_delta = max(self.drop_delta, (xact.numel() + 3) // 4)
                     self.drop_nodes.append(dict(blk=drop[2], p=float(drop[0]), seed=int(drop[1]), shape=tuple(xact.shape)))
-                else:
-                    self.ops.append(lambda s, a=ga: L.rho_gn_apply(*a, s))
                 self.info.append(dict(kind="gn_apply", flops=0.0, bytes=2.0 * esz * xact.numel()))
                 cx1, cx2, cpre = xact, None, None
             # A conv behind a nearest x2 upsample as one 2-tap launch per output parity on the SOURCE tensor (rho_conv_desc.ph_h):
@@ -755,8 +721,8 @@ class _Plan:
                          for i, ((a, b), wt) in enumerate(cw.ws2)]
             elif phased:
                 cw.enable_phases(up_hw, dgrad=self.train)
-                descs = [ops.make_conv_desc(cx1, None, wt, cw.b, kernel=(cw.kernel[0], 2 if ph[0] else cw.kernel[1], 2 if ph[1] else cw.kernel[2]),
-                                            cout=cout, split=split_, y=y, y2=None, phase_hw=ph) for ph, wt in cw.wph]
+                descs = [ops.make_conv_desc(cx1, None, wt, cw.b, kernel=cw.phase_kernel(ph), cout=cout, split=split_, y=y, y2=None, phase_hw=ph)
+                         for ph, wt in cw.wph]
             else:
                 d = ops.make_conv_desc(cx1, cx2, cw.w, cw.b, kernel=cw.kernel, cout=cout, split=split_, y=y, y2=y2,
                                        stride_hw=stride_hw, up_hw=up_hw, pre_a=cpre["a"] if cpre else None,
@@ -821,9 +787,7 @@ class _Plan:
             c1_ = x1.shape[-1]
             c2_ = x2.shape[-1] if x2 is not None else 0
             yt = buf(*x1.shape[:4], c1_ + c2_)
-            Sx = x1.shape[1] * x1.shape[2] * x1.shape[3]
-            ga = (ptr(x1), c1_, ptr(x2), c2_, dtc, x1.shape[0], Sx, ptr(pre["a"]), ptr(pre["b"]), int(pre_silu), ptr(yt))
-            self.ops.append(lambda s, a=ga: L.rho_gn_apply(*a, s))
+            self.ops.append(ops.gn_apply_launch(x1, x2, pre, pre_silu, yt))
             self.info.append(dict(kind="gn_apply", flops=0.0, bytes=2.0 * esz * yt.numel()))
             self.nodes.append(dict(k="act", x1=x1, x2=x2, pre=pre, pre_silu=pre_silu, y=yt))
             return yt
@@ -946,11 +910,10 @@ class _Plan:
         # 3-D, one input / output channel: each end is ONE launch with its intermediate in LDS (csrc/ends.hip; A/B switch) instead
         # of the GEMM form's two (im2col + GEMM, GEMM + tap gather)
         direct_ends = gemm_ends and dims == 3 and os.environ.get("RHO_DIRECT_ENDS", "1") != "0"
-        # training plans (round 4): the same two forward launches; their backward = GEMM-shaped weight gradients against an im2col
+        # training plans: the same two forward launches; their backward = GEMM-shaped weight gradients against an im2col
         # of the one-channel operand (k_wgrad1) and, for the head's data gradient, rho_stem_conv3d on dpred with mirrored taps -
         # instead of 3x3x3 launches whose single channel is padded to 32 (31 / 32 of their matrix work on zeros)
-        direct_ends_train = (train and dt == torch.bfloat16 and dims == 3 and os.environ.get("RHO_DIRECT_ENDS", "1") != "0"
-                             and os.environ.get("RHO_DIRECT_ENDS_TRAIN", "1") != "0" and os.environ.get("RHO_DW_ARENA", "1") != "0")
+        direct_ends_train = train and dt == torch.bfloat16 and dims == 3 and os.environ.get("RHO_DIRECT_ENDS", "1") != "0"
         stem_direct = None
         if (direct_ends or direct_ends_train) and xshape[1] == 1 and tuple(stem.kernel) == (3, 3, 3) and stem.cout in (32, 64):
             sg = eng._conv_as_gemm(m.input_blocks[0][0], _StemAsGemm)
@@ -999,8 +962,7 @@ class _Plan:
                 # training: the activated input is kept (the head's weight gradient contracts it with the im2col of dpred);
                 # a non-SiLU activation: applied by the materialising pass (the head kernel's own prologue knows SiLU only)
                 xact = (buf if train else scratch)(B, D, H, W, h.shape[-1])
-                ga0 = (ptr(h), h.shape[-1], None, 0, dtc, B, D * H * W, ptr(g["a"]), ptr(g["b"]), eng.act, ptr(xact))
-                self.ops.append(lambda s, a=ga0: L.rho_gn_apply(*a, s))
+                self.ops.append(ops.gn_apply_launch(h, None, g, eng.act, xact))
                 self.info.append(dict(kind="gn_apply", flops=0.0, bytes=2.0 * esz * xact.numel()))
                 ga = (ptr(xact), None, None, 0, ptr(hg.w), ptr(m.out[2].bias), ptr(y2), B, D, H, W, h.shape[-1])
                 if train:
@@ -1025,716 +987,11 @@ class _Plan:
         self.bwd_info: List[dict] = []
         self.bwd_marks: List[Tuple[int, List[nn.Parameter]]] = []   # after bwd[:i] these parameters' gradients are final
         if train:
-            self._build_backward()
+            BackwardBuilder(self).build()
         # k-split of the small-grid 2-D / 1-D launches (rho_conv_desc.ws): one workspace per plan, shared by its ordered launches
         ws = ops.attach_conv_workspace(self.fwd_descs, dev)
         if ws is not None:
             self.keep.append(ws)
-
-    # ------------------------------------------------------------------ backward construction
-    def _build_backward(self) -> None:
-        eng, L = self.eng, self.L
-        m = eng.model
-        dt = eng.dtype
-        dtc = hip.dtype_code(dt)
-        dev = eng.device
-        B = self.B
-        pool = _Pool(dev)
-        self.keep.append(pool)
-        for cw in eng._convs:
-            cw.enable_dgrad()
-        G: Dict[int, Tensor] = {}        # activation data_ptr -> gradient buffer
-        written = set()
-        bw, binfo = self.bwd, self.bwd_info
-        esz = 2 if dt == torch.bfloat16 else 4
-
-        def key(t: Tensor) -> int:
-            return t.data_ptr()
-
-        # ---- overlap of the HBM-bound GroupNorm backward with the weight gradient (round 4; RHO_BWD_OVERLAP=0: one stream).  Per
-        # normalised conv the order on the launch stream was  wgrad | dgrad | gn_bwd reduce / finalize / apply  - three kernels that
-        # cannot share the chip (two matrix-bound, one at HBM rate: 24 ms of passes per c3 step with the matrix cores idle).  The
-        # weight gradient is off the critical path (it needs dY only), so it now goes to a SIDE stream right after the data gradient:
-        #     main:  dgrad ............ | gn_bwd reduce, finalize, apply | (wait) next node
-        #     side:                     | wgrad ....................... |
-        # one wave per SIMD of k_wgrad leaves registers and wave slots for the elementwise passes, which run in its shadow.  Only
-        # this pair overlaps: the next node's launches wait for the side stream (two matrix-bound kernels sharing the CUs cost more in
-        # L2 locality than they return - measured in round 3).  Pool buffers released by the weight-gradient path are recycled after
-        # that wait only.
-        # MEASURED (same-box A/B, c3): 406.3 / 402.1 ms per step with the side stream against 398.5 / 400.0 without - the passes do not
-        # hide (the weight gradient slows by as much as they take), so this stays OFF; the switch remains for other shapes.
-        overlap = os.environ.get("RHO_BWD_OVERLAP", "0") != "0"
-        self._side = torch.cuda.Stream(device=dev) if overlap else None
-        self._overlap_on = True                      # profile() turns it off: per-launch timings need the serial order
-        defer: Dict[str, object] = {"on": False, "ops": [], "puts": []}
-
-        def emit(fn, kind, flops=0.0, nbytes=0.0, **shape):
-            info = dict(kind=kind, flops=flops, bytes=nbytes, **shape)
-            if defer["on"]:
-                defer["ops"].append((fn, info))
-                return
-            bw.append(fn)
-            binfo.append(info)
-
-        def wput(t: Tensor):
-            """pool.put for buffers the weight-gradient path read: held back while that path is being deferred to the side stream."""
-            if defer["on"]:
-                defer["puts"].append(t)
-            else:
-                pool.put(t)
-
-        def flush_side():
-            """Emit the deferred weight-gradient launches as side-stream launches (called right after the data-gradient launch)."""
-            for fn, info in defer["ops"]:
-                ev = torch.cuda.Event()
-
-                def run(s, fn=fn, ev=ev):
-                    if not self._overlap_on:
-                        return fn(s)
-                    ev.record(torch.cuda.current_stream())
-                    self._side.wait_event(ev)
-                    return fn(self._side.cuda_stream)
-                bw.append(run)
-                binfo.append(info)
-            defer["ops"] = []
-
-        def join_side():
-            ev = torch.cuda.Event()
-
-            def run(s, ev=ev):
-                if self._overlap_on:
-                    ev.record(self._side)
-                    torch.cuda.current_stream().wait_event(ev)
-                return 0
-            bw.append(run)
-            binfo.append(dict(kind="sync", flops=0.0, bytes=0.0))
-            for t in defer["puts"]:
-                pool.put(t)
-            defer["puts"] = []
-
-        # Residual adds folded into the next GroupNorm-backward apply pass (round 4; RHO_FOLD_ADD=0: a pass of their own as before):
-        # `G[res] += dY` of a residual connection whose target already holds a gradient is NOT launched; the addend waits here
-        # until the apply pass that accumulates into G[res] anyway takes it as `add1` (one read instead of read + read + write).
-        # Any other access to G[res] flushes it as the plain rho_add_inplace first.
-        fold_add = os.environ.get("RHO_FOLD_ADD", "1") != "0"
-        pending_add: Dict[int, Tensor] = {}
-        skip_partner: Dict[int, int] = {}               # id(1x1x1 skip node) -> id(the block's in-conv node), see fuse_skip_dgrad
-        held_skips: Dict[int, tuple] = {}               # id(in-conv node) -> (skip node, dY, width) waiting for its GroupNorm backward
-
-        def flush_add(k: int):
-            src = pending_add.pop(k, None)
-            if src is not None:
-                a = (ptr(G[k]), ptr(src), dtc, src.numel())
-                emit(lambda s, a=a: L.rho_add_inplace(*a, s), "add", nbytes=3.0 * esz * src.numel())
-                if src.data_ptr() not in {g_.data_ptr() for g_ in G.values()}:
-                    pool.put(src)
-
-        def gradbuf(t: Tensor, fold_ok: bool = False):
-            """(buffer, accumulate?) for a write into the gradient of activation t."""
-            k = key(t)
-            if not fold_ok:
-                flush_add(k)
-            if k in G:
-                return G[k], (k in written)
-            G[k] = pool.get(tuple(t.shape), t.dtype)
-            return G[k], False
-
-        # scratch shared by all layers (stream-ordered reuse)
-        max_w = max(cw.taps * cw.coutp * cw.cinp for cw in eng._convs)
-        dwbuf = torch.empty(max_w, dtype=torch.float32, device=dev)
-        max_c = max(max(cw.coutp, cw.cinp) for cw in eng._convs)
-        nc_tmp = torch.empty(B * max(max_c, 64), dtype=torch.float32, device=dev)
-        c_tmp = torch.empty(max(max_c, 64), dtype=torch.float32, device=dev)
-        self.dfilm = torch.empty(B, max(eng.film_total, 1), dtype=torch.float32, device=dev)
-        self.demb = torch.empty(B, 4 * eng.mc, dtype=torch.float32, device=dev)
-        self.demb_h = torch.empty(B, 4 * eng.mc, dtype=torch.float32, device=dev)
-        self.keep.extend([dwbuf, nc_tmp, c_tmp])
-        film_stride = self.film.shape[1]
-
-        def pgrad(p: nn.Parameter) -> int:
-            return p.grad.data_ptr()       # resolved at launch time: optimizers may re-home .grad
-
-        # Deterministic training (rho_set_deterministic / RHO_DETERMINISTIC=1): the weight gradient flushes through ordered slabs
-        # (rho_conv_nd_wgrad_ws) instead of fp32 atomics; one workspace per plan, sized for its largest launch after all are known
-        self.deterministic = ops.deterministic()
-        det_ws: Dict[str, object] = {"bytes": 0, "t": None}
-
-        def wgrad_call(d, dy_ptr: int, w_: int, dw_ptr: Callable[[], int], db_ptr: Callable[[], int]):
-            if not self.deterministic:
-                return lambda s: L.rho_conv_nd_wgrad(C.byref(d), dy_ptr, w_, dw_ptr(), db_ptr(), s)
-            det_ws["bytes"] = max(det_ws["bytes"], int(L.rho_conv_wgrad_workspace_bytes(C.byref(d), w_)))
-            return lambda s: L.rho_conv_nd_wgrad_ws(C.byref(d), dy_ptr, w_, dw_ptr(), db_ptr(), ptr(det_ws["t"]), det_ws["bytes"], s)
-        self._det_ws = det_ws
-
-        # ---- weight-gradient accumulation ARENA (round 4; RHO_DW_ARENA=0 restores the shared scratch): every weight-gradient launch
-        # accumulates into a region of its own ([taps][coutp][cinp] fp32 + the channel sums), the whole arena is cleared by ONE memset
-        # at the head of the backward, and the regions are moved into the parameter gradients by ONE table-driven launch per ~32 MiB
-        # of parameters (rho_wgrad_finalize_batch) - instead of a memset + finalize + bias-gradient launch per convolution
-        # (~250 launches of a few microseconds each per step).  Parameters are reported final (bwd_marks) after their batch.
-        use_arena = os.environ.get("RHO_DW_ARENA", "1") != "0"
-        arena: Dict[str, object] = {"t": None, "floats": 0}
-        # (a batch closes at 32 MiB of parameters, or a sixteenth of the model where that is smaller, so that data-parallel buckets
-        #  still become final - and their all-reduce still starts - well inside the backward)
-        fin_batch_bytes = min(int(float(os.environ.get("RHO_FIN_BATCH_MB", "32")) * 2 ** 20),
-                              max(1, sum(4 * cw.weight.numel() for cw in eng._convs) // 16))
-        fin: Dict[str, object] = {"entries": [], "params": [], "bytes": 0}
-        self._arena = arena
-
-        def region(nfloats: int) -> int:
-            off = arena["floats"]
-            arena["floats"] = off + ((int(nfloats) + 63) // 64) * 64
-            return off
-
-        def aptr(off: int) -> Callable[[], int]:
-            return lambda: arena["t"].data_ptr() + 4 * off
-
-        def fin_add(**e):
-            fin["entries"].append(e)
-
-        def fin_close(force: bool = False):
-            """Emit the batched finalize of the pending regions (and report their parameters final) once enough bytes are pending."""
-            if not fin["entries"] or (not force and fin["bytes"] < fin_batch_bytes):
-                return
-            entries, params = fin["entries"], fin["params"]
-            fin["entries"], fin["params"], fin["bytes"] = [], [], 0
-            state = {"sig": None, "dev": None, "blocks": 0}
-
-            def run(s, entries=entries, state=state):
-                sig = (arena["t"].data_ptr(),) + tuple(pgrad(e["param"]) for e in entries)
-                if sig != state["sig"]:
-                    raw, blk = [], 0
-                    for e in entries:
-                        op = hip.WfinOp()
-                        op.dw, op.grad, op.row_src = arena["t"].data_ptr() + 4 * e["off"], pgrad(e["param"]), e["rs"]
-                        op.cout, op.cin, op.coutp, op.cinb = e["cout"], e["cin"], e["coutp"], e["cinb"]
-                        op.kd, op.kh, op.kw = e["k"]
-                        op.total = e["cout"] * e["cin"] * e["k"][0] * e["k"][1] * e["k"][2]
-                        op.kind, op.up_h, op.up_w, op.phase_stride = e["kind"], e.get("up_h", 0), e.get("up_w", 0), e.get("stride", 0)
-                        op.nblk = max(1, min((op.total + 255) // 256, 512))
-                        op.blk0 = blk
-                        blk += op.nblk
-                        raw.append(bytes(op))
-                    state["dev"] = torch.frombuffer(bytearray(b"".join(raw)), dtype=torch.uint8).to(dev)
-                    state["blocks"], state["sig"] = blk, sig
-                return L.rho_wgrad_finalize_batch(state["dev"].data_ptr(), len(entries), state["blocks"], s)
-            emit(run, "wgrad_finalize", nbytes=12.0 * sum(e["cout"] * e["cin"] * e["k"][0] * e["k"][1] * e["k"][2] for e in entries))
-            self.keep.append(state)
-            self.bwd_marks.append((len(bw), params))
-
-        if use_arena:
-            emit(lambda s: (arena["t"].zero_(), 0)[1], "memset")
-            arena_memset_info = binfo[-1]
-
-        def bias_and_wgrad(node, dY: Tensor, dyw: int):
-            cw = node["cw"]
-            N, Do, Ho, Wo = node["out_dims"]
-            S = Do * Ho * Wo
-            nblk = ops.gn_nblk(S)
-            part = pool.get((N * nblk * (dyw // 8) * 16,), torch.float32)
-            rs = ptr(cw.row_src)
-            # bias gradient = channel sums of dY: accumulated by the weight-gradient kernel itself (below)
-            if node["res_add_off"] is not None:        # additive timestep embedding (unet_v2.py:291)
-                dst = self.dfilm.data_ptr() + 4 * node["res_add_off"]
-                a = (ptr(dY), dtc, N, S, dyw, ptr(part), dst, film_stride, 0, None, 0)
-                emit(lambda s, a=a: L.rho_chan_sum(*a, s), "chan_sum", nbytes=float(esz) * N * S * dyw)
-            wput(part)
-            if node.get("phased") and node["pre"] is None and node["x2"] is None and self.phase_upsample_bwd:
-                # Upsample + conv ran as sub-pixel phases: per phase a 2-tap weight gradient on the SOURCE tensor against that parity
-                # of dY (12 / 27 of the multiply-adds, no upsampled copy), routed back to the 3-tap parameter gradient
-                x1 = node["x1"]
-                if use_arena:
-                    nwp = max(kk[0] * kk[1] * kk[2] for kk in [(cw.kernel[0], 2 if ph_[0] else cw.kernel[1], 2 if ph_[1] else cw.kernel[2])
-                                                                for ph_, _ in cw.wph]) * cw.coutp * cw.cinp
-                    stride_ = ((nwp + 63) // 64) * 64
-                    off_b, off0 = region(max(dyw, cw.coutp)), region(stride_ * len(cw.wph))
-                    for idx, (ph, wt) in enumerate(cw.wph):
-                        kern = (cw.kernel[0], 2 if ph[0] else cw.kernel[1], 2 if ph[1] else cw.kernel[2])
-                        d = ops.make_conv_desc(x1, None, wt, cw.b, kernel=kern, cout=cw.cout, split=cw.cout, y=dY, y2=None, phase_hw=ph)
-                        self.keep.append(d)
-                        self.wgrad_descs.append((d, dyw))
-                        emit(wgrad_call(d, ptr(dY), dyw, aptr(off0 + idx * stride_), aptr(off_b)), "wgrad",
-                             flops=2.0 * N * S * cw.cout * cw.cin * cw.taps / len(cw.wph),
-                             nbytes=float(esz) * (x1.numel() + dY.numel() / len(cw.wph)),
-                             cin=cw.cin, cout=cw.cout, taps=cw.taps, positions=N * S // len(cw.wph))
-                    up_h_, up_w_ = int(any(ph[0] for ph, _ in cw.wph)), int(any(ph[1] for ph, _ in cw.wph))
-                    fin_add(kind=1, off=off0, param=cw.weight, rs=None, cout=cw.cout, cin=cw.cin, coutp=cw.coutp, cinb=cw.cinp, k=cw.kernel,
-                            up_h=up_h_, up_w=up_w_, stride=stride_)
-                    fin_add(kind=0, off=off_b, param=cw.bias_param, rs=rs, cout=cw.cout, cin=1, coutp=dyw, cinb=1, k=(1, 1, 1))
-                    fin["params"] += [cw.weight, cw.bias_param]
-                    fin["bytes"] += 4 * cw.weight.numel()
-                    return
-                cbv = c_tmp[:max(dyw, cw.coutp)]
-                emit(lambda s, t2=cbv: (t2.zero_(), 0)[1], "memset", nbytes=4.0 * cbv.numel())
-                for ph, wt in cw.wph:
-                    kern = (cw.kernel[0], 2 if ph[0] else cw.kernel[1], 2 if ph[1] else cw.kernel[2])
-                    d = ops.make_conv_desc(x1, None, wt, cw.b, kernel=kern, cout=cw.cout, split=cw.cout, y=dY, y2=None, phase_hw=ph)
-                    self.keep.append(d)
-                    self.wgrad_descs.append((d, dyw))
-                    nwp = kern[0] * kern[1] * kern[2] * cw.coutp * cw.cinp
-                    dwv = dwbuf[:nwp]
-                    emit(lambda s, t=dwv: (t.zero_(), 0)[1], "memset", nbytes=4.0 * nwp)
-                    emit(wgrad_call(d, ptr(dY), dyw, lambda: ptr(dwbuf), lambda: ptr(c_tmp)), "wgrad",
-                         flops=2.0 * N * S * cw.cout * cw.cin * cw.taps / len(cw.wph),
-                         nbytes=float(esz) * (x1.numel() + dY.numel() / len(cw.wph)),
-                         cin=cw.cin, cout=cw.cout, taps=cw.taps, positions=N * S // len(cw.wph))
-                    emit(lambda s, cw=cw, ph=ph: L.rho_wgrad_finalize_phase(ptr(dwbuf), pgrad(cw.weight), cw.cout, cw.cin, cw.kernel[0],
-                                                                           cw.kernel[1], cw.kernel[2], ph[0], ph[1], cw.coutp, cw.cinp, 1, s),
-                         "wgrad_finalize", nbytes=8.0 * nwp)
-                emit(lambda s, cw=cw, rs=rs, w_=dyw: L.rho_wgrad_finalize(ptr(c_tmp), pgrad(cw.bias_param), cw.cout, 1, 1, w_, 1, rs, 1, s),
-                     "bias_grad")
-                return
-            # weight gradient (forward descriptor; upsampled input materialised)
-            x1 = node["x1"]
-            tmp_up = None
-            if node["up_hw"] != (0, 0):
-                uh, uw = node["up_hw"]
-                tmp_up = pool.get((x1.shape[0], x1.shape[1], x1.shape[2] * (2 if uh else 1), x1.shape[3] * (2 if uw else 1),
-                                   x1.shape[4]), dt)
-                a = (ptr(x1), ptr(tmp_up), dtc, x1.shape[0] * x1.shape[1], x1.shape[2], x1.shape[3], x1.shape[4], int(uh), int(uw))
-                emit(lambda s, a=a: L.rho_upsample2x(*a, s), "upsample", nbytes=5.0 * esz * x1.numel())
-                x1 = tmp_up
-            pre = node["pre"]
-            x2 = node["x2"]
-            xact = None
-            if node.get("xact") is not None:
-                x1, x2 = node["xact"], None              # materialised by the forward plan
-            elif pre is not None:
-                # materialise act(a*x+b) once (HBM-rate) instead of redoing it in every (cout tile, cin chunk) workgroup
-                c1_ = x1.shape[-1]
-                c2_ = x2.shape[-1] if x2 is not None else 0
-                xact = pool.get(tuple(x1.shape[:4]) + (c1_ + c2_,), dt)
-                Nn = x1.shape[0]
-                Sx = x1.shape[1] * x1.shape[2] * x1.shape[3]
-                a = (ptr(x1), c1_, ptr(x2), c2_, dtc, Nn, Sx, ptr(pre["a"]), ptr(pre["b"]), int(node["pre_silu"]), ptr(xact))
-                if node.get("drop") is not None:     # the same mask as the forward: same key, same counter
-                    ad = a + (float(node["drop"][0]), int(node["drop"][1]), ptr(self.drop_ctr))
-                    emit(lambda s, a=ad: L.rho_gn_apply_drop(*a, s), "gn_apply", nbytes=2.0 * esz * xact.numel())
-                else:
-                    emit(lambda s, a=a: L.rho_gn_apply(*a, s), "gn_apply", nbytes=2.0 * esz * xact.numel())
-                x1, x2 = xact, None
-            d = ops.make_conv_desc(x1, x2, cw.w, cw.b, kernel=cw.kernel, cout=cw.cout, split=cw.cout, y=dY, y2=None,
-                                   stride_hw=node["stride_hw"], pre_silu=False)
-            self.keep.append(d)
-            self.wgrad_descs.append((d, dyw))
-            nw = cw.taps * cw.coutp * cw.cinp
-            if use_arena:
-                off_w, off_b = region(nw), region(max(dyw, cw.coutp))
-                emit(wgrad_call(d, ptr(dY), dyw, aptr(off_w), aptr(off_b)), "wgrad",
-                     flops=2.0 * N * S * cw.cout * cw.cin * cw.taps, nbytes=float(esz) * (x1.numel() + dY.numel()),
-                     cin=cw.cin, cout=cw.cout, taps=cw.taps, positions=N * S)
-                fin_add(kind=0, off=off_w, param=cw.weight, rs=rs, cout=cw.cout, cin=cw.cin, coutp=cw.coutp, cinb=cw.cinp, k=cw.kernel)
-                fin_add(kind=0, off=off_b, param=cw.bias_param, rs=rs, cout=cw.cout, cin=1, coutp=dyw, cinb=1, k=(1, 1, 1))
-                fin["params"] += [cw.weight, cw.bias_param]
-                fin["bytes"] += 4 * cw.weight.numel()
-                if tmp_up is not None:
-                    wput(tmp_up)
-                if xact is not None:
-                    wput(xact)
-                return
-            dwv = dwbuf[:nw]
-            cbv = c_tmp[:max(dyw, cw.coutp)]
-            emit(lambda s, t=dwv, t2=cbv: (t.zero_(), t2.zero_(), 0)[2], "memset", nbytes=4.0 * nw)
-            emit(wgrad_call(d, ptr(dY), dyw, lambda: ptr(dwbuf), lambda: ptr(c_tmp)), "wgrad",
-                 flops=2.0 * N * S * cw.cout * cw.cin * cw.taps, nbytes=float(esz) * (x1.numel() + dY.numel()),
-                 cin=cw.cin, cout=cw.cout, taps=cw.taps, positions=N * S)
-            emit(lambda s, cw=cw, rs=rs: L.rho_wgrad_finalize(ptr(dwbuf), pgrad(cw.weight), cw.cout, cw.cin, cw.taps, cw.coutp,
-                                                              cw.cinp, rs, 1, s), "wgrad_finalize", nbytes=8.0 * nw)
-            # (row-permuted, truncated) accumulate of the channel sums into bias.grad
-            emit(lambda s, cw=cw, rs=rs, w_=dyw: L.rho_wgrad_finalize(ptr(c_tmp), pgrad(cw.bias_param), cw.cout, 1, 1, w_, 1, rs, 1, s),
-                 "bias_grad")
-            if tmp_up is not None:
-                wput(tmp_up)
-            if xact is not None:
-                wput(xact)
-
-        def gn_backward(pre, pre_silu, x1, x2, dact, fused=None, drop=None, skip=None):
-            """dact = gradient of act(GroupNorm(x) * (1 + scale) + shift): reduce / finalize / apply into the gradients of x1 (, x2),
-            the norm's parameters and the FiLM rows.  ``fused`` = (tile sums, tiles per sample) when the dgrad launch that produced
-            dact already reduced dz and dz * x in its epilogue (rho_conv_desc.gnb_*): the reduce pass is skipped.  ``skip`` = (node,
-            dY, width) of the block's 1x1x1 skip convolution whose data gradient was held back: it runs here, with the apply pass in
-            its epilogue (rho_conv_desc.gna_*), or - where that launch does not exist - on its own in front of the apply pass."""
-            c1 = x1.shape[-1]
-            c2 = x2.shape[-1] if x2 is not None else 0
-            norm = pre["norm"]
-            Cc, N_, S_ = pre["C"], pre["N"], pre["S"]
-            skip_fused = None
-            if skip is not None:
-                sk_node, sk_dY, sk_w = skip
-                can = (drop is None and int(pre_silu) <= 1 and key(x1) not in written and key(x1) not in pending_add
-                       and (x2 is None or key(x2) not in written) and S_ % 256 == 0 and Cc % 32 == 0
-                       and (x2 is None or c2 % (8 if dt == torch.bfloat16 else 4) == 0))
-                if can:
-                    skip_fused = skip
-                else:
-                    dgrad(sk_node, sk_dY, sk_w, hold_skip=False)          # the two-pass form: data gradient first, apply accumulates
-                    pool.put(sk_dY)
-            g1, acc1 = gradbuf(x1, fold_ok=True)
-            add1 = pending_add.pop(key(x1), None)              # a residual's gradient waiting to join G[x1]: folded into this pass
-            g2, acc2 = gradbuf(x2) if x2 is not None else (None, False)
-            cA = pool.get((N_, Cc), torch.float32)
-            cP = pool.get((N_, 32), torch.float32)
-            cQ = pool.get((N_, 32), torch.float32)
-            work = pool.get((2 * N_ * Cc,), torch.float32)
-            scale = dscale = dshift = None
-            fstride = 0
-            if pre["film_off"] is not None:
-                scale = self.film.data_ptr() + 4 * pre["film_off"]
-                fstride = film_stride
-                dscale = self.dfilm.data_ptr() + 4 * pre["film_off"]
-                dshift = self.dfilm.data_ptr() + 4 * (pre["film_off"] + Cc)
-            if fused is None:
-                a1 = (ptr(dact), ptr(x1), c1, ptr(x2), c2, dtc, N_, S_, ptr(pre["a"]), ptr(pre["b"]), ptr(pre["st"]),
-                      int(pre_silu), ptr(pre["part"]))
-                if drop is not None:
-                    a1d = a1 + (float(drop[0]), int(drop[1]), ptr(self.drop_ctr))
-                    emit(lambda s, a=a1d: L.rho_gn_bwd_reduce_drop(*a, s), "gn_bwd_reduce", nbytes=2.0 * esz * N_ * S_ * Cc)
-                else:
-                    emit(lambda s, a=a1: L.rho_gn_bwd_reduce(*a, s), "gn_bwd_reduce", nbytes=2.0 * esz * N_ * S_ * Cc)
-                part_ptr, part_n, fmt = ptr(pre["part"]), pre["nblk"], 0
-            else:
-                part_ptr, part_n, fmt = ptr(fused[0]), fused[1], 1
-            emit(lambda s, pre=pre, norm=norm, scale=scale, fstride=fstride, work=work, dscale=dscale, dshift=dshift,
-                 cA=cA, cP=cP, cQ=cQ, N_=N_, Cc=Cc, S_=S_, part_ptr=part_ptr, part_n=part_n, fmt=fmt: L.rho_gn_bwd_finalize(
-                     part_ptr, N_, Cc, S_, part_n, fmt, ptr(norm.weight), ptr(norm.bias), scale, fstride, ptr(pre["st"]),
-                     ptr(work), pgrad(norm.weight), pgrad(norm.bias), 1, dscale, dshift, film_stride, ptr(cA), ptr(cP),
-                     ptr(cQ), s), "gn_bwd_finalize")
-            a3 = (ptr(dact), ptr(x1), c1, ptr(x2), c2, dtc, N_, S_, ptr(pre["a"]), ptr(pre["b"]), int(pre_silu),
-                  ptr(cA), ptr(cP), ptr(cQ), ptr(g1), ptr(g2), int(acc1), int(acc2), ptr(add1))
-            nb3 = esz * N_ * S_ * (3.0 * Cc + (c1 if acc1 else 0) + (c2 if acc2 else 0) + (c1 if add1 is not None else 0))
-            if skip_fused is not None:
-                # dX = skip^T(dY) + [cA * (dact * act'(a x + b)) + cQ * x + cP] in the 1x1x1 data-gradient launch's epilogue
-                sk_node, sk_dY, sk_w = skip_fused
-                scw = sk_node["cw"]
-                if acc1 or acc2 or add1 is not None:
-                    raise hip.RhoHipError("internal: fused skip data gradient on a gradient that already has a writer (backward plan)")
-                d = ops.make_conv_desc(sk_dY, None, scw.wd, scw.zero_bias, kernel=scw.kernel, cout=Cc, split=c1, y=g1, y2=g2,
-                                       y2_cl=x2 is not None)
-                d.gnb_x1, d.gnb_x2, d.gnb_c1, d.gnb_silu = ptr(x1), ptr(x2), c1, int(pre_silu)
-                d.gnb_a, d.gnb_b = ptr(pre["a"]), ptr(pre["b"])
-                d.gna_g, d.gna_cA, d.gna_cP, d.gna_cQ = ptr(dact), ptr(cA), ptr(cP), ptr(cQ)
-                self.keep.append(d)
-                self.fwd_descs.append(d)
-                emit(lambda s, d=d: L.rho_conv_nd_fwd(C.byref(d), s), "dgrad", flops=2.0 * N_ * S_ * Cc * scw.cout,
-                     nbytes=float(esz) * (sk_dY.numel() + 3.0 * N_ * S_ * Cc))
-                pool.put(sk_dY)
-            elif drop is not None:
-                a3d = a3 + (float(drop[0]), int(drop[1]), ptr(self.drop_ctr))
-                emit(lambda s, a=a3d: L.rho_gn_bwd_apply_drop(*a, s), "gn_bwd_apply", nbytes=nb3)
-            else:
-                emit(lambda s, a=a3: L.rho_gn_bwd_apply(*a, s), "gn_bwd_apply", nbytes=nb3)
-            if add1 is not None and add1.data_ptr() not in {g_.data_ptr() for g_ in G.values()}:
-                pool.put(add1)                                 # (stream order: recycled buffers are written by later launches only)
-            written.add(key(x1))
-            if x2 is not None:
-                written.add(key(x2))
-            for t in (cA, cP, cQ, work):
-                pool.put(t)
-
-        def dgrad(node, dY: Tensor, dyw: int, after_launch: Optional[Callable[[], None]] = None, hold_skip: bool = True):
-            """Data gradient of a conv node.  Returns True when the launch was held back: the 1x1x1 skip convolution of a ResBlock
-            whose in-conv path ends in a GroupNorm backward of the same inputs - it runs inside that pass (gn_backward's ``skip``)."""
-            cw = node["cw"]
-            if hold_skip and id(node) in skip_partner:
-                held_skips[skip_partner[id(node)]] = (node, dY, dyw)
-                return True
-            x1, x2, pre = node["x1"], node["x2"], node["pre"]
-            c1 = x1.shape[-1]
-            c2 = x2.shape[-1] if x2 is not None else 0
-            cin = c1 + c2
-            if dyw != cw.wd.shape[2] or cw.wd.shape[1] != cin:
-                raise hip.RhoHipError("internal: dgrad weight shape does not match the gradient tensors")
-            common = dict(kernel=cw.kernel, cout=cin)
-            if node.get("phased") and pre is None and x2 is None and self.phase_upsample_bwd:
-                # Upsample + conv ran as sub-pixel phases: each phase's share of dX is a 2-tap conv of that parity of dY with the
-                # phase's flipped weights, accumulated in place - 12 / 27 of the multiply-adds, no full-resolution intermediate
-                g1, acc1 = gradbuf(x1)
-                for i, (ph, wt) in enumerate(cw.wphd):
-                    kern = (cw.kernel[0], 2 if ph[0] else cw.kernel[1], 2 if ph[1] else cw.kernel[2])
-                    d = ops.make_conv_desc(dY, None, wt, cw.zero_bias, kernel=kern, cout=cin, split=cin, y=g1, y2=None,
-                                           res=g1 if (acc1 or i > 0) else None, phase_dgrad_hw=ph)
-                    self.keep.append(d)
-                    self.fwd_descs.append(d)
-                    emit(lambda s, d=d: L.rho_conv_nd_fwd(C.byref(d), s), "dgrad",
-                         flops=2.0 * (dY.numel() // dyw) * cin * cw.cout * cw.taps / len(cw.wphd),
-                         nbytes=float(esz) * (dY.numel() / len(cw.wphd) + x1.numel() * (2 if (acc1 or i > 0) else 1)))
-                written.add(key(x1))
-            elif pre is not None or node["up_hw"] != (0, 0):
-                N, Do, Ho, Wo = node["out_dims"]
-                tshape = (N, Do, Ho, Wo, cin) if node["up_hw"] != (0, 0) else tuple(x1.shape[:4]) + (cin,)
-                dact = pool.get(tshape, dt)       # gradient of the activated / upsampled tensor
-                d = ops.make_conv_desc(dY, None, cw.wd, cw.zero_bias, split=cin, y=dact, y2=None, **common)
-                fused = None
-                if (pre is not None and self.fuse_gn_bwd > 0 and cin >= self.fuse_gn_bwd and int(node["pre_silu"]) <= 1
-                        and node.get("drop") is None):
-                    # the norm's backward reductions ride in this launch's epilogue where a tile lies in one sample
-                    tiles = int(L.rho_conv_stats_tiles(C.byref(d)))
-                    if tiles > 0:
-                        sbuf = pool.get((x1.shape[0] * tiles * 2 * cin,), torch.float32)
-                        d.stats = sbuf.data_ptr()
-                        d.gnb_x1, d.gnb_x2, d.gnb_c1 = ptr(x1), ptr(x2), c1
-                        d.gnb_a, d.gnb_b, d.gnb_silu = ptr(pre["a"]), ptr(pre["b"]), int(node["pre_silu"])
-                        fused = (sbuf, tiles)
-                self.keep.append(d)
-                self.fwd_descs.append(d)
-                emit(lambda s, d=d: L.rho_conv_nd_fwd(C.byref(d), s), "dgrad",
-                     flops=2.0 * (dact.numel() // cin) * cin * cw.cout * cw.taps, nbytes=float(esz) * (dY.numel() + dact.numel()))
-                if after_launch is not None:
-                    after_launch()                    # (the deferred weight gradient starts here, on the side stream)
-                if pre is not None:
-                    gn_backward(pre, node["pre_silu"], x1, x2, dact, fused, drop=node.get("drop"), skip=held_skips.pop(id(node), None))
-                    if fused is not None:
-                        pool.put(fused[0])
-                else:   # upsample: sum the 2x2 (1x2) children
-                    g1, acc1 = gradbuf(x1)
-                    a = (ptr(dact), ptr(g1), dtc, x1.shape[0] * x1.shape[1], x1.shape[2], x1.shape[3], x1.shape[4],
-                         int(node["up_hw"][0]), int(node["up_hw"][1]), int(acc1))
-                    emit(lambda s, a=a: L.rho_pool2x_sum(*a, s), "pool2x", nbytes=5.0 * esz * x1.numel())
-                    written.add(key(x1))
-                pool.put(dact)
-            elif node.get("s2") and self.s2_split_bwd:
-                # stride-2 conv: one launch per parity of dX (dx[2m] = w1 dy[m]; dx[2m+1] = w2 dy[m] + w0 dy[m+1]) instead of a 27-tap
-                # conv over a zero-stuffed dY (three of four multiply-adds on zeros)
-                g1, acc1 = gradbuf(x1)
-                for (a, b), wt in cw.ws2d:
-                    kern = (3, len(cw.S2_BWD[a]), len(cw.S2_BWD[b]))
-                    d = ops.make_conv_desc(dY, None, wt, cw.zero_bias, kernel=kern, cout=cin, split=cin, y=g1, y2=None,
-                                           res=g1 if acc1 else None, phase_hw=(a + 1, b + 1))
-                    self.keep.append(d)
-                    self.fwd_descs.append(d)
-                    emit(lambda s, d=d: L.rho_conv_nd_fwd(C.byref(d), s), "dgrad",
-                         flops=2.0 * (dY.numel() // dyw) * cin * cw.cout * kern[0] * kern[1] * kern[2],
-                         nbytes=float(esz) * (dY.numel() + x1.numel() / 4 * (2 if acc1 else 1)))
-                written.add(key(x1))
-            else:
-                g1, acc1 = gradbuf(x1)
-                g2, acc2 = gradbuf(x2) if x2 is not None else (None, False)
-                st = node["stride_hw"]
-                zs = (int(st[0] == 2), int(st[1] == 2))
-                d = ops.make_conv_desc(dY, None, cw.wd, cw.zero_bias, split=c1, y=g1, y2=g2, y2_cl=x2 is not None,
-                                       res=g1 if acc1 else None, res2=g2 if (x2 is not None and acc2) else None,
-                                       zs_hw=zs, out_hw=(x1.shape[2], x1.shape[3]) if zs != (0, 0) else (0, 0), **common)
-                self.keep.append(d)
-                self.fwd_descs.append(d)
-                emit(lambda s, d=d: L.rho_conv_nd_fwd(C.byref(d), s), "dgrad",
-                     flops=2.0 * (x1.numel() // c1) * cin * cw.cout * cw.taps, nbytes=float(esz) * (dY.numel() + x1.numel()))
-                written.add(key(x1))
-                if x2 is not None:
-                    written.add(key(x2))
-
-        # ---- head: dpred [N, Cout, S] float32 -> channels-last, as wide as the dgrad weights expect
-        self.dpred_in = torch.empty(tuple(self.out.shape), dtype=torch.float32, device=dev)
-        head = self.nodes[-1]
-
-        def im2col_of(src_f32: Tensor, dims4):
-            """[N, 1, D, H, W] float32 -> channels-last [N, D, H, W, 32] (27 taps + zero pad), the K = 32 operand of the GEMM forms."""
-            N_, D_, H_, W_ = dims4
-            im = pool.get((N_, D_, H_, W_, 32), dt)
-            a_ = (ptr(src_f32), ptr(im), dtc, N_, 1, D_, H_, W_, 3, 3, 3, 32)
-            emit(lambda s, a=a_: L.rho_im2col_taps(*a, s), "pack", nbytes=4.0 * src_f32.numel() + float(esz) * im.numel())
-            return im
-
-        def gemm_wgrad(x_t: Tensor, dy_t: Tensor, rows: int):
-            """dw[rows][cin] (+ channel sums of dy_t) = sum_pos dy_t[pos][:rows] x_t[pos][:] on the GEMM-shaped k_wgrad1; returns the
-            arena offsets (weights, channel sums)."""
-            cin_ = x_t.shape[-1]
-            dummy_w = torch.empty(1, rows, cin_, dtype=dt, device=dev)
-            dummy_b = torch.zeros(rows, dtype=torch.float32, device=dev)
-            self.keep.extend([dummy_w, dummy_b])
-            d = ops.make_conv_desc(x_t, None, dummy_w, dummy_b, kernel=(1, 1, 1), cout=rows, split=rows, y=dy_t, y2=None)
-            self.keep.append(d)
-            self.wgrad_descs.append((d, dy_t.shape[-1]))
-            off_w, off_b = region(rows * cin_), region(max(rows, dy_t.shape[-1]))
-            npos_ = x_t.numel() // cin_
-            emit(wgrad_call(d, ptr(dy_t), dy_t.shape[-1], aptr(off_w), aptr(off_b)), "wgrad", flops=2.0 * npos_ * 27 * max(rows, cin_),
-                 nbytes=float(esz) * (x_t.numel() + dy_t.numel()), cin=cin_, cout=rows, taps=1, positions=npos_)
-            return off_w, off_b
-
-        if head["k"] == "head_direct":
-            # one-output-channel head conv (unet_v2.py:679-683): data gradient = rho_stem_conv3d on dpred with mirrored taps; weight
-            # gradient = GEMM of the kept activated input against the im2col of dpred (rows = taps, mirrored back by finalize kind 2);
-            # bias gradient = the im2col's centre column sum (tap 13 never touches the padding) = sum of dpred
-            hcw = head["cw"]
-            N, Do, Ho, Wo = head["out_dims"]
-            Ch = head["x"].shape[-1]
-            hdw = eng._head_dgrad(m.out[2])
-            dact = pool.get((N, Do, Ho, Wo, Ch), dt)
-            a = (ptr(self.dpred_in), ptr(hdw.w), ptr(hdw.zero_bias), ptr(dact), None, N, Do, Ho, Wo, Ch)
-            emit(lambda s, a=a: L.rho_stem_conv3d(*a, s), "dgrad", flops=2.0 * N * Do * Ho * Wo * Ch * 27,
-                 nbytes=4.0 * N * Do * Ho * Wo + float(esz) * dact.numel())
-            im = im2col_of(self.dpred_in, (N, Do, Ho, Wo))
-            off_w, off_b = gemm_wgrad(head["xact"], im, 32)
-            pool.put(im)
-            fin_add(kind=2, off=off_w, param=hcw.weight, rs=None, cout=1, cin=Ch, coutp=32, cinb=Ch, k=(3, 3, 3))   # (walks [ci][tap])
-            fin_add(kind=0, off=off_b + 13, param=hcw.bias_param, rs=None, cout=1, cin=1, coutp=1, cinb=1, k=(1, 1, 1))
-            fin["params"] += [hcw.weight, hcw.bias_param]
-            fin["bytes"] += 4 * hcw.weight.numel()
-            gn_backward(head["pre"], eng.act, head["x"], None, dact)
-            pool.put(dact)
-            self.bwd_marks.append((len(bw), [head["pre"]["norm"].weight, head["pre"]["norm"].bias]))
-        else:
-            hw = head["cw"].wd.shape[2]
-            N, Do, Ho, Wo = head["out_dims"]
-            dhead = pool.get((N, Do, Ho, Wo, hw), dt)
-            a = (ptr(self.dpred_in), ptr(dhead), dtc, N, head["cw"].cout, Do * Ho * Wo, hw)
-            emit(lambda s, a=a: L.rho_pack_input(*a, s), "pack")
-            G[key(head["y2"])] = dhead
-            written.add(key(head["y2"]))
-
-        rs_hw = (1, 1) if eng.dims >= 2 else (0, 1)
-        # 1x1x1 skip-conv nodes whose block input also feeds a normalised conv (the block's in-conv, an earlier node): id(skip node) ->
-        # id(in-conv node).  Their data gradient is held until that node's GroupNorm backward (fuse_skip_dgrad)
-        if self.fuse_skip_dgrad:
-            for i, nd in enumerate(self.nodes):
-                if (nd["k"] == "conv" and nd["cw"].taps == 1 and nd["pre"] is None and not nd["stem"] and nd["up_hw"] == (0, 0)
-                        and tuple(nd["stride_hw"]) == (1, 1) and nd["res"] is None and not nd.get("phased") and not nd.get("s2")):
-                    for pj in range(i - 1, -1, -1):
-                        pn = self.nodes[pj]
-                        if (pn["k"] == "conv" and pn["pre"] is not None and pn["x1"] is nd["x1"] and pn["x2"] is nd["x2"]
-                                and pn["up_hw"] == (0, 0) and not pn["stem"]):
-                            skip_partner[id(nd)] = id(pn)
-                            break
-        for node in reversed(self.nodes):
-            if node["k"] == "head_direct":
-                continue                                       # (handled above)
-            if node["k"] == "stem_direct":
-                # one-input-channel stem conv (unet_v2.py:535): weight gradient = GEMM of the im2col of the input against dY
-                # (dw[co][tap], the parameter's own layout), bias gradient = channel sums of dY; no data gradient
-                flush_add(key(node["y"]))
-                dY = G.pop(key(node["y"]), None)
-                if dY is None:
-                    raise hip.RhoHipError("internal: missing gradient of the stem output in the backward plan")
-                scw = node["cw"]
-                im = im2col_of(self.x_in, node["out_dims"])
-                off_w, off_b = gemm_wgrad(im, dY, scw.cout)
-                pool.put(im)
-                pool.put(dY)
-                fin_add(kind=0, off=off_w, param=scw.weight, rs=None, cout=scw.cout, cin=27, coutp=scw.cout, cinb=32, k=(1, 1, 1))
-                fin_add(kind=0, off=off_b, param=scw.bias_param, rs=None, cout=scw.cout, cin=1, coutp=dY.shape[-1], cinb=1, k=(1, 1, 1))
-                fin["params"] += [scw.weight, scw.bias_param]
-                fin["bytes"] += 4 * scw.weight.numel()
-                fin_close()
-                continue
-            if node["k"] == "resample":
-                # y = avgpool / nearest-upsample(x): the transposed map into the gradient of x (accumulating if x has other consumers)
-                flush_add(key(node["y"]))
-                dy = G.pop(key(node["y"]), None)
-                if dy is None:
-                    raise hip.RhoHipError("internal: missing gradient of a resampled tensor in the backward plan")
-                xt = node["x"]
-                gx, accx = gradbuf(xt)
-                a = (ptr(dy), ptr(gx), dtc, xt.shape[0] * xt.shape[1], xt.shape[2], xt.shape[3], xt.shape[4], rs_hw[0], rs_hw[1], int(accx))
-                if node["mode"] == "up":
-                    emit(lambda s, a=a: L.rho_pool2x_sum(*a, s), "pool2x", nbytes=5.0 * esz * xt.numel())
-                else:
-                    emit(lambda s, a=a: L.rho_avgpool2x_bwd(*a, s), "avgpool_bwd", nbytes=3.0 * esz * xt.numel())
-                written.add(key(xt))
-                pool.put(dy)
-                continue
-            if node["k"] == "act":
-                flush_add(key(node["y"]))
-                dact = G.pop(key(node["y"]), None)
-                if dact is None:
-                    raise hip.RhoHipError("internal: missing gradient of a materialised activation in the backward plan")
-                gn_backward(node["pre"], node["pre_silu"], node["x1"], node["x2"], dact)
-                pool.put(dact)
-                pre = node["pre"]
-                self.bwd_marks.append((len(bw), [pre["norm"].weight, pre["norm"].bias]))
-                continue
-            if node["k"] == "attn":
-                flush_add(key(node["ao"]))
-                dao = G.get(key(node["ao"]))
-                N, T, Cc = node["N"], node["T"], node["C"]
-                dqkv = pool.get(tuple(node["qk"].shape[:4]) + (3 * Cc,), dt)   # = dY of the qkv projection
-                delta = pool.get((N, node["heads"], T), torch.float32)
-                a = (ptr(node["qk"]), ptr(node["vt"]), ptr(node["ao"]), ptr(dao), ptr(node["lse"]), ptr(delta), dqkv.data_ptr(), 3 * Cc,
-                     dqkv.data_ptr() + 2 * Cc * esz, 3 * Cc, dtc, N, T, node["heads"], Cc // node["heads"])
-                emit(lambda s, a=a: L.rho_attention_bwd(*a, s), "attention_bwd", flops=14.0 * N * T * T * Cc)
-                G[key(node["qk"])] = dqkv
-                written.add(key(node["qk"]))
-                pool.put(delta)
-                pool.put(G.pop(key(node["ao"])))
-                continue
-            cw = node["cw"]
-            out_t = node["y"] if node["y"] is not None else node["y2"]
-            flush_add(key(out_t))
-            dY = G.get(key(out_t))
-            if dY is None:
-                raise hip.RhoHipError("internal: missing output gradient in backward plan")
-            dyw = dY.shape[-1]
-            held_for_add = False
-            # residual input of the epilogue: alias (first contribution) or accumulate
-            if node["res"] is not None:
-                rk = key(node["res"])
-                if rk not in G:
-                    G[rk] = dY
-                    written.add(rk)
-                elif fold_add and rk not in pending_add and G[rk].shape == dY.shape:
-                    pending_add[rk] = dY                       # joins G[rk] in the next apply pass that accumulates into it
-                    held_for_add = True
-                else:
-                    flush_add(rk)
-                    a = (ptr(G[rk]), ptr(dY), dtc, dY.numel())
-                    emit(lambda s, a=a: L.rho_add_inplace(*a, s), "add", nbytes=3.0 * esz * dY.numel())
-            # (normalised convs: the weight gradient runs beside the GroupNorm backward passes, see `overlap` above)
-            ov = overlap and node["pre"] is not None and not node["stem"] and node["up_hw"] == (0, 0)
-            defer["on"] = ov
-            bias_and_wgrad(node, dY, dyw)
-            defer["on"] = False
-            held_skip = False
-            if not node["stem"]:
-                held_skip = bool(dgrad(node, dY, dyw, after_launch=flush_side if ov else None))
-            if ov:
-                if defer["ops"]:
-                    raise hip.RhoHipError("internal: deferred weight-gradient launches were never issued (backward plan)")
-                join_side()
-            # the output gradient is dead now unless a residual aliased it
-            aliased = node["res"] is not None and G.get(key(node["res"])) is dY
-            G.pop(key(out_t), None)
-            if not aliased and not held_for_add and not held_skip:
-                pool.put(dY)
-            ps = [] if use_arena else [cw.weight, cw.bias_param]      # (arena: reported with their finalize batch)
-            if node["pre"] is not None:
-                ps += [node["pre"]["norm"].weight, node["pre"]["norm"].bias]
-            if ps:
-                self.bwd_marks.append((len(bw), ps))
-            if use_arena:
-                fin_close()
-
-        if pending_add:
-            raise hip.RhoHipError("internal: a residual gradient was never added (backward plan)")
-        if held_skips:
-            raise hip.RhoHipError("internal: a held skip data gradient was never launched (backward plan)")
-        if use_arena:
-            fin_close(force=True)
-            arena["t"] = torch.empty(max(arena["floats"], 64), dtype=torch.float32, device=dev)
-            arena_memset_info["bytes"] = 4.0 * arena["t"].numel()
-            self.arena_bytes = 4 * arena["t"].numel()           # (a fixed cost of the model's size, whatever the plan keeps of activations)
-            pool.all.append(arena["t"])
-        # ---- embedding path (needs the FiLM gradients of every block)
-        e = 4 * eng.mc
-        first = True
-        emb_params: List[nn.Parameter] = []
-        for blk in eng._film_blocks:
-            lin = blk.emb_layers[1]
-            off = eng._film_off[id(blk)]
-            O = lin.weight.shape[0]
-            dptr = self.dfilm.data_ptr() + 4 * off
-            emit(lambda s, lin=lin, dptr=dptr, O=O, first=first: L.rho_linear_bwd(
-                dptr, film_stride, ptr(self.emb), ptr(lin.weight), pgrad(lin.weight), pgrad(lin.bias), ptr(self.demb), B, e, O, eng.act, 1,
-                0 if first else 1, s), "linear_bwd", flops=4.0 * B * e * O)
-            first = False
-            emb_params += [lin.weight, lin.bias]
-        te0, te2 = m.time_embed[0], m.time_embed[2]
-        emit(lambda s: L.rho_linear_bwd(ptr(self.demb), 0, ptr(self.emb_h), ptr(te2.weight), pgrad(te2.weight), pgrad(te2.bias),
-                                        ptr(self.demb_h), B, e, e, eng.act, 1, 0, s), "linear_bwd")
-        emit(lambda s: L.rho_linear_bwd(ptr(self.demb_h), 0, ptr(self.sin_in), ptr(te0.weight), pgrad(te0.weight), pgrad(te0.bias),
-                                        None, B, eng.mc, e, 0, 1, 0, s), "linear_bwd")
-        emb_params += [te2.weight, te2.bias, te0.weight, te0.bias]
-        self.bwd_marks.append((len(bw), emb_params))
-        if self.deterministic and det_ws["bytes"] > 0:
-            det_ws["t"] = torch.empty((det_ws["bytes"] + 3) // 4, dtype=torch.float32, device=dev)
-            pool.all.append(det_ws["t"])
-        self.pool_bytes = sum(t.numel() * t.element_size() for t in pool.all)
 
     def nbytes(self) -> int:
         """Device bytes this plan owns (forward buffers kept for its lifetime + the backward pool)."""
@@ -1843,7 +1100,6 @@ class _Plan:
         s = hip.stream()
         lst, infos = (self.bwd, self.bwd_info) if backward else (self.ops, self.info)
         tot = [0.0] * len(lst)
-        ov_was, self._overlap_on = getattr(self, "_overlap_on", False), False       # every launch on the timed stream, in order
         for _ in range(repeats):
             evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in lst]
             for op, (e0, e1) in zip(lst, evs):
@@ -1855,5 +1111,4 @@ class _Plan:
             torch.cuda.synchronize()
             for i, (e0, e1) in enumerate(evs):
                 tot[i] += e0.elapsed_time(e1)
-        self._overlap_on = ov_was
         return [dict(info, ms=tot[i] / repeats) for i, info in enumerate(infos)]

@@ -2,7 +2,7 @@
 # AB_VAR=<name> AB_ON=<value> AB_OFF=<value> AB_MODE=<train|sample> [AB_ARGS="--config c1"] bash tests/gpu_ab_env2.sh
 OUT=${RHO_RUN_OUT:-runs}      # logs and profiles (git-ignored)
 mkdir -p $OUT
-VAR=${AB_VAR:-RHO_DW_ARENA}; MODE=${AB_MODE:-train}
+VAR=${AB_VAR:-RHO_FUSE_SKIP_DGRAD}; MODE=${AB_MODE:-train}
 for tag in on off on2 off2; do
   F=${AB_ON:-1}; if [ "$tag" = "off" ] || [ "$tag" = "off2" ]; then F=${AB_OFF:-0}; fi
   env $VAR=$F timeout -k 10 400 python bench.py --full --mode $MODE --steps 6 --warmup 2 --train-steps 6 --no-cpu-baseline --no-checkpoint-leg ${AB_ARGS:-} > $OUT/abenv2_$tag.log 2>&1

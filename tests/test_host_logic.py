@@ -213,3 +213,26 @@ def test_prep_and_finalize_table_records_match_the_header_structs():
     from rho_diffusion_amd import hip
     assert C.sizeof(hip.PrepOp) == 128 and hip.PrepOp.total.offset == 56 and hip.PrepOp.kind.offset == 64 and hip.PrepOp.blk0.offset == 116
     assert C.sizeof(hip.WfinOp) == 104 and hip.WfinOp.phase_stride.offset == 64 and hip.WfinOp.kind.offset == 72 and hip.WfinOp.blk0.offset == 96
+
+
+def test_plan_key_lists_exactly_the_switches_the_engine_reads():
+    """UNetEngine._PLAN_ENV is the part of the plan key that follows the A/B switches (tests/test_gpu_round4.py:
+    test_plan_key_follows_use_checkpoint_and_switches): every RHO_* name the plan modules pass to os.environ.get must be in it, or
+    flipping that switch would replay a plan built under the old value; and every name in it must still be read by the engine, or
+    the key carries a switch that no longer exists."""
+    import pathlib
+    import re
+    from rho_diffusion_amd.engine import unet_engine
+    from rho_diffusion_amd.engine.unet_engine import UNetEngine
+    read = re.compile(r"os\.environ\.get\(\s*[\"'](RHO_[A-Z0-9_]+)[\"']")
+    eng_dir = pathlib.Path(unet_engine.__file__).parent
+    in_plan = set()
+    for name in ("unet_engine.py", "backward_plan.py"):
+        in_plan |= set(read.findall((eng_dir / name).read_text()))
+    assert in_plan, "the pattern no longer finds the engine's environment reads"
+    assert in_plan <= set(UNetEngine._PLAN_ENV), sorted(in_plan - set(UNetEngine._PLAN_ENV))
+    in_engine = set()
+    for f in eng_dir.glob("*.py"):
+        in_engine |= set(read.findall(f.read_text()))
+    assert set(UNetEngine._PLAN_ENV) <= in_engine, sorted(set(UNetEngine._PLAN_ENV) - in_engine)
+    assert len(set(UNetEngine._PLAN_ENV)) == len(UNetEngine._PLAN_ENV)
