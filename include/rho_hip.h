@@ -810,6 +810,64 @@ int rho_groupnorm_act_bwd(const void* x, const void* dy, const float* stats, con
                           float* dgamma, float* dbeta, int dtype, int64_t n, int64_t s, int64_t c, int64_t groups, int act,
                           void* stream);
 
+/* ------------------------------------------------------------------ VisionTransformer (rho_diffusion/models/vit.py:32-372)
+ * Token rows [B, N, E] row-major are the engine's channels-last layout with N positions and E channels: every nn.Linear over tokens
+ * runs as a 1x1x1 rho_conv_nd_fwd (+ rho_conv_nd_wgrad and the data-gradient form), the attention on rho_attention_fwd / _bwd.
+ * What those do not cover is below (csrc/vit.hip); all of it is HBM-bound, float32 statistics, no atomics, fixed summation orders. */
+
+/* nn.LayerNorm(embed_dim), eps 1e-5 (vit.py:145-146 norm_1 / norm_2, applied at :178 and :182), with the broadcast add of the time
+ * embedding (vit.py:175-176) fused into the load:
+ *     y[r, :] = LN(x[r, :] + add[r / rows_per_sample, :]) * gamma + beta
+ * x, y: `dtype` [rows, e]; add: float32 [rows / rows_per_sample, e] or NULL (rows_per_sample is then ignored); gamma, beta float32 [e];
+ * stats: float32 [rows, 2] = (mean, rstd) for the backward.  e % 32 == 0, 32 <= e <= rho_layernorm_max_dim() (2048), any rows >= 1.
+ * A fixed fraction of a wave (4 .. 64 lanes) holds a row in registers; mean, then the centred sum of squares (two passes over the
+ * registers, float32). */
+int64_t rho_layernorm_max_dim(void);
+int rho_layernorm_fwd(const void* x, const float* add, const float* gamma, const float* beta, void* y, float* stats, int dtype,
+                      int64_t rows, int64_t rows_per_sample, int64_t e, void* stream);
+
+/* Its backward (autograd of nn.LayerNorm at vit.py:178,182 and of the add at :176), from x, add and the saved stats:
+ *     dx[r, :] (+)= rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma         (acc_dx: added to what dx holds - the
+ *                                                                                           residual streams of vit.py:181,184)
+ *     dadd[b, :]  = sum over the rows of sample b of the dx computed here (the time embedding's gradient; NULL: not wanted)
+ *     dgamma (+)= sum_r dy * xhat,  dbeta (+)= sum_r dy                                    (acc_params: added, e.g. into p.grad)
+ * The reductions over rows run as per-block partials in `workspace` (rho_layernorm_bwd_workspace_bytes) and a finalize pass that adds
+ * them in block order: two runs give the same bits. */
+int64_t rho_layernorm_bwd_workspace_bytes(int64_t rows, int64_t rows_per_sample, int64_t e, int dtype, int has_add);
+int rho_layernorm_bwd(const void* dy, const void* x, const float* add, const float* stats, const float* gamma, void* dx, int acc_dx,
+                      float* dadd, float* dgamma, float* dbeta, int acc_params, void* workspace, int64_t workspace_bytes, int dtype,
+                      int64_t rows, int64_t rows_per_sample, int64_t e, void* stream);
+
+/* Patch gather (the operand of PatchEmbedding.conv_shaper, a kernel = stride = p convolution, vit.py:73-78,123-129):
+ *     tokens[b, n, k] = x[b, c, g0 p + i0, g1 p + i1, g2 p + i2]    x float32 [B, C, s0, s1, s2] (missing leading axes: extent 1)
+ * with n = (g0 G1 + g1) G2 + g2 the "(h w d)" order of vit.py:99-107 and k = ((c p + i0) p + i1) p + i2, i.e. the column order of
+ * conv_shaper.weight.reshape(E, K); columns K .. kp - 1 are zero (kp % 32 == 0, what the GEMM reads).  tokens: `dtype` [B, N, kp].
+ * Also the backward of rho_unpatchify; dbias (optional, float32 [C]) then receives (acc_dbias: is added) the per-channel sums of x =
+ * the bias gradient of output_conv (vit.py:282-288): up to 256 block partials per channel in dbias_ws (scratch of
+ * rho_patchify_dbias_workspace_bytes(C) bytes, required with dbias) and a second launch that adds them in block order. */
+int64_t rho_patchify_dbias_workspace_bytes(int64_t c);
+int rho_patchify(const float* x, void* tokens, int dtype, int64_t batch, int64_t c, int dims, int64_t s0, int64_t s1, int64_t s2,
+                 int64_t p, int64_t kp, float* dbias, int acc_dbias, float* dbias_ws, void* stream);
+
+/* The inverse scatter [B, N, kp] -> float32 [B, C, s0, s1, s2] (+ bias[c], optional): the second half of output_conv, a ConvTranspose
+ * with kernel = stride = p (vit.py:282-288,365-371), which is a GEMM over the token rows followed by this.  Also the backward of
+ * rho_patchify (bias NULL). */
+int rho_unpatchify(const void* tokens, const float* bias, float* out, int dtype, int64_t batch, int64_t c, int dims, int64_t s0, int64_t s1,
+                   int64_t s2, int64_t p, int64_t kp, void* stream);
+
+/* y = act(x + bias[c]) over `dtype` rows [rows, cols] (cols % 8 == 0) for all six activation codes (see rho_timestep_embed), and
+ * dx = dy * act'(x + bias[c]): the activation between the two MLP linears (vit.py:157-164) and behind the time / position transforms
+ * (vit.py:167-171,291-295).  bias (float32 [cols]) is optional; the model passes NULL, because its linears run as rho_conv_nd_fwd /
+ * rho_linear launches whose epilogue has already added the bias - the argument serves a caller whose GEMM has no bias epilogue. */
+int rho_bias_act(const void* x, const float* bias, void* y, int dtype, int64_t rows, int64_t cols, int act, void* stream);
+int rho_bias_act_bwd(const void* x, const float* bias, const void* dy, void* dx, int dtype, int64_t rows, int64_t cols, int act,
+                     void* stream);
+
+/* x[b, :] += pos over `dtype` [batch, m] with pos float32 [m] (embedded_patches.add_(pos_embedding), vit.py:351-353; m = N * E), and
+ * its gradient dpos[j] = sum_b dx[b, j] (b ascending). */
+int rho_pos_add(void* x, const float* pos, int dtype, int64_t batch, int64_t m, void* stream);
+int rho_pos_add_bwd(const void* dx, float* dpos, int dtype, int64_t batch, int64_t m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1162,3 +1162,148 @@ def attention_bwd(qk: Tensor, vt: Tensor, o: Tensor, dout: Tensor, lse: Tensor, 
                                       dqkv.data_ptr() + 2 * Cc * esz, 3 * Cc, dtype_code(qk.dtype), B, T, heads, Cc // heads,
                                       stream()), "rho_attention_bwd")
     return dqkv
+
+
+# ----------------------------------------------------------------------------- VisionTransformer (csrc/vit.hip)
+def vit_kpad(k: int) -> int:
+    """Row width of the patch tokens: K = C * p^dims padded to the multiple of 32 the GEMM reads and writes."""
+    return ((int(k) + 31) // 32) * 32
+
+
+def _rows2d(x: Tensor, name: str):
+    hip.require_gpu(x, name)
+    if x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous() or x.dim() < 2:
+        raise RhoHipError(f"{name} must be a contiguous float32 / bfloat16 [..., E] GPU tensor, got {x.dtype} {tuple(x.shape)}")
+    return x.numel() // x.shape[-1], x.shape[-1]
+
+
+def layernorm(x: Tensor, gamma: Tensor, beta: Tensor, add: Optional[Tensor] = None, out: Optional[Tensor] = None,
+              stats: Optional[Tensor] = None):
+    """(y, stats) = LayerNorm(x + add[sample]) * gamma + beta over the last axis of token rows x [B, N, E] (or [R, E]); ``add`` float32
+    [B, E] with B dividing the row count; stats float32 [R, 2] = (mean, rstd) (rho_layernorm_fwd)."""
+    R, E = _rows2d(x, "x")
+    _f32c(gamma, "gamma"), _f32c(beta, "beta")
+    rps = R
+    if add is not None:
+        _f32c(add, "add")
+        if add.dim() != 2 or add.shape[1] != E or R % add.shape[0]:
+            raise RhoHipError(f"add must be float32 [B, {E}] with B dividing {R} rows, got {tuple(add.shape)}")
+        rps = R // add.shape[0]
+    if gamma.numel() != E or beta.numel() != E:
+        raise RhoHipError(f"gamma / beta must have {E} elements")
+    out = torch.empty_like(x) if out is None else out
+    stats = torch.empty(R, 2, dtype=torch.float32, device=x.device) if stats is None else stats
+    check(hip.lib().rho_layernorm_fwd(ptr(x), ptr(add), ptr(gamma), ptr(beta), ptr(out), ptr(stats), dtype_code(x.dtype), R, rps, E, stream()),
+          "rho_layernorm_fwd")
+    return out, stats
+
+
+def layernorm_bwd(dy: Tensor, x: Tensor, stats: Tensor, gamma: Tensor, dgamma: Tensor, dbeta: Tensor, add: Optional[Tensor] = None,
+                  dx: Optional[Tensor] = None, dadd: Optional[Tensor] = None, acc_dx: bool = False, acc_params: bool = False,
+                  workspace: Optional[Tensor] = None):
+    """Backward of ``layernorm``: returns (dx, dadd); dgamma / dbeta float32 [E] are written (acc_params: added to).  dx may be given
+    (acc_dx: the result is added to it); dadd float32 [B, E] is produced when ``add`` is given (rho_layernorm_bwd)."""
+    R, E = _rows2d(x, "x")
+    if dy.shape != x.shape or dy.dtype != x.dtype or not dy.is_contiguous():
+        raise RhoHipError("dy must match x in shape, dtype and be contiguous")
+    _f32c(stats, "stats"), _f32c(gamma, "gamma"), _f32c(dgamma, "dgamma"), _f32c(dbeta, "dbeta")
+    rps = R
+    if add is not None:
+        _f32c(add, "add")
+        if add.dim() != 2 or add.shape[1] != E or R % add.shape[0]:
+            raise RhoHipError(f"add must be float32 [B, {E}] with B dividing {R} rows, got {tuple(add.shape)}")
+        rps = R // add.shape[0]
+        dadd = torch.empty_like(add) if dadd is None else _f32c(dadd, "dadd")
+    if dx is None:
+        if acc_dx:
+            raise RhoHipError("acc_dx needs the buffer to accumulate into")
+        dx = torch.empty_like(x)
+    need = int(hip.lib().rho_layernorm_bwd_workspace_bytes(R, rps, E, dtype_code(x.dtype), int(add is not None)))
+    if need <= 0:
+        raise RhoHipError(f"layernorm_bwd: unsupported shape rows={R} E={E}")
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    check(hip.lib().rho_layernorm_bwd(ptr(dy), ptr(x), ptr(add), ptr(stats), ptr(gamma), ptr(dx), int(acc_dx), ptr(dadd), ptr(dgamma),
+                                      ptr(dbeta), int(acc_params), ptr(workspace), workspace.numel() * workspace.element_size(),
+                                      dtype_code(x.dtype), R, rps, E, stream()), "rho_layernorm_bwd")
+    return dx, dadd
+
+
+def _patch_args(shape, p: int):
+    B, Cc = int(shape[0]), int(shape[1])
+    sp = [int(v) for v in shape[2:]]
+    dims = len(sp)
+    if not 1 <= dims <= 3:
+        raise RhoHipError(f"patch kernels take 1-D / 2-D / 3-D data, got shape {tuple(shape)}")
+    if any(s % p for s in sp):
+        raise RhoHipError(f"spatial shape {sp} is not divisible by patch_size {p}")
+    s3 = [1] * (3 - dims) + sp
+    N = int(math.prod(s // p for s in sp))
+    return B, Cc, dims, s3, N, Cc * p ** dims
+
+
+def patchify(x: Tensor, p: int, dtype: torch.dtype, out: Optional[Tensor] = None, dbias: Optional[Tensor] = None,
+             acc_dbias: bool = False) -> Tensor:
+    """float32 [B, C, *spatial] -> tokens [B, N, Kp] in ``dtype`` (rho_patchify); ``dbias`` float32 [C] receives the channel sums."""
+    _f32c(x, "x")
+    B, Cc, dims, s3, N, K = _patch_args(x.shape, p)
+    kp = vit_kpad(K)
+    out = torch.empty(B, N, kp, dtype=dtype, device=x.device) if out is None else out
+    ws = None
+    if dbias is not None:
+        if _f32c(dbias, "dbias").numel() != Cc:
+            raise RhoHipError(f"dbias must be float32 [{Cc}]")
+        ws = torch.empty(int(hip.lib().rho_patchify_dbias_workspace_bytes(Cc)) // 4, dtype=torch.float32, device=x.device)
+    check(hip.lib().rho_patchify(ptr(x), ptr(out), dtype_code(dtype), B, Cc, dims, s3[0], s3[1], s3[2], int(p), kp, ptr(dbias),
+                                 int(acc_dbias), ptr(ws), stream()), "rho_patchify")
+    return out
+
+
+def unpatchify(tokens: Tensor, shape, p: int, bias: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """tokens [B, N, Kp] -> float32 ``shape`` = [B, C, *spatial] (+ bias[c]) (rho_unpatchify)."""
+    hip.require_gpu(tokens, "tokens")
+    B, Cc, dims, s3, N, K = _patch_args(shape, p)
+    kp = vit_kpad(K)
+    if tuple(tokens.shape) != (B, N, kp) or not tokens.is_contiguous():
+        raise RhoHipError(f"tokens must be contiguous [{B}, {N}, {kp}], got {tuple(tokens.shape)}")
+    if bias is not None and _f32c(bias, "bias").numel() != Cc:
+        raise RhoHipError(f"bias must be float32 [{Cc}]")
+    out = torch.empty(tuple(int(v) for v in shape), dtype=torch.float32, device=tokens.device) if out is None else _f32c(out, "out")
+    check(hip.lib().rho_unpatchify(ptr(tokens), ptr(bias), ptr(out), dtype_code(tokens.dtype), B, Cc, dims, s3[0], s3[1], s3[2], int(p), kp,
+                                   stream()), "rho_unpatchify")
+    return out
+
+
+def bias_act(x: Tensor, act: int, bias: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """act(x + bias[c]) over the last axis (rho_bias_act); ``act``: an activation code (ACT_CODES)."""
+    R, Cc = _rows2d(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    check(hip.lib().rho_bias_act(ptr(x), ptr(bias), ptr(out), dtype_code(x.dtype), R, Cc, int(act), stream()), "rho_bias_act")
+    return out
+
+
+def bias_act_bwd(x: Tensor, dy: Tensor, act: int, bias: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """dy * act'(x + bias[c]) (rho_bias_act_bwd)."""
+    R, Cc = _rows2d(x, "x")
+    if dy.shape != x.shape or dy.dtype != x.dtype or not dy.is_contiguous():
+        raise RhoHipError("dy must match x in shape, dtype and be contiguous")
+    out = torch.empty_like(x) if out is None else out
+    check(hip.lib().rho_bias_act_bwd(ptr(x), ptr(bias), ptr(dy), ptr(out), dtype_code(x.dtype), R, Cc, int(act), stream()), "rho_bias_act_bwd")
+    return out
+
+
+def pos_add(x: Tensor, pos: Tensor) -> Tensor:
+    """x[b] += pos in place: x [B, N, E] in the engine dtype, pos float32 [N, E] (rho_pos_add)."""
+    _rows2d(x, "x"), _f32c(pos, "pos")
+    if pos.numel() * x.shape[0] != x.numel():
+        raise RhoHipError(f"pos {tuple(pos.shape)} does not match x {tuple(x.shape)}")
+    check(hip.lib().rho_pos_add(ptr(x), ptr(pos), dtype_code(x.dtype), x.shape[0], pos.numel(), stream()), "rho_pos_add")
+    return x
+
+
+def pos_add_bwd(dx: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """float32 [N, E] = sum over the batch of dx [B, N, E] (rho_pos_add_bwd)."""
+    _rows2d(dx, "dx")
+    out = torch.empty(tuple(dx.shape[1:]), dtype=torch.float32, device=dx.device) if out is None else _f32c(out, "out")
+    check(hip.lib().rho_pos_add_bwd(ptr(dx), ptr(out), dtype_code(dx.dtype), dx.shape[0], out.numel(), stream()), "rho_pos_add_bwd")
+    return out

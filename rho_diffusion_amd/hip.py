@@ -197,6 +197,21 @@ SIGNATURES = {
                                       c_int64, c_int64, c_int64, c_int, c_void_p]),
     "rho_attention_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                   c_int, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    # ---- VisionTransformer (models/vit.py, csrc/vit.hip)
+    "rho_layernorm_max_dim": (c_int64, []),
+    "rho_layernorm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p]),
+    "rho_layernorm_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int, c_int]),
+    "rho_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p]),
+    "rho_patchify_dbias_workspace_bytes": (c_int64, [c_int64]),
+    "rho_patchify": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                             c_int, c_void_p, c_void_p]),
+    "rho_unpatchify": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
+                               c_void_p]),
+    "rho_bias_act": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p]),
+    "rho_bias_act_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p]),
+    "rho_pos_add": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
+    "rho_pos_add_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
 }
 
 
