@@ -59,6 +59,7 @@ class BackwardBuilder:
     def __init__(self, plan):
         self.plan = plan
         self.eng = eng = plan.eng
+        self.sw = plan.sw
         self.L = plan.L
         self.dt = eng.dtype
         self.dtc = hip.dtype_code(eng.dtype)
@@ -198,7 +199,7 @@ class BackwardBuilder:
             a = (ptr(dY), dtc, N, S, dyw, ptr(part), dst, self.film_stride, 0, None, 0)
             self.emit(lambda s, a=a: L.rho_chan_sum(*a, s), "chan_sum", nbytes=float(esz) * N * S * dyw)
         pool.put(part)
-        if node.get("phased") and node["pre"] is None and node["x2"] is None and plan.phase_upsample_bwd:
+        if node.get("phased") and node["pre"] is None and node["x2"] is None and self.sw.phase_upsample_bwd:
             # Upsample + conv ran as sub-pixel phases: per phase a 2-tap weight gradient on the SOURCE tensor against that parity
             # of dY (12 / 27 of the multiply-adds, no upsampled copy), routed back to the 3-tap parameter gradient
             x1 = node["x1"]
@@ -357,7 +358,7 @@ class BackwardBuilder:
         if dyw != cw.wd.shape[2] or cw.wd.shape[1] != cin:
             raise hip.RhoHipError("internal: dgrad weight shape does not match the gradient tensors")
         common = dict(kernel=cw.kernel, cout=cin)
-        if node.get("phased") and pre is None and x2 is None and plan.phase_upsample_bwd:
+        if node.get("phased") and pre is None and x2 is None and self.sw.phase_upsample_bwd:
             # Upsample + conv ran as sub-pixel phases: each phase's share of dX is a 2-tap conv of that parity of dY with the
             # phase's flipped weights, accumulated in place - 12 / 27 of the multiply-adds, no full-resolution intermediate
             g1, acc1 = self.gradbuf(x1)
@@ -373,7 +374,7 @@ class BackwardBuilder:
             dact = pool.get(tshape, self.dt)       # gradient of the activated / upsampled tensor
             d = ops.make_conv_desc(dY, None, cw.wd, cw.zero_bias, split=cin, y=dact, y2=None, **common)
             fused = None
-            if (pre is not None and plan.fuse_gn_bwd > 0 and cin >= plan.fuse_gn_bwd and int(node["pre_silu"]) <= 1
+            if (pre is not None and self.sw.fuse_gn_bwd > 0 and cin >= self.sw.fuse_gn_bwd and int(node["pre_silu"]) <= 1
                     and node.get("drop") is None):
                 # the norm's backward reductions ride in this launch's epilogue where a tile lies in one sample
                 tiles = int(L.rho_conv_stats_tiles(C.byref(d)))
@@ -397,7 +398,7 @@ class BackwardBuilder:
                 self.emit(lambda s, a=a: L.rho_pool2x_sum(*a, s), "pool2x", nbytes=5.0 * esz * x1.numel())
                 written.add(key(x1))
             pool.put(dact)
-        elif node.get("s2") and plan.s2_split_bwd:
+        elif node.get("s2") and self.sw.s2_split_bwd:
             # stride-2 conv: one launch per parity of dX (dx[2m] = w1 dy[m]; dx[2m+1] = w2 dy[m] + w0 dy[m+1]) instead of a 27-tap
             # conv over a zero-stuffed dY (three of four multiply-adds on zeros)
             g1, acc1 = self.gradbuf(x1)
@@ -629,7 +630,7 @@ class BackwardBuilder:
             self.head_direct(head)
         else:
             self.head_packed(head)
-        if plan.fuse_skip_dgrad:
+        if self.sw.fuse_skip_dgrad:
             self.pair_skips()
         kinds = {"stem_direct": self.stem_direct, "resample": self.resample, "act": self.act, "attn": self.attn, "conv": self.conv}
         for node in reversed(plan.nodes):

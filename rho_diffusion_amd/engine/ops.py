@@ -1033,14 +1033,17 @@ def attention(qk: Tensor, vt: Tensor, heads: int, out: Optional[Tensor] = None, 
 # ============================================================================= backward ops
 def prep_conv_weight_dgrad(w: Tensor, dtype: torch.dtype, col_src: Optional[Tensor] = None,
                            out: Optional[Tensor] = None) -> Tensor:
-    """PyTorch conv weight [Cout, Cin, *k] -> dgrad weights [taps, ceil32(Cin), ceilCK(Cout)] (flipped, transposed)."""
+    """PyTorch conv weight [Cout, Cin, *k] -> dgrad weights [taps, ceil32(Cin), ceilCK(Cout)] (flipped, transposed); a given
+    ``out`` [taps, rows, cols] sets the padded extents."""
     _f32c(w, "w")
     cout, cin = w.shape[0], w.shape[1]
     taps = int(math.prod(w.shape[2:])) if w.dim() > 2 else 1
     ck = elem_chunk(dtype)
-    rowsp = ((cin + 31) // 32) * 32
-    colsp = ((cout + ck - 1) // ck) * ck
-    out = torch.empty(taps, rowsp, colsp, dtype=dtype, device=w.device) if out is None else out
+    if out is None:
+        out = torch.empty(taps, ((cin + 31) // 32) * 32, ((cout + ck - 1) // ck) * ck, dtype=dtype, device=w.device)
+    if out.shape[0] != taps or out.shape[1] < cin or out.shape[2] < cout or out.dtype != dtype or not out.is_contiguous():
+        raise RhoHipError(f"prep_conv_weight_dgrad: out {tuple(out.shape)} {out.dtype} does not hold [{taps}, >={cin}, >={cout}] {dtype}")
+    rowsp, colsp = out.shape[1], out.shape[2]
     check(hip.lib().rho_prep_conv_weight_dgrad(ptr(w), ptr(out), dtype_code(dtype), cout, cin, taps, rowsp, colsp, ptr(col_src),
                                                stream()), "rho_prep_conv_weight_dgrad")
     return out

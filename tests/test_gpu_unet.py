@@ -237,3 +237,70 @@ def test_stem_and_head_as_gemm_match_the_conv_form(monkeypatch):
                 outs.append(m(x.to(DEV), t.to(DEV)).float().cpu())
         assert rel_l2(outs[0], outs[1]) < 1e-2, case
         assert rel_l2(outs[0], torch.from_numpy(g4[f"{case}/pred"])) < 3e-2, case
+
+
+# ----------------------------------------------------------------------------- prepared weights and plan construction
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_conv_weight_layouts_batched_equals_eager(dtype):
+    """Every prepared layout of a conv (forward, padded bias, data gradient, sub-pixel phases, parity splits, and the data-gradient
+    forms of the last two) comes out bit-equal from the one-launch table (``prep_into`` + ``PrepTable.launch``) and from the
+    per-tensor calls (``refresh``) - ops.PrepTable promises "same arguments, same results".  cout = 40 and cin = 24 are ragged
+    against every padding (32 rows, 16 / 32-channel chunks).  ``row_src`` has one entry per PADDED row (ops.prep_conv_weight):
+    a permutation of the 40 rows, then valid rows again for the 24 padding rows."""
+    from rho_diffusion_amd.engine import ops
+    from rho_diffusion_amd.engine.unet_engine import _ConvW
+    weight = nn.Parameter(det_normal((40, 24, 3, 3, 3), "layouts_w").to(DEV))
+    bias = nn.Parameter(det_normal((40,), "layouts_b").to(DEV))
+    perm = [(7 * i + 3) % 40 for i in range(40)]
+    assert sorted(perm) == list(range(40))
+    row_src = torch.tensor(perm + perm[:24], dtype=torch.int32, device=DEV)
+    cw = _ConvW(weight, bias, dtype, row_src)
+    cw.enable_dgrad()
+    cw.enable_phases((1, 1), dgrad=True)
+    cw.enable_s2(dgrad=True)
+    bufs = {"w": cw.w, "b": cw.b, "wd": cw.wd}
+    for name in ("wph", "wphd", "ws2", "ws2d"):
+        lst = getattr(cw, name)
+        assert len(lst) == 4, name
+        bufs.update({f"{name}{key}": t for key, t in lst})
+
+    def sentinel():
+        for t in bufs.values():
+            t.fill_(7.0)
+
+    sentinel()
+    table = ops.PrepTable(weight.device)
+    assert cw.prep_into(table)
+    table.launch()
+    batched = {k: t.clone() for k, t in bufs.items()}
+    sentinel()
+    cw.refresh()
+    for k, t in bufs.items():
+        assert not bool((batched[k] == 7.0).all()), k
+        diff = float((t.float() - batched[k].float()).abs().max())
+        print(f"{k}: max |eager - batched| = {diff:.3e}")
+        assert torch.equal(t, batched[k]), (k, diff)
+
+
+@pytest.mark.parametrize("min_wgs", ["1", "0"])
+def test_plan_build_is_repeatable(min_wgs, monkeypatch):
+    """Building a training plan twice on one engine gives the same plan: the second build finds the phase / parity / data-gradient
+    layouts that the first one enabled on the shared conv weights.  RHO_PHASE_MIN_WGS = 1 is the smallest non-zero threshold;
+    at tiny3d's 512 positions the phase and parity forms themselves only run under the suite's own setting, 0, so that is built
+    too and must contain both."""
+    from rho_diffusion_amd.engine.unet_engine import _Plan
+    from rho_diffusion_amd.models import UNet
+    monkeypatch.setenv("RHO_PHASE_MIN_WGS", min_wgs)
+    kw, xshape, _ = UNET_CASES["tiny3d"]
+    model = UNet(**dict(kw, compute_dtype="bf16"))
+    model.load_state_dict(det_state_dict(model.state_dict(), "repeatable"))
+    eng = model.to(DEV).engine()
+    with torch.inference_mode(False), torch.no_grad():
+        first, second = _Plan(eng, tuple(xshape), False, True), _Plan(eng, tuple(xshape), False, True)
+    if min_wgs == "0":
+        assert any(n.get("phased") for n in first.nodes) and any(n.get("s2") for n in first.nodes)
+    assert first.info == second.info
+    assert first.bwd_info == second.bwd_info
+    assert first.variants() == second.variants()
+    assert first.nbytes() == second.nbytes()
+    assert [i for i, _ in first.bwd_marks] == [i for i, _ in second.bwd_marks]

@@ -197,7 +197,7 @@ def test_unetv2_refuses_dropout_and_unbuilt_activations_naming_the_reference_lin
 def test_head_dgrad_weight_layout_is_the_mirrored_taps_as_contraction_form():
     """engine._HeadDgradW (round 4): w[0][c][t] = weight[0][c][26 - t] for t < 27, zero beyond - what rho_stem_conv3d needs to compute
     the data gradient of the one-output-channel head conv from dpred (host-side index table, checked without a GPU)."""
-    from rho_diffusion_amd.engine.unet_engine import _HeadDgradW
+    from rho_diffusion_amd.engine.weights import _HeadDgradW
     w = torch.nn.Parameter(torch.arange(1 * 4 * 27, dtype=torch.float32).reshape(1, 4, 3, 3, 3))
     hd = _HeadDgradW(w, torch.float32)
     assert hd.w.shape == (1, 4, 32)
@@ -227,8 +227,9 @@ def test_plan_key_lists_exactly_the_switches_the_engine_reads():
     read = re.compile(r"os\.environ\.get\(\s*[\"'](RHO_[A-Z0-9_]+)[\"']")
     eng_dir = pathlib.Path(unet_engine.__file__).parent
     in_plan = set()
-    for name in ("unet_engine.py", "backward_plan.py"):
-        in_plan |= set(read.findall((eng_dir / name).read_text()))
+    for f in eng_dir.glob("*.py"):                  # every module of the plan: all of the engine but the tensor-level wrappers
+        if f.name != "ops.py":
+            in_plan |= set(read.findall(f.read_text()))
     assert in_plan, "the pattern no longer finds the engine's environment reads"
     assert in_plan <= set(UNetEngine._PLAN_ENV), sorted(in_plan - set(UNetEngine._PLAN_ENV))
     in_engine = set()
