@@ -282,7 +282,8 @@ typedef struct rho_conv_desc {
  * replaces conv_nd (layers.py:77-88) at every call site of unet_v2.py (ResBlock convs :215,
  * :241; skip 1x1 :256; Downsample :153-162; Upsample+conv :122-134; attention qkv / proj_out
  * :323,:331 with the residual of :342; stem :535; head :679-683) with the GroupNorm affine +
- * FiLM + SiLU (:212-216, :285-289) applied while the halo tile is staged. */
+ * FiLM + SiLU (:212-216, :285-289) applied while the halo tile is staged.  Wide bf16 1x1x1 launches without a prologue or a
+ * second input (the attention projections) run as a plain LDS-DMA GEMM, k_gemm1x1, instead (RHO_GEMM1X1=0: never). */
 int rho_conv_nd_fwd(const rho_conv_desc* desc, void* stream);
 
 /* Weights of one sub-pixel phase (see rho_conv_desc.ph_h): from the fp32 parameter [cout][cin][kd][kh][kw] (kh / kw = 3 on a

@@ -1321,6 +1321,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__
 }
 
 #include "conv32.h"
+#include "gemm1x1.h"
 
 // ------------------------------------------------------------------------------------------ host
 namespace {
@@ -1460,6 +1461,14 @@ static int conv_impl(const rho_conv_desc* dp, void* stream, int64_t* stats_tiles
         if (g_variant != nullptr) { snprintf(g_variant->buf, (size_t)g_variant->cap, "k_conv32<bf16>"); return 0; }
         if (d.stats && d.split != d.cout) return RHO_E_ARG;
         return launch_conv32(d, as_stream(stream));
+    }
+
+    // the wide bf16 1x1x1 convolutions without prologue (attention qkv / proj_out, un-folded skips): a plain GEMM (gemm1x1.h)
+    if (gemm1x1_applies(d)) {
+        if (stats_tiles) { *stats_tiles = gemm1x1_stats_tiles(d); return 0; }
+        if (ws_want) { *ws_want = 0; return 0; }
+        if (g_variant != nullptr) { snprintf(g_variant->buf, (size_t)g_variant->cap, "k_gemm1x1<bf16,256x%d>", G1_BN); return 0; }
+        return launch_gemm1x1(d, as_stream(stream));
     }
 
     // output extents per sample (padding k/2).  Zero-stuffed input (dgrad of a stride-2 conv): the

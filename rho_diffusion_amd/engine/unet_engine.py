@@ -48,7 +48,7 @@ Tensor = torch.Tensor
 
 
 PlanSwitches = namedtuple("PlanSwitches", "materialize_act materialize_min_cout phase_upsample phase_upsample_bwd phase_min_wgs fold_skip "
-                                     "s2_split s2_split_bwd fuse_gn_bwd gemm_ends direct_ends fuse_skip_dgrad")
+                                     "s2_split s2_split_bwd fuse_gn_bwd gemm_ends direct_ends fuse_skip_dgrad gemm1x1")
 
 
 class UNetEngine:
@@ -273,7 +273,7 @@ class UNetEngine:
     #  own RHO_CONV_SPLITK is latched at its first launch, so no rebuild could follow it and it is not part of the key)
     _PLAN_ENV = ("RHO_TRAIN_MATERIALIZE", "RHO_MATERIALIZE_MIN_COUT", "RHO_PHASE_UPSAMPLE", "RHO_PHASE_UPSAMPLE_BWD", "RHO_PHASE_MIN_WGS",
                  "RHO_FOLD_SKIP", "RHO_S2_SPLIT", "RHO_S2_SPLIT_BWD", "RHO_FUSE_GN_BWD", "RHO_GEMM_ENDS", "RHO_DIRECT_ENDS",
-                 "RHO_FUSE_SKIP_DGRAD")
+                 "RHO_FUSE_SKIP_DGRAD", "RHO_GEMM1X1")
 
     @staticmethod
     def _plan_switches() -> PlanSwitches:
@@ -296,7 +296,10 @@ class UNetEngine:
             # backward of a ResBlock with a 1x1x1 skip convolution: the skip's data gradient and the GroupNorm backward apply of the
             # in-conv path write the same dX - one launch (rho_conv_desc.gna_*) instead of a data-gradient launch plus an apply pass
             # that re-reads and re-writes it
-            fuse_skip_dgrad=os.environ.get("RHO_FUSE_SKIP_DGRAD", "1") != "0")
+            fuse_skip_dgrad=os.environ.get("RHO_FUSE_SKIP_DGRAD", "1") != "0",
+            # read by the library at every conv query and launch (gemm1x1.h: k_gemm1x1 for the wide bf16 1x1x1 convs, 0 = k_conv);
+            # recorded here so that a plan - its variant names and statistics rows - is rebuilt when the switch flips
+            gemm1x1=os.environ.get("RHO_GEMM1X1", "1") != "0")
 
     def _plan_signature(self) -> tuple:
         """Everything besides (shape, labels, mode) that is baked into a plan when it is built: the per-ResBlock ``use_checkpoint``
