@@ -102,6 +102,51 @@ int rho_get_deterministic(void);
 int rho_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
               float beta2, float eps, float weight_decay, int32_t step, void* stream);
 
+/* The other registry optimizers (rho_diffusion/registry.py:177-193) as ONE fused update over a flat float32 arena: the single-tensor
+ * paths of torch 2.10's torch/optim/{adam,adamw,sgd,rmsprop,adagrad,adamax,nadam,radam,adadelta}.py (_single_tensor_*), one launch
+ * instead of a dozen ATen calls per parameter.  p, g and the state arenas s0 / s1 / s2 are float32[n]; g is only read.
+ *   kind              hp[3..]                                   s0            s1            s2
+ *   RHO_OPT_ADAM      beta1, beta2                              exp_avg       exp_avg_sq    max_exp_avg_sq (AMSGRAD)
+ *   RHO_OPT_ADAMW     the same with decoupled weight decay
+ *   RHO_OPT_SGD       momentum, dampening                       momentum_buffer (momentum != 0; step 1 seeds it with the gradient)
+ *   RHO_OPT_RMSPROP   alpha, momentum                           square_avg    grad_avg (CENTERED)   momentum_buffer (momentum > 0)
+ *   RHO_OPT_ADAGRAD   lr_decay                                  sum
+ *   RHO_OPT_ADAMAX    beta1, beta2                              exp_avg       exp_inf
+ *   RHO_OPT_NADAM     beta1, beta2, momentum_decay, mu_product  exp_avg       exp_avg_sq
+ *   RHO_OPT_RADAM     beta1, beta2                              exp_avg       exp_avg_sq
+ *   RHO_OPT_ADADELTA  rho                                       square_avg    acc_delta
+ * hp: float32[8] on the HOST, read during the call: {lr, weight_decay, eps, then the kind's own as listed, rest ignored}.  NAdam's
+ * mu_product is the running product INCLUDING this step's mu (torch keeps it as a float32 scalar per parameter; the caller owns
+ * it).  step is 1-based; bias corrections, NAdam's mu / mu_next, RAdam's rho_t and rectification and Adagrad's clr are computed
+ * here in double and passed to the kernel by value.  flags: RHO_OPT_* bits; a slot the kind and its options do not use may be NULL
+ * and is not touched.  gscale (optional, float32[1] on the device): g is multiplied by gscale[0] as it is loaded - the clip
+ * coefficient of rho_clip_coef - and the gradient arena is not rewritten.  RHO_E_ARG: NULL p / g / hp / a needed slot, n <= 0,
+ * unknown kind or flag, step < 1. */
+#define RHO_OPT_ADAM 0
+#define RHO_OPT_ADAMW 1
+#define RHO_OPT_SGD 2
+#define RHO_OPT_RMSPROP 3
+#define RHO_OPT_ADAGRAD 4
+#define RHO_OPT_ADAMAX 5
+#define RHO_OPT_NADAM 6
+#define RHO_OPT_RADAM 7
+#define RHO_OPT_ADADELTA 8
+#define RHO_OPT_MAXIMIZE 1
+#define RHO_OPT_AMSGRAD 2
+#define RHO_OPT_DECOUPLED_WD 4
+#define RHO_OPT_NESTEROV 8
+#define RHO_OPT_CENTERED 16
+int rho_optim_step(int32_t kind, uint32_t flags, float* p, const float* g, float* s0, float* s1, float* s2, int64_t n,
+                   const float* hp, int32_t step, const float* gscale, void* stream);
+
+/* Global gradient norm for clipping (torch.nn.utils.clip_grad_norm_, called at rho_diffusion/diffusion/diffusers.py:134), without
+ * atomics or a host round trip.  rho_sumsq_partial writes rho_sumsq_blocks(n) per-workgroup sums of x[i]^2 to partials[0 ..) in a
+ * fixed order that does not depend on x's alignment; the caller lays the partials of all its arenas side by side.  rho_clip_coef
+ * (one workgroup) adds them in index order and writes out = {norm, coef = min(1, max_norm / (norm + 1e-6))} (float32[2], device). */
+int rho_sumsq_blocks(int64_t n);
+int rho_sumsq_partial(const float* x, int64_t n, float* partials, void* stream);
+int rho_clip_coef(const float* partials, int64_t n_partials, float max_norm, float* out, void* stream);
+
 /* ------------------------------------------------------------------ embeddings */
 
 /* Timestep embedding of UNet.forward (unet_v2.py:699-701): the interleaved sinusoid of models/common.py:27-43 for ANY integer

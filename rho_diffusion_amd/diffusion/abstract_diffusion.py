@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import math
 import types
-from inspect import getfullargspec
 from logging import getLogger
 from typing import Any, Mapping, Union
 
@@ -74,20 +73,14 @@ class AbstractDiffusionPipeline(_Base):
 
     def configure_optimizers(self, mpi_world_size: int = 1):
         """AdamW defaults merged with the configured kwargs; lr *= sqrt(world) (abstract_diffusion.py:86-148).
-        Unlike the reference the stored kwargs are not mutated."""
-        opt_kwargs = dict(self.hparams.opt_kwargs)
-        spec = getfullargspec(AdamW)
-        names = [a for a in spec.args if a not in ("self", "params")]
-        for key, value in zip(names, spec.defaults or ()):
-            opt_kwargs.setdefault(key, value)
-        opt_kwargs.pop("lr_schedule", None)
+        Unlike the reference the stored kwargs are not mutated, a merged-in AdamW default that the named
+        optimizer does not take is dropped instead of raising TypeError (``optimizer="SGD"`` has no ``betas``), and a registry
+        optimizer with a fused HIP counterpart (``optim.fused_optimizer_class``) is built as that."""
+        from ..optim import fused_optimizer_class, optimizer_kwargs
+        cls = fused_optimizer_class(self.optimizer) or self.optimizer
+        opt_kwargs = optimizer_kwargs(cls, dict(self.hparams.opt_kwargs))
         opt_kwargs["lr"] = opt_kwargs["lr"] * math.sqrt(mpi_world_size)
-        if self.optimizer is AdamW:
-            from ..optim import HipAdamW
-            opt = HipAdamW(self.parameters(), **{k: v for k, v in opt_kwargs.items()
-                                                 if k in ("lr", "betas", "eps", "weight_decay")})
-        else:
-            opt = self.optimizer(self.parameters(), **opt_kwargs)
+        opt = cls(self.parameters(), **opt_kwargs)
         return {"optimizer": opt}
 
     @property

@@ -408,6 +408,58 @@ def adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: float, b
           "rho_adamw")
 
 
+# kind codes and flag bits of rho_optim_step (include/rho_hip.h)
+OPT_KINDS = {"Adam": 0, "AdamW": 1, "SGD": 2, "RMSprop": 3, "Adagrad": 4, "Adamax": 5, "NAdam": 6, "RAdam": 7, "Adadelta": 8}
+OPT_MAXIMIZE, OPT_AMSGRAD, OPT_DECOUPLED_WD, OPT_NESTEROV, OPT_CENTERED = 1, 2, 4, 8, 16
+
+
+def optim_step(kind: str, p: Tensor, g: Tensor, states, hp, step: int, flags: int = 0, gscale: Optional[Tensor] = None) -> None:
+    """One fused update of the flat arena ``p`` by ``g`` (rho_optim_step).  ``states``: up to three state arenas in the kind's slot
+    order, None for a slot it does not use; ``hp``: (lr, weight_decay, eps, then the kind's own hyperparameters), rounded to float32
+    as the ABI receives them; ``gscale``: 1-element device tensor that scales the gradient as it is loaded."""
+    if kind not in OPT_KINDS:
+        raise RhoHipError(f"no fused update for optimizer kind {kind!r}")
+    _f32c(p, "p")
+    _f32c(g, "g")
+    s = list(states) + [None] * (3 - len(states))
+    for i, t in enumerate(s):
+        if t is not None and (_f32c(t, f"s{i}").numel() != p.numel()):
+            raise RhoHipError(f"state arena s{i} has {t.numel()} elements, the parameters {p.numel()}")
+    if g.numel() != p.numel():
+        raise RhoHipError(f"gradient arena has {g.numel()} elements, the parameters {p.numel()}")
+    if gscale is not None:
+        _f32c(gscale, "gscale")
+    vals = [float(v) for v in hp] + [0.0] * (8 - len(hp))
+    hp_arr = (C.c_float * 8)(*vals)
+    check(hip.lib().rho_optim_step(OPT_KINDS[kind], flags, ptr(p), ptr(g), *(ptr(t) if t is not None else None for t in s), p.numel(),
+                                   C.addressof(hp_arr), step, ptr(gscale) if gscale is not None else None, stream()),
+          "rho_optim_step")
+
+
+def sumsq_blocks(n: int) -> int:
+    """Number of per-workgroup partials rho_sumsq_partial writes for an n-element arena."""
+    k = hip.lib().rho_sumsq_blocks(n)
+    check(min(k, 0), "rho_sumsq_blocks")
+    return k
+
+
+def sumsq_partial(x: Tensor, partials: Tensor) -> None:
+    """Per-workgroup sums of x^2 into ``partials`` (>= sumsq_blocks(x.numel()) float32), fixed order, no atomics."""
+    _f32c(x, "x")
+    _f32c(partials, "partials")
+    if partials.numel() < sumsq_blocks(x.numel()):
+        raise RhoHipError("partials buffer too small")
+    check(hip.lib().rho_sumsq_partial(ptr(x), x.numel(), ptr(partials), stream()), "rho_sumsq_partial")
+
+
+def clip_coef(partials: Tensor, max_norm: float, out: Tensor) -> None:
+    """out[0] = sqrt(sum partials), out[1] = min(1, max_norm / (out[0] + 1e-6)) (torch.nn.utils.clip_grad_norm_), one workgroup."""
+    _f32c(partials, "partials")
+    if _f32c(out, "out").numel() < 2:
+        raise RhoHipError("out needs 2 floats")
+    check(hip.lib().rho_clip_coef(ptr(partials), partials.numel(), max_norm, ptr(out), stream()), "rho_clip_coef")
+
+
 # ----------------------------------------------------------------------------- embeddings
 # activation codes of the C ABI (include/rho_hip.h, rho_timestep_embed): the elementwise, parameter-free entries of the reference's
 # activation registry (rho_diffusion/registry.py:162-170)

@@ -81,6 +81,11 @@ SIGNATURES = {
     "rho_set_deterministic": (c_int, [c_int]),
     "rho_get_deterministic": (c_int, []),
     "rho_adamw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int32, c_void_p]),
+    "rho_optim_step": (c_int, [c_int32, C.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p,
+                               c_void_p]),
+    "rho_sumsq_blocks": (c_int, [c_int64]),
+    "rho_sumsq_partial": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "rho_clip_coef": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "rho_timestep_embed": (c_int, [c_void_p] * 11 + [c_int64, c_int64, c_int64, c_int, c_void_p]),
     "rho_multi_embed": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
