@@ -37,7 +37,8 @@ extern "C" {
 /* ABI version: bumped on ANY signature / struct-layout change (2: table_len in rho_q_sample(_coef), fmt in rho_gn_bwd_finalize,
  * rho_conv_desc grew; 3: round-3 additions; 9: the rho_gd_* / metrics entry points of csrc/gaussian.hip;
  * 10: learned variances - RHO_GD_LOG_BETA, the *_lv / strided / hybrid-loss entry points; the dataset entry points added since -
- * rho_crop_resize, rho_line_profile, rho_pil_resize_taps, rho_u8_image_batch - change no existing signature or struct, so by this
+ * rho_crop_resize, rho_line_profile, rho_pil_resize_taps, rho_u8_image_batch, the guidance trio rho_p_sample_step_cfg,
+ * rho_cond_keep_mask, rho_cond_drop - change no existing signature or struct, so by this
  * rule they leave it at 10: a binding that lacks them fails on the missing symbol).  A loader must compare rho_abi_version() with the header it was written against
  * before calling anything else (hip.py does; a build with all symbols but older signatures would be called with shifted arguments). */
 #define RHO_ABI_VERSION 10
@@ -64,6 +65,15 @@ int rho_q_sample(const float* x0, const float* eps, float* x_t, const float* alp
  * *t_dev (int32[1], device).  x updated in place; n elements. */
 int rho_p_sample_step(float* x, const float* eps_hat, const float* z, const float* coef_table,
                       const int32_t* t_dev, int64_t n, void* stream);
+
+/* p_sample_step under classifier-free guidance (Ho & Salimans 2022; adds to ddpm.py:210-218, the reference has no guided sampler:
+ * its ClassifierGuidance, conditioning.py:142-155, holds no classifier).  x2 float32 [2, n]: row 0 is x_t, row 1 its copy - the
+ * doubled batch the backbone reads; eps2 float32 [2, n]: row 0 the conditional, row 1 the null-condition prediction.
+ * g = fma(scale, e_c - e_u, e_u), then the update of rho_p_sample_step on (row 0 of x2, g, z) with the same coef / t_dev / z rules
+ * (t <= 0: nothing is written; t <= 1 or z == NULL: no noise), stored to BOTH rows of x2.  z float32 [n] or NULL.  Replaces the
+ * combine pass, the update and the copy into the second half: 6n floats moved (5n without z) instead of 9n. */
+int rho_p_sample_step_cfg(float* x2, const float* eps2, const float* z, const float* coef_table, const int32_t* t_dev,
+                          float scale, int64_t n, void* stream);
 
 /* Device-resident loop state of reverse_process (ddpm.py:195): *t_dev -= 1 and *offset_dev += delta,
  * so that one captured HIP graph replays every step without host involvement. Either may be NULL. */
@@ -183,6 +193,18 @@ int rho_multi_embed_bwd(const float* demb, const int32_t* idx, float* const* dta
  * out int64[n] uniform on [0, high), Philox4x32-10 stream (seed, offset) as rho_philox_normal (offset read from *offset_dev
  * when given).  Removes the CPU draw + H2D copy of every training step. */
 int rho_randint(int64_t* out, int64_t n, int64_t high, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, void* stream);
+
+/* Label dropout of classifier-free guidance training (adds to DDPM.training_step, ddpm.py:231-288; the reference always feeds the
+ * labels).  keep uint8 [n]: keep[b] = (u_b >= p) with one uniform per sample from the Philox4x32-10 stream (seed, offset) in
+ * rho_randint's counter layout (u_b = word b & 3 of counter offset + (b >> 2), over 2^32; offset read from *offset_dev when given).
+ * 0 <= p < 1; p = 0 keeps every sample. */
+int rho_cond_keep_mask(uint8_t* keep, int64_t n, float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, void* stream);
+
+/* Applies a keep mask to what rho_multi_embed wrote: for keep[b] == 0, cond[b, :] = 0 (the null condition is the zero row: the
+ * timestep embedding stands alone) and cond_idx[b, 0 .. nkeys) = -1, which rho_multi_embed_bwd skips - the tables get no gradient
+ * from a dropped sample.  cond float32 [batch, dim]; cond_idx int32 [batch, nkeys] or NULL (pre-embedded conditions); rows with
+ * keep[b] != 0 are not touched. */
+int rho_cond_drop(float* cond, int32_t* cond_idx, const uint8_t* keep, int64_t batch, int64_t dim, int64_t nkeys, void* stream);
 
 /* out[b, o] = bias[o] + sum_k act(x[b, k]) * w[o, k] (+ add[b, o])   all float32.
  * act_in: 0 = identity, 1 = SiLU.  act_out: 0 = identity, 1 = SiLU.

@@ -153,6 +153,63 @@ extern "C" int rho_p_sample_step(float* x, const float* eps_hat, const float* z,
     return 0;
 }
 
+// ----------------------------------------------------------------------------- p_sample_step, classifier-free guidance
+// x2 = [2, n]: row 0 is x_t, row 1 its copy (the 2B batch the engine reads); eps2 = [2, n]: the conditional and the null-condition
+// prediction of that batch.  g = e_u + scale * (e_c - e_u), then p_update on (x, g, z) as above, stored to BOTH rows: 4n floats
+// read (3n when z is ignored), 2n written, no guided prediction and no duplicate of x_t in between.
+// One written-out contraction again: the difference, one fma, then p_update - the 16-byte body and the scalar form round alike.
+__device__ __forceinline__ float p_update_cfg(float c0, float c1, float c2, float s, float x, float ec, float eu, float z) {
+    return p_update(c0, c1, c2, x, __fmaf_rn(s, ec - eu, eu), z);
+}
+// Row 1 starts n elements behind row 0, so the 16-byte form needs n % 4 == 0 besides the aligned bases (the caller decides: vec);
+// it then covers every element and has no tail of its own.  Any other n or pointer takes the scalar loop.
+__global__ __launch_bounds__(256) void k_p_sample_cfg(float* __restrict__ x2, const float* __restrict__ e2,
+                                                      const float* __restrict__ z, const float* __restrict__ coef,
+                                                      const int32_t* __restrict__ t_dev, float s, int64_t n, int vec) {
+    const int t = *t_dev;
+    if (t <= 0) return;
+    const float c0 = coef[3 * t + 0], c1 = coef[3 * t + 1], c2 = (t > 1 && z != nullptr) ? coef[3 * t + 2] : 0.0f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        float4* xa = (float4*)x2;
+        float4* xb = (float4*)(x2 + n);
+        const float4* ec4 = (const float4*)e2;
+        const float4* eu4 = (const float4*)(e2 + n);
+        const float4* z4 = (const float4*)z;
+        for (int64_t i = tid; i < n4; i += stride) {
+            float4 a = xa[i];
+            const float4 ec = ec4[i], eu = eu4[i];
+            float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (c2 != 0.0f) zz = z4[i];
+            a.x = p_update_cfg(c0, c1, c2, s, a.x, ec.x, eu.x, zz.x);
+            a.y = p_update_cfg(c0, c1, c2, s, a.y, ec.y, eu.y, zz.y);
+            a.z = p_update_cfg(c0, c1, c2, s, a.z, ec.z, eu.z, zz.z);
+            a.w = p_update_cfg(c0, c1, c2, s, a.w, ec.w, eu.w, zz.w);
+            xa[i] = a;
+            xb[i] = a;
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += stride) {
+            const float zz = (c2 != 0.0f) ? z[i] : 0.0f;
+            const float r = p_update_cfg(c0, c1, c2, s, x2[i], e2[i], e2[n + i], zz);
+            x2[i] = r;
+            x2[n + i] = r;
+        }
+    }
+}
+
+extern "C" int rho_p_sample_step_cfg(float* x2, const float* eps2, const float* z, const float* coef_table, const int32_t* t_dev,
+                                     float scale, int64_t n, void* stream) {
+    if (!x2 || !eps2 || !coef_table || !t_dev || n <= 0) return RHO_E_ARG;
+    const int vec = (n % 4 == 0 && (((uintptr_t)x2 | (uintptr_t)eps2 | (uintptr_t)z) & 15) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(k_p_sample_cfg, dim3(grid_for(vec ? n / 4 : n, 256)), dim3(256), 0, as_stream(stream), x2, eps2, z,
+                       coef_table, t_dev, scale, n, vec);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
 // t <- t - 1 and philox offset += delta: keeps the sampling loop's step state on the device
 __global__ void k_step_advance(int32_t* t_dev, uint64_t* offset_dev, uint64_t delta) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {

@@ -4,6 +4,7 @@
 //   k_multi_embed      MultiEmbeddings.forward (models/conditioning.py:115-139): category by exact float equality, rows summed
 //   k_multi_embed_bwd  its backward (scatter-add of the embedding gradient into the tables)
 //   k_randint          random_timesteps (diffusion/abstract_diffusion.py:163-169) on the device, Philox4x32-10
+//   k_cond_keep / k_cond_drop   label dropout of classifier-free guidance training (no counterpart in the reference)
 // All latency-bound: tiny operands, no host synchronisation, graph-capturable.
 #include "common.h"
 
@@ -181,6 +182,50 @@ extern "C" int rho_randint(int64_t* out, int64_t n, int64_t high, uint64_t seed,
     if (!out || n <= 0 || high <= 0 || high > 0x7FFFFFFFLL) return RHO_E_ARG;
     hipLaunchKernelGGL(k_randint, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), out, n, high, seed, offset,
                        offset_dev);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
+// ----------------------------------------------------------------------------- label dropout (classifier-free guidance)
+// The null condition is the ZERO row of the embedded condition: the timestep embedding of a dropped sample stands alone.
+// k_cond_keep draws the keep mask, one Philox word per sample in k_randint's counter layout (sample b: word b & 3 of counter
+// offset + (b >> 2)) against the dropout threshold of common.h: keep[b] = word_b >= uint32(p * 2^32), i.e. u_b >= p for the
+// uniform u_b = word_b / 2^32.  Reproducible from (seed, offset), independent of launch geometry.
+__global__ void k_cond_keep(uint8_t* __restrict__ keep, int64_t n, uint32_t thr, uint64_t seed, uint64_t offset,
+                            const uint64_t* __restrict__ offset_dev) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t r[4];
+    philox4x32_10((offset_dev ? *offset_dev : offset) + (uint64_t)(i >> 2), seed, r);
+    keep[i] = r[i & 3] >= thr ? 1 : 0;
+}
+
+extern "C" int rho_cond_keep_mask(uint8_t* keep, int64_t n, float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                                  void* stream) {
+    if (!keep || n <= 0 || !(p >= 0.0f) || !(p < 1.0f)) return RHO_E_ARG;
+    const uint32_t thr = (uint32_t)((double)p * 4294967296.0);
+    hipLaunchKernelGGL(k_cond_keep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), keep, n, thr, seed, offset,
+                       offset_dev);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
+// A sample with keep[b] == 0 loses its condition: cond[b, :] = 0 and idx[b, :] = -1, the value k_multi_embed_bwd(_det) already
+// skip, so the tables receive no gradient from it.  One workgroup per sample; idx may be NULL (pre-embedded conditions).
+__global__ __launch_bounds__(256) void k_cond_drop(float* __restrict__ cond, int32_t* __restrict__ idx,
+                                                   const uint8_t* __restrict__ keep, int dim, int nkeys) {
+    const int b = blockIdx.x;
+    if (keep[b] != 0) return;
+    for (int d = threadIdx.x; d < dim; d += 256) cond[(int64_t)b * dim + d] = 0.0f;
+    if (idx != nullptr && threadIdx.x < nkeys) idx[(int64_t)b * nkeys + threadIdx.x] = -1;
+}
+
+extern "C" int rho_cond_drop(float* cond, int32_t* cond_idx, const uint8_t* keep, int64_t batch, int64_t dim, int64_t nkeys,
+                             void* stream) {
+    if (!cond || !keep || batch <= 0 || batch > 0x7FFFFFFF || dim <= 0 || dim > 0x7FFFFFFF) return RHO_E_ARG;
+    if (cond_idx != nullptr && (nkeys <= 0 || nkeys > 16)) return RHO_E_ARG;
+    hipLaunchKernelGGL(k_cond_drop, dim3((unsigned)batch), dim3(256), 0, as_stream(stream), cond, cond_idx, keep, (int)dim,
+                       (int)nkeys);
     RHO_LAUNCH_CHECK();
     return 0;
 }

@@ -9,6 +9,8 @@ The arithmetic runs in the HIP kernels of librho_hip.so:
   * reverse update -> rho_p_sample_step; the step index lives on the device (rho_step_advance), the
                       loop issues no host synchronisation and no per-step H2D copies
   * loss           -> rho_mse
+  * guidance       -> classifier-free (not in the reference): label dropout in training_step (rho_cond_keep_mask draws, the
+                      engine's rho_cond_drop applies), guided sampling at batch 2B with rho_p_sample_step_cfg
 Reference quirks are kept deliberately: 0.8*sqrt(beta) noise scale, z = 0 for t <= 1,
 no update at t = 0 although the backbone is evaluated, clamp to [-1, 1] after every update,
 checkpoint spacing T // 10.
@@ -34,7 +36,8 @@ class DDPM(AbstractDiffusionPipeline):
     def __init__(self, backbone, backbone_kwargs: dict, schedule, loss_func, timesteps: Union[int, Tensor] = 1000,
                  cond_fn: str = None, cond_fn_kwargs: dict = None, optimizer=None,
                  opt_kwargs: Union[Mapping[str, Any], None] = {}, t_checkpoints=None, sampling_batch_size=10,
-                 sample_every_n_epochs=5, sample_parameter_space=None, save_checkpoint_every_n_epochs=10):
+                 sample_every_n_epochs=5, sample_parameter_space=None, save_checkpoint_every_n_epochs=10,
+                 guidance_scale=None, cond_drop_prob: float = 0.0):
         super().__init__(backbone=backbone, backbone_kwargs=backbone_kwargs, schedule=schedule, timesteps=timesteps,
                          cond_fn=cond_fn, cond_fn_kwargs=cond_fn_kwargs, optimizer=optimizer, opt_kwargs=opt_kwargs)
         if isinstance(loss_func, str):
@@ -47,6 +50,15 @@ class DDPM(AbstractDiffusionPipeline):
         self.sample_every_n_epochs = sample_every_n_epochs
         self.sample_parameter_space = sample_parameter_space
         self.save_weights_every_n_epochs = save_checkpoint_every_n_epochs
+        # classifier-free guidance (Ho & Salimans 2022): during training the labels of a sample are dropped with probability
+        # ``cond_drop_prob`` (its condition becomes the zero row, the null condition); with ``guidance_scale`` = s set, sampling
+        # evaluates the backbone on the labels and on the null condition and follows e_u + s * (e_c - e_u).  s = 1 is the
+        # conditional model, s = 0 the unconditional one.  The defaults (None, 0) are the reference's behaviour.
+        cond_drop_prob = float(cond_drop_prob)
+        if not 0.0 <= cond_drop_prob < 1.0:
+            raise ValueError(f"cond_drop_prob must lie in [0, 1): got {cond_drop_prob} (at 1 no sample would ever see its labels)")
+        self.cond_drop_prob = cond_drop_prob
+        self.guidance_scale = None if guidance_scale is None else float(guidance_scale)
         # counter-based RNG state: one stream per rank (seed + rank), offset advances per draw
         self.noise_seed = int(os.environ.get("RHO_SEED", "777")) + int(os.environ.get("RANK", "0"))
         self._noise_offset = 0
@@ -95,9 +107,26 @@ class DDPM(AbstractDiffusionPipeline):
         return [x_t.type(data.dtype), noise.type(data.dtype)]
 
     # ------------------------------------------------------------------ p_sample loop
+    def _refuse_unguidable(self, conditions) -> None:
+        """The requirements of guided sampling that can be checked before anything is drawn."""
+        if conditions is None:
+            raise ValueError("guidance_scale needs `conditions`: guidance contrasts the labelled prediction with the unlabelled one")
+        if not hasattr(self.backbone, "engine"):
+            raise ValueError(f"guidance_scale needs a backbone with a HIP engine that takes labels; {type(self.backbone).__name__} "
+                             "is unconditional")
+        if getattr(self.backbone, "num_classes", None) is None:
+            raise ValueError("guidance_scale needs a class-conditional backbone (num_classes is None)")
+
     @torch.no_grad()  # (reference: inference_mode; no_grad keeps the plan buffers usable in training too)
-    def reverse_process(self, x_T: Tensor, conditions=None, t_checkpoints=None) -> dict:
-        """ddpm.py:132-229.  ``x_T`` is only a shape/device template (:171)."""
+    def reverse_process(self, x_T: Tensor, conditions=None, t_checkpoints=None, guidance_scale=None) -> dict:
+        """ddpm.py:132-229.  ``x_T`` is only a shape/device template (:171).  ``guidance_scale`` (default: the attribute of that
+        name; None = the reference's loop) samples with classifier-free guidance: the engine runs at batch 2B on
+        cat(x_t, x_t) with cat(embedded labels, zeros), rho_p_sample_step_cfg combines the two predictions, applies the update
+        and writes it to both halves.  The noise draws, their Philox offsets and the returned shapes are those of the unguided
+        call."""
+        scale = self.guidance_scale if guidance_scale is None else float(guidance_scale)
+        if scale is not None:
+            self._refuse_unguidable(conditions)
         hip.require_gpu(x_T, "x_T")
         dev = x_T.device
         batch_size = x_T.size(0)
@@ -128,10 +157,29 @@ class DDPM(AbstractDiffusionPipeline):
 
         engine = self.backbone.engine() if hasattr(self.backbone, "engine") else None
         t_dev = torch.full((1,), denoise_steps - 1, dtype=torch.int32, device=dev)
+        if scale is None:
+            x_all = x_t                                     # what the backbone reads
+
+            def update(pred, z):
+                ops.p_sample_step(x_t, pred, z, tables["coef"], t_dev)
+        else:
+            e = 4 * self.backbone.model_channels
+            if not (torch.is_tensor(cc) and cc.dim() == 2 and tuple(cc.shape) == (batch_size, e)):
+                raise ValueError(f"guidance_scale needs conditions that embed to [batch, 4 * model_channels] = ({batch_size}, {e}), "
+                                 "whose null condition is the zero row: the backbone's cond_fn does not give that form for "
+                                 f"{'these conditions' if not torch.is_tensor(cc) else tuple(cc.shape)}")
+            # the doubled batch: rows [0, B) carry the labels, rows [B, 2B) the null condition; x_t is its first half from here on
+            cc = cc.to(device=dev, dtype=torch.float32)
+            cc = torch.cat([cc, torch.zeros_like(cc)]).contiguous()
+            x_all = torch.cat([x_t, x_t])
+            x_t = x_all[:batch_size]
+
+            def update(pred, z):
+                ops.p_sample_step_cfg(x_all, pred, z, tables["coef"], t_dev, scale)
         t_idx = 0
         if (self.hip_graph_sampling and engine is not None and denoise_steps > 2 and "noise" not in self.__dict__
                 and type(self).noise is DDPM.noise):
-            done = self._reverse_process_graph(x_t, cc, engine, tables, t_dev, denoise_steps, buf, steps_per_ckpt, num_checkpoints)
+            done = self._reverse_process_graph(x_all, x_t, cc, engine, update, t_dev, denoise_steps, buf, steps_per_ckpt, num_checkpoints)
             if done:
                 self._check_backbone_errors()
                 return {"buffer": buf, "denoised": x_t}
@@ -139,11 +187,11 @@ class DDPM(AbstractDiffusionPipeline):
         for t in range(denoise_steps - 1, -1, -1):
             z = self.noise(x_t) if t > 1 else None          # drawn before the backbone call (:196-199)
             if engine is not None:
-                pred = engine.forward(x_t, None, cc, t_scalar_dev=t_dev)
+                pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
             else:
                 pred = self.backbone(x_t, torch.full((batch_size,), t, device=dev, dtype=torch.long), cc)
             if t > 0:
-                ops.p_sample_step(x_t, pred.contiguous(), z, tables["coef"], t_dev)
+                update(pred.contiguous(), z)
             if buf is not None and t % steps_per_ckpt == 0 and t_idx < num_checkpoints:
                 buf[:, t_idx].copy_(x_t)
                 t_idx += 1
@@ -151,22 +199,23 @@ class DDPM(AbstractDiffusionPipeline):
         self._check_backbone_errors()
         return {"buffer": buf, "denoised": x_t}
 
-    def _reverse_process_graph(self, x_t, cc, engine, tables, t_dev, denoise_steps, buf, steps_per_ckpt, num_checkpoints) -> bool:
+    def _reverse_process_graph(self, x_all, x_t, cc, engine, update, t_dev, denoise_steps, buf, steps_per_ckpt, num_checkpoints) -> bool:
         """The loop of reverse_process with steps t = T-2 .. 0 replayed from one captured HIP graph (step T-1 runs eagerly:
         it builds the engine plan and its buffers).  Same arithmetic and the same Philox stream as the eager loop: z is
         drawn at the offset the eager loop would use (the draws of t <= 1 are ignored by the update kernel either way).
-        Returns False (nothing modified but the RNG offset bookkeeping) if the capture fails."""
+        ``x_all`` is what the backbone reads and ``update`` writes - ``x_t`` itself, or under guidance the doubled batch whose
+        first half ``x_t`` is.  Returns False (nothing modified but the RNG offset bookkeeping) if the capture fails."""
         dev = x_t.device
         n_elem = x_t.numel()
         delta = (n_elem + 3) // 4
         z = torch.empty_like(x_t)
         off_dev = torch.full((1,), self._noise_offset, dtype=torch.int64, device=dev)
-        x_save = x_t.clone()
+        x_save = x_all.clone()
 
         def step():
             ops.philox_normal(z, self.noise_seed, 0, offset_dev=off_dev)
-            pred = engine.forward(x_t, None, cc, t_scalar_dev=t_dev)
-            ops.p_sample_step(x_t, pred, z, tables["coef"], t_dev)
+            pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
+            update(pred, z)
             ops.step_advance(t_dev, off_dev, delta)
 
         t_idx = 0
@@ -185,7 +234,7 @@ class DDPM(AbstractDiffusionPipeline):
                 step()
         except Exception as exc:  # noqa: BLE001  (capture is an optimisation; any failure -> eager loop)
             torch.cuda.synchronize()
-            x_t.copy_(x_save)
+            x_all.copy_(x_save)
             if buf is not None:
                 buf.zero_()
             self.hip_graph_sampling = False
@@ -206,6 +255,14 @@ class DDPM(AbstractDiffusionPipeline):
             self._noise_offset += (batch_size + 3) // 4
             return t
         return self.random_timesteps(batch_size).to(device)
+
+    def _draw_cond_keep(self, batch_size: int, device) -> Tensor:
+        """uint8 [B] keep mask of the label dropout: 1 with probability 1 - cond_drop_prob, drawn on the device from this rank's
+        Philox stream under a seed of its own (rho_cond_keep_mask), the shared offset advanced as ``_draw_timesteps`` does.
+        Tests override it to inject a mask, as they inject ``noise``."""
+        keep = ops.cond_keep_mask(batch_size, self.cond_drop_prob, self.noise_seed ^ 0x2545F4914F6CDD1D, self._noise_offset, device=device)
+        self._noise_offset += (batch_size + 3) // 4
+        return keep
 
     def _check_nan(self, force: bool = False) -> None:
         """Device-side form of the per-step host check at ddpm.py:268-272: the flag is set by the
@@ -241,7 +298,16 @@ class DDPM(AbstractDiffusionPipeline):
         t = self._draw_timesteps(batch_size, data.device)
         x_data, noise = self.forward_process(data, t)
         self._check_nan()
-        if labels is not None:
+        if labels is not None and self.cond_drop_prob > 0.0 and self.backbone.training and torch.is_grad_enabled():
+            if not hasattr(self.backbone, "engine"):
+                raise ValueError(f"cond_drop_prob needs a backbone with a HIP engine that takes labels, not {type(self.backbone).__name__}")
+            engine = self.backbone.engine()
+            engine.set_cond_keep(self._draw_cond_keep(batch_size, data.device))     # consumed by the training forward below
+            try:
+                pred_noise = self.backbone(x_data, t, labels)
+            finally:
+                engine.set_cond_keep(None)
+        elif labels is not None:
             pred_noise = self.backbone(x_data, t, labels)
         else:
             pred_noise = self.backbone(x_data, t)
@@ -278,7 +344,7 @@ class DDPM(AbstractDiffusionPipeline):
         cond = None
         if parameter_space is not None:
             cond = sample_from_discrete_parameter_space(parameter_space, sample_data.shape[0], random=random, device=self.device)
-        results = self.reverse_process(x_T=sample_data, conditions=cond, t_checkpoints=self.t_checkpoints)
+        results = self.reverse_process(x_T=sample_data, conditions=cond, t_checkpoints=self.t_checkpoints, guidance_scale=self.guidance_scale)
         self.last_samples = results
         return self.make_image_grid(results["denoised"], filename="output_%d.png" % self.current_epoch)
 

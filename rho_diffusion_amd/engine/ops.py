@@ -58,6 +58,23 @@ def p_sample_step(x: Tensor, eps_hat: Tensor, z: Optional[Tensor], coef_table: T
     return x
 
 
+def p_sample_step_cfg(x2: Tensor, eps2: Tensor, z: Optional[Tensor], coef_table: Tensor, t_dev: Tensor, scale: float) -> Tensor:
+    """One guided reverse update (rho_p_sample_step_cfg).  ``x2`` [2B, ...]: x_t and its copy; ``eps2`` [2B, ...]: the conditional
+    and the null-condition prediction; ``z`` [B, ...] or None.  Both halves of ``x2`` receive the update."""
+    _f32c(x2, "x2"), _f32c(eps2, "eps2"), _f32c(coef_table, "coef_table")
+    if z is not None:
+        _f32c(z, "z")
+    n = x2.numel() // 2
+    if x2.numel() != 2 * n or eps2.numel() != 2 * n or (z is not None and z.numel() != n):
+        raise RhoHipError(f"x2 / eps2 hold two rows of n elements and z one: got {x2.numel()}, {eps2.numel()}, "
+                          f"{None if z is None else z.numel()}")
+    if t_dev.dtype != torch.int32:
+        raise RhoHipError("t_dev must be int32[1] on the GPU")
+    check(hip.lib().rho_p_sample_step_cfg(ptr(x2), ptr(eps2), ptr(z), ptr(coef_table), ptr(t_dev), float(scale), n, stream()),
+          "rho_p_sample_step_cfg")
+    return x2
+
+
 def q_sample_coef(x0: Tensor, eps: Tensor, t: Tensor, coef_a: Tensor, coef_b: Tensor, out: Optional[Tensor] = None,
                   err_flag: Optional[Tensor] = None) -> Tensor:
     """x_t = a[t] * x0 + b[t] * eps with explicit float32 tables (GaussianDiffusionPipeline.q_sample)."""
@@ -502,6 +519,31 @@ def randint(n: int, high: int, seed: int, offset: int = 0, offset_dev: Optional[
     hip.require_gpu(out, "out")
     check(hip.lib().rho_randint(ptr(out), n, high, seed & (2 ** 64 - 1), offset, ptr(offset_dev), stream()), "rho_randint")
     return out
+
+
+def cond_keep_mask(n: int, p: float, seed: int, offset: int = 0, offset_dev: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                   device=None) -> Tensor:
+    """uint8 [n] keep mask of label dropout: keep[b] = (u_b >= p), one Philox uniform per sample from the stream (seed, offset)."""
+    out = torch.empty(n, dtype=torch.uint8, device=device) if out is None else out
+    hip.require_gpu(out, "out")
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < n:
+        raise RhoHipError("out must be a contiguous uint8 tensor of at least n elements")
+    check(hip.lib().rho_cond_keep_mask(ptr(out), n, float(p), seed & (2 ** 64 - 1), offset, ptr(offset_dev), stream()),
+          "rho_cond_keep_mask")
+    return out
+
+
+def cond_drop(cond: Tensor, cond_idx: Optional[Tensor], keep: Tensor, nkeys: int = 0) -> Tensor:
+    """Zero the rows of ``cond`` [B, dim] whose ``keep`` [B] (uint8) is 0 and set their ``cond_idx`` [B, nkeys] entries to -1."""
+    _f32c(cond, "cond")
+    hip.require_gpu(keep, "keep")
+    B = cond.shape[0]
+    if cond.dim() != 2 or keep.dtype != torch.uint8 or not keep.is_contiguous() or keep.numel() != B:
+        raise RhoHipError(f"cond must be [B, dim] and keep uint8 [B]: got {tuple(cond.shape)}, {keep.dtype} {tuple(keep.shape)}")
+    if cond_idx is not None and (cond_idx.dtype != torch.int32 or not cond_idx.is_contiguous() or cond_idx.numel() < B * nkeys):
+        raise RhoHipError("cond_idx must be a contiguous int32 tensor of at least B * nkeys elements")
+    check(hip.lib().rho_cond_drop(ptr(cond), ptr(cond_idx), ptr(keep), B, cond.shape[1], nkeys, stream()), "rho_cond_drop")
+    return cond
 
 
 def sph_harm_fields(lm: Tensor, grid: int, out: Optional[Tensor] = None, minmax_in: Optional[Tensor] = None,

@@ -77,6 +77,7 @@ class UNetEngine:
         self._prep_sig = None
         self._prep_eager: List[_ConvW] = []
         self._last_train_plan: Optional["_Plan"] = None
+        self._cond_keep: Optional[Tensor] = None      # label-dropout mask for the next training forward (set_cond_keep)
         with torch.inference_mode(False):
             self._collect()
             self.refresh_weights(force=True)
@@ -252,6 +253,12 @@ class UNetEngine:
         return emb + main
 
     # ------------------------------------------------------------------ forward / backward
+    def set_cond_keep(self, keep: Optional[Tensor]) -> None:
+        """Label dropout (classifier-free guidance training): hand the NEXT ``forward(train=True)`` a keep mask [B] (nonzero = the
+        sample keeps its labels).  A dropped sample's condition becomes the zero row and contributes no gradient to the label
+        embedding.  One forward consumes the mask; inference forwards neither see nor consume it; None withdraws it."""
+        self._cond_keep = keep
+
     def forward(self, x: Tensor, timesteps: Tensor, y: Optional[Tensor] = None,
                 t_scalar_dev: Optional[Tensor] = None, train: bool = False) -> Tensor:
         hip.require_gpu(x, "x")
@@ -264,9 +271,11 @@ class UNetEngine:
         if plan is None:
             with torch.inference_mode(False), torch.no_grad():     # plan buffers must stay ordinary tensors
                 plan = self._plans[key] = _Plan(self, tuple(x.shape), y is not None, bool(train))
+        keep = None
         if train:
             self._last_train_plan = plan
-        return plan.run(x, timesteps, y, t_scalar_dev)
+            keep, self._cond_keep = self._cond_keep, None
+        return plan.run(x, timesteps, y, t_scalar_dev, keep)
 
     # environment switches a plan reads while it is built (A/B knobs): part of the plan key, so flipping one rebuilds the plan
     # (exactly the names _plan_switches reads, the engine's only reads - tests/test_host_logic.py holds the two together; the library's
@@ -376,7 +385,9 @@ class _Plan:
         return out
 
     # ------------------------------------------------------------------ execution
-    def run(self, x: Tensor, timesteps: Optional[Tensor], y: Optional[Tensor], t_scalar_dev: Optional[Tensor]) -> Tensor:
+    def run(self, x: Tensor, timesteps: Optional[Tensor], y: Optional[Tensor], t_scalar_dev: Optional[Tensor],
+            keep: Optional[Tensor] = None) -> Tensor:
+        """``keep`` (training plans only, see UNetEngine.set_cond_keep): [B] mask, a sample whose entry is 0 loses its condition."""
         eng = self.eng
         m = eng.model
         if x.data_ptr() != self.x_in.data_ptr():
@@ -384,10 +395,18 @@ class _Plan:
         te0, te2 = m.time_embed[0], m.time_embed[2]
         self.cond_src = None
         self.cond_dev = None
+        if keep is not None:
+            if self.cond is None:
+                raise hip.RhoHipError("a label keep mask was set, but this forward has no labels to drop")
+            if keep.numel() != self.B:
+                raise hip.RhoHipError(f"the label keep mask has {keep.numel()} entries for a batch of {self.B}")
+            keep = (keep.reshape(-1) != 0).to(device=self.cond.device, dtype=torch.uint8)
         if self.cond is not None:
             # label handling of unet_v2.py:702-719
             if y.dim() == 2 and tuple(y.shape) == tuple(self.emb.shape):
                 self.cond.copy_(y.to(self.cond.device))
+                if keep is not None:
+                    ops.cond_drop(self.cond, None, keep)       # rows of the copy: the caller's tensor stays as it is
             else:
                 if y.dim() == 1:
                     assert y.shape == (x.shape[0],)
@@ -403,10 +422,15 @@ class _Plan:
                     check(self.L.rho_multi_embed(ptr(yf), 1 if yf.dim() == 1 else yf.shape[1], ptr(cd["space"]), ptr(cd["key_off"]),
                                                  ptr(cd["tables"]), cd["nkeys"], self.B, self.cond.shape[1], ptr(self.cond),
                                                  ptr(self.cond_idx), ptr(eng.err_flag()), hip.stream()), "rho_multi_embed")
+                    if keep is not None:
+                        # zero row + category -1: rho_multi_embed_bwd skips the sample, its table rows get no gradient
+                        ops.cond_drop(self.cond, self.cond_idx, keep, cd["nkeys"])
                     self.cond_dev = cd
                 else:
                     with (torch.enable_grad() if self.train else torch.no_grad()):
                         c = m.cond_fn(y)          # a user-supplied cond_fn module (not MultiEmbeddings): evaluated as given
+                        if keep is not None:
+                            c = c * keep.to(c.dtype).reshape((-1,) + (1,) * (c.dim() - 1))      # under autograd: no gradient from a dropped row
                     self.cond_src = c if (self.train and c.requires_grad) else None
                     self.cond.copy_(c.detach())
         # timestep embedding: sinusoid of t (any integer) -> Linear -> SiLU -> Linear (+ cond), one launch

@@ -73,6 +73,7 @@ SIGNATURES = {
     "rho_build_info": (C.c_char_p, []),
     "rho_q_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "rho_p_sample_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rho_p_sample_step_cfg": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p]),
     "rho_step_advance": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
     "rho_philox_normal": (c_int, [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p]),
     "rho_mse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -91,6 +92,8 @@ SIGNATURES = {
                                 c_void_p]),
     "rho_multi_embed_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "rho_randint": (c_int, [c_void_p, c_int64, c_int64, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "rho_cond_keep_mask": (c_int, [c_void_p, c_int64, c_float, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "rho_cond_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "rho_sph_harm_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "rho_sph_harm_fields": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rho_crop_resize_taps": (c_int64, [c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
