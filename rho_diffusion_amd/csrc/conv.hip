@@ -1328,102 +1328,98 @@ namespace {
 
 using namespace rho_conv;
 
-// Variant query (rho_conv_variant): the same dispatch as a launch, but the chosen instantiation is written as text
-// instead of being launched - so the name can never disagree with what rho_conv_nd_fwd runs.
-struct VariantOut {
-    char* buf;
-    int cap;
+// One launch, planned on the host: which kernel runs, with which arguments, and what the caller has to provide for it.  conv_plan()
+// fills it from the descriptor alone - no HIP call, no pointer of the descriptor followed - and rho_conv_nd_fwd and its three
+// queries all read it, so a query cannot disagree with the launch.  The stages run in this order and the first failure ends the
+// plan.  A query reads the status of the stage it depends on and no later one: callers ask for the statistics tiles and the
+// workspace first and attach stats / gnb_* / ws afterwards, so those queries succeed for descriptors a launch would still refuse.
+enum Stage {
+    ST_DESC,     // 1  descriptor validation
+    ST_ROUTE,    // 2  k_conv32 / k_gemm1x1 (which plan their own launch, conv32.h / gemm1x1.h) or k_conv
+    ST_GEOM,     // 3  geometry, cout tile, position tile, grid, statistics tiles      -> rho_conv_stats_tiles
+    ST_KSPLIT,   // 4  k-split and its workspace                                        -> rho_conv_workspace_bytes
+    ST_ATTACH,   // 5  stats / gnb_* / gna_* / sk_* attachments, LDS bytes
+    ST_KEY,      // 6  variant key and its instantiation                                -> rho_conv_variant, rho_conv_nd_fwd
+    ST_DONE
 };
-thread_local VariantOut* g_variant = nullptr;
+enum Kernel { K_CONV, K_CONV32, K_GEMM1X1 };
+struct VariantKey { bool bf16; int kd, kh, kw, BM, MAXP, NW; bool M16, FSK, GNA; };      // one instantiation of k_conv
+using ConvFn = void (*)(const ConvK);
+struct ConvPlan : PlanStatus<Stage> {
+    Kernel kernel;
+    VariantKey key;          // k_conv only, as are fn, k, grid and lds
+    ConvFn fn;
+    ConvK k;
+    dim3 grid;
+    size_t lds;
+    int64_t stats_tiles;     // statistics tiles per sample (0: this launch has none)
+    int64_t ws_want;         // workspace bytes the k-split asks for (0: not split)
+    int ksplit;              // the split the attached workspace allows (1: none)
+    long long positions;     // output positions of the launch's own grid = rows of a k-split slab
+};
 
-template <typename T, int KD, int KH, int KW, int BM, int MAXP, int NW, bool M16 = false, bool FSK = false, bool GNA = false>
-int launch_one(const ConvK& k, dim3 grid, size_t lds, hipStream_t st) {
-    if (g_variant != nullptr) {
-        snprintf(g_variant->buf, (size_t)g_variant->cap, "k_conv<%s,%d,%d,%d,BM=%d,MAXP=%d,NW=%d,M16=%d>%s%s", sizeof(T) == 2 ? "bf16" : "f32",
-                 KD, KH, KW, BM, MAXP, NW, (int)M16, FSK ? "+skip" : "", GNA ? "+gn_apply" : "");
-        return 0;
-    }
-    auto fn = k_conv<T, KD, KH, KW, BM, MAXP, NW, M16, FSK, GNA>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(fn, grid, dim3(NW * 64), lds, st, k);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+// key -> instantiation; nullptr for a key that has none.  The cout tiles of one flavour: 128 couts on 8 waves with S / 2 halo slots
+// per thread, 64 (and 32, where the flavour has it) couts on 4 waves with S
+template <typename T, int KD, int KH, int KW, int S, bool M16, bool FSK, bool GNA, bool BM32>
+ConvFn conv_tiles(const VariantKey& v) {
+    if (v.MAXP != (v.BM == 128 ? S / 2 : S) || v.NW != (v.BM == 128 ? 8 : 4)) return nullptr;
+    if (v.BM == 128) return k_conv<T, KD, KH, KW, 128, S / 2, 8, M16, FSK, GNA>;
+    if (v.BM == 64) return k_conv<T, KD, KH, KW, 64, S, 4, M16, FSK, GNA>;
+    if constexpr (BM32) { if (v.BM == 32) return k_conv<T, KD, KH, KW, 32, S, 4, M16, FSK, GNA>; }
+    return nullptr;
 }
-
-// np = halo positions of the chosen tile.  BM = 128 runs 8 waves (slots per thread: 5 for np <= 640, else 14).
+// ... and the flavours of one tap shape.  Every shape has the small-halo tiles (np <= 640: S = 10); the sub-pixel phase shapes (2-tap
+// axes; 3x1x1: the even-even parity of a stride-2 split) are stride 1 and have no others.
 template <typename T, int KD, int KH, int KW>
-int launch_bm(const ConvK& k, int BM, int np, dim3 grid, size_t lds, bool m16, hipStream_t st) {
-    // sub-pixel phase kernels (2-tap axes; 3x1x1: the even-even parity of a stride-2 split): stride 1 - the small-halo variants only
+ConvFn conv_kernel_taps(const VariantKey& v) {
+    constexpr int NT = KD * KH * KW;
     constexpr bool PHASE = (KH == 2 || KW == 2 || (KD == 3 && KH == 1 && KW == 1));
-    if constexpr (PHASE) { if (np > 640) return RHO_E_SHAPE; }
-    if constexpr (sizeof(T) == 2 && KD * KH * KW > 1 && (KD * KH * KW) % 3 == 0) {
-        // bf16, stride 1, no upsampling, regular halo: the 16x16x32 MFMA layout (holds a higher clock under load)
-        if (m16 && np <= 640) {
-            if constexpr (KD == 3 && KH == 3 && KW == 3) {
-                if (k.sk_w != nullptr) {                   // (conv_impl only sets it for this geometry)
-                    if (BM == 128) return launch_one<T, KD, KH, KW, 128, 5, 8, true, true>(k, grid, lds, st);
-                    if (BM == 64) return launch_one<T, KD, KH, KW, 64, 10, 4, true, true>(k, grid, lds, st);
-                }
-            }
-            if (BM == 128) return launch_one<T, KD, KH, KW, 128, 5, 8, true>(k, grid, lds, st);
-            if (BM == 64) return launch_one<T, KD, KH, KW, 64, 10, 4, true>(k, grid, lds, st);
-        }
+    constexpr bool HAS_M16 = sizeof(T) == 2 && NT > 1 && NT % 3 == 0;      // the 16x16x32 MFMA layout (holds a higher clock under load)
+    if (v.FSK) {              // folded skip: the 16x16x32 3x3x3 variants
+        if constexpr (HAS_M16 && NT == 27) { if (v.M16 && !v.GNA) return conv_tiles<T, KD, KH, KW, 10, true, true, false, false>(v); }
+        return nullptr;
     }
-    if (k.sk_w != nullptr) return RHO_E_ARG;               // a folded skip needs one of the two variants above
-    if (k.gna_g != nullptr) {                              // GroupNorm backward apply in the epilogue: the 1x1x1 instantiations
-        if constexpr (KD * KH * KW == 1) {
-            if (np > 640) return RHO_E_SHAPE;
-            if (BM == 128) return launch_one<T, 1, 1, 1, 128, 5, 8, false, false, true>(k, grid, lds, st);
-            if (BM == 64) return launch_one<T, 1, 1, 1, 64, 10, 4, false, false, true>(k, grid, lds, st);
-            return launch_one<T, 1, 1, 1, 32, 10, 4, false, false, true>(k, grid, lds, st);
-        }
-        return RHO_E_ARG;
+    if (v.GNA) {              // GroupNorm backward apply in the epilogue: 1x1x1
+        if constexpr (NT == 1) { if (!v.M16) return conv_tiles<T, 1, 1, 1, 10, false, false, true, true>(v); }
+        return nullptr;
     }
-    if (BM == 128) {
-        if (np <= 640) return launch_one<T, KD, KH, KW, 128, 5, 8>(k, grid, lds, st);
-        if constexpr (!PHASE) return launch_one<T, KD, KH, KW, 128, 14, 8>(k, grid, lds, st);
+    if (v.M16) {
+        if constexpr (HAS_M16) return conv_tiles<T, KD, KH, KW, 10, true, false, false, false>(v);
+        return nullptr;
     }
-#define RHO_CASE(bm)                                                                   \
-    if (BM == bm) {                                                                    \
-        if (np <= 640) return launch_one<T, KD, KH, KW, bm, 10, 4>(k, grid, lds, st);  \
-        if constexpr (!PHASE) return launch_one<T, KD, KH, KW, bm, 28, 4>(k, grid, lds, st); \
-    }
-    RHO_CASE(32)
-    RHO_CASE(64)
-#undef RHO_CASE
-    return RHO_E_ARG;
+    if (ConvFn f = conv_tiles<T, KD, KH, KW, 10, false, false, false, true>(v)) return f;
+    if constexpr (!PHASE) return conv_tiles<T, KD, KH, KW, 28, false, false, false, true>(v);
+    return nullptr;
 }
-
 template <typename T>
-int launch_taps(const rho_conv_desc& d, const ConvK& k, int BM, int np, dim3 grid, size_t lds, bool m16, hipStream_t st) {
-    if (d.kd == 3 && d.kh == 3 && d.kw == 3) return launch_bm<T, 3, 3, 3>(k, BM, np, grid, lds, m16, st);
-    if (d.kd == 1 && d.kh == 3 && d.kw == 3) return launch_bm<T, 1, 3, 3>(k, BM, np, grid, lds, m16, st);
-    if (d.kd == 1 && d.kh == 1 && d.kw == 3) return launch_bm<T, 1, 1, 3>(k, BM, np, grid, lds, m16, st);
-    if (d.kd == 1 && d.kh == 1 && d.kw == 1) return launch_bm<T, 1, 1, 1>(k, BM, np, grid, lds, m16, st);
-    // sub-pixel phases of a conv behind a nearest x2 upsample (3-D / 2-D: both inner axes; 1-D: the last)
-    if (d.kd == 3 && d.kh == 2 && d.kw == 2) return launch_bm<T, 3, 2, 2>(k, BM, np, grid, lds, m16, st);
-    if (d.kd == 1 && d.kh == 2 && d.kw == 2) return launch_bm<T, 1, 2, 2>(k, BM, np, grid, lds, m16, st);
-    if (d.kd == 1 && d.kh == 1 && d.kw == 2) return launch_bm<T, 1, 1, 2>(k, BM, np, grid, lds, m16, st);
-    // parity split of a 3-D stride-2 conv (1- and 2-tap inner axes)
-    if (d.kd == 3 && d.kh == 1 && d.kw == 1) return launch_bm<T, 3, 1, 1>(k, BM, np, grid, lds, m16, st);
-    if (d.kd == 3 && d.kh == 1 && d.kw == 2) return launch_bm<T, 3, 1, 2>(k, BM, np, grid, lds, m16, st);
-    if (d.kd == 3 && d.kh == 2 && d.kw == 1) return launch_bm<T, 3, 2, 1>(k, BM, np, grid, lds, m16, st);
-    return RHO_E_ARG;
+ConvFn conv_kernel(const VariantKey& v) {
+    if (v.kd < 1 || v.kd > 3 || v.kh < 1 || v.kh > 3 || v.kw < 1 || v.kw > 3) return nullptr;
+    switch (v.kd * 100 + v.kh * 10 + v.kw) {
+        case 333: return conv_kernel_taps<T, 3, 3, 3>(v);
+        case 133: return conv_kernel_taps<T, 1, 3, 3>(v);
+        case 113: return conv_kernel_taps<T, 1, 1, 3>(v);
+        case 111: return conv_kernel_taps<T, 1, 1, 1>(v);
+        // sub-pixel phases of a conv behind a nearest x2 upsample (3-D / 2-D: both inner axes; 1-D: the last)
+        case 322: return conv_kernel_taps<T, 3, 2, 2>(v);
+        case 122: return conv_kernel_taps<T, 1, 2, 2>(v);
+        case 112: return conv_kernel_taps<T, 1, 1, 2>(v);
+        // parity split of a 3-D stride-2 conv (1- and 2-tap inner axes)
+        case 311: return conv_kernel_taps<T, 3, 1, 1>(v);
+        case 312: return conv_kernel_taps<T, 3, 1, 2>(v);
+        case 321: return conv_kernel_taps<T, 3, 2, 1>(v);
+    }
+    return nullptr;
 }
+ConvFn conv_kernel(const VariantKey& v) { return v.bf16 ? conv_kernel<bf16_raw>(v) : conv_kernel<float>(v); }
 
-}  // namespace
+bool m16_env_on() { static const bool on = env_on("RHO_CONV_M16"); return on; }
+// A/B knob: short contractions (<= N input-channel chunks) on the 4-wave 64-cout tile, two workgroups per CU, instead of the
+// 8-wave 128-cout tile whose waves all sit in set-up / epilogue at the same time (0 = off)
+int bm64_max_chunks() { static const int n = getenv("RHO_BM64_MAX_CHUNKS") ? atoi(getenv("RHO_BM64_MAX_CHUNKS")) : 0; return n; }
+bool splitk_env_on() { static const bool on = env_on("RHO_CONV_SPLITK"); return on; }
 
-static bool m16_env_on() {
-    static const bool on = !(getenv("RHO_CONV_M16") && atoi(getenv("RHO_CONV_M16")) == 0);
-    return on;
-}
-
-static int conv_impl(const rho_conv_desc* dp, void* stream, int64_t* stats_tiles, int64_t* ws_want = nullptr) {
-    if (!dp) return RHO_E_ARG;
-    const rho_conv_desc& d = *dp;
+// The stages of a plan: returns the error of the stage that p.stage names, or 0 with p.stage = ST_DONE
+int conv_plan_stages(const rho_conv_desc& d, ConvPlan& p) {
     if (!d.x1 || !d.w || !d.bias) return RHO_E_ARG;
     if (d.dtype != RHO_F32 && d.dtype != RHO_BF16) return RHO_E_ARG;
     const int CK = d.dtype == RHO_BF16 ? 32 : 16;
@@ -1454,23 +1450,21 @@ static int conv_impl(const rho_conv_desc* dp, void* stream, int64_t* stats_tiles
     if ((d.ph_h || d.phd_h || d.ph_w || d.phd_w) && d.kd * d.kh * d.kw == 1) return RHO_E_ARG;   // (the 1x1x1 path merges the axes)
     if ((d.phd_h || d.phd_w) && (d.kd == 2 || d.pre_a)) return RHO_E_ARG;
 
-    // the 32 -> 32 channel 3x3x3 layers: the persistent register-resident-weights kernel (conv32.h)
-    if (conv32_applies(d)) {
-        if (stats_tiles) { *stats_tiles = conv32_wps(d); return 0; }
-        if (ws_want) { *ws_want = 0; return 0; }
-        if (g_variant != nullptr) { snprintf(g_variant->buf, (size_t)g_variant->cap, "k_conv32<bf16>"); return 0; }
-        if (d.stats && d.split != d.cout) return RHO_E_ARG;
-        return launch_conv32(d, as_stream(stream));
+    p.stage = ST_ROUTE;
+    p.ksplit = 1;
+    // the 32 -> 32 channel 3x3x3 layers: the persistent register-resident-weights kernel (conv32.h); the wide bf16 1x1x1
+    // convolutions without prologue (attention qkv / proj_out, un-folded skips): a plain GEMM (gemm1x1.h)
+    const bool c32 = conv32_applies(d);
+    if (c32 || gemm1x1_applies(d)) {
+        p.kernel = c32 ? K_CONV32 : K_GEMM1X1;
+        p.stats_tiles = c32 ? conv32_wps(d) : gemm1x1_stats_tiles(d);
+        p.stage = ST_DONE;
+        return 0;
     }
 
-    // the wide bf16 1x1x1 convolutions without prologue (attention qkv / proj_out, un-folded skips): a plain GEMM (gemm1x1.h)
-    if (gemm1x1_applies(d)) {
-        if (stats_tiles) { *stats_tiles = gemm1x1_stats_tiles(d); return 0; }
-        if (ws_want) { *ws_want = 0; return 0; }
-        if (g_variant != nullptr) { snprintf(g_variant->buf, (size_t)g_variant->cap, "k_gemm1x1<bf16,256x%d>", G1_BN); return 0; }
-        return launch_gemm1x1(d, as_stream(stream));
-    }
-
+    p.stage = ST_GEOM;
+    const int taps = d.kd * d.kh * d.kw;
+    const bool k111 = d.kd == 1 && d.kh == 1 && d.kw == 1;
     // output extents per sample (padding k/2).  Zero-stuffed input (dgrad of a stride-2 conv): the
     // virtual input and the output both have the forward conv's input extent out_h / out_w.
     const int hv = d.zs_h ? d.out_h : d.h, wv = d.zs_w ? d.out_w : d.w_;   // virtual input extents
@@ -1480,12 +1474,7 @@ static int conv_impl(const rho_conv_desc* dp, void* stream, int64_t* stats_tiles
     const int ho_out = d.ph_h ? 2 * ho : ho, wo_out = d.ph_w ? 2 * wo : wo;
     const int n_phase = (d.ph_h ? 2 : 1) * (d.ph_w ? 2 : 1);
     const int phase_idx = (d.ph_h ? d.ph_h - 1 : 0) * (d.ph_w ? 2 : 1) + (d.ph_w ? d.ph_w - 1 : 0);
-    const int dout = d.d;
-
-    // axes that carry no kernel extent are merged with the batch so tiles stay full:
-    //   1x1x1: everything is one long W axis;  1xkxk: depth*batch is the tile's depth axis.
-    ConvK k{};
-    int gridz = d.n;
+    ConvK& k = p.k;
     // (a 1-tap phased axis sits on the output row: the even parity of a stride-2 conv's forward / data gradient)
     k.pad_h = d.kh == 1 ? 0 : d.ph_h ? 2 - d.ph_h : d.phd_h ? d.phd_h - 1 : d.kh / 2;
     k.pad_w = d.kw == 1 ? 0 : d.ph_w ? 2 - d.ph_w : d.phd_w ? d.phd_w - 1 : d.kw / 2;
@@ -1493,53 +1482,39 @@ static int conv_impl(const rho_conv_desc* dp, void* stream, int64_t* stats_tiles
     k.ix_mul = d.phd_w ? 2 : 1; k.ix_add = d.phd_w ? d.phd_w - 1 : 0;
     k.oy_mul = d.ph_h ? 2 : 1; k.oy_add = d.ph_h ? d.ph_h - 1 : 0;
     k.ox_mul = d.ph_w ? 2 : 1; k.ox_add = d.ph_w ? d.ph_w - 1 : 0;
-    if (d.kd == 1 && d.kh == 1 && d.kw == 1) {
-        if (d.sh != 1 || d.sw != 1 || d.up_h || d.up_w) return RHO_E_ARG;
-        k.D = 1; k.H = 1; k.W = d.n * d.d * d.h * d.w_;
-        k.Do = 1; k.Ho = 1; k.Wo = k.W;
-        gridz = 1;
-    } else if (d.kd == 1) {
-        k.D = d.n * d.d; k.H = hv; k.W = wv;
-        k.Do = k.D; k.Ho = ho; k.Wo = wo;
-        gridz = 1;
-    } else {
-        k.D = d.d; k.H = hv; k.W = wv;
-        k.Do = dout; k.Ho = ho; k.Wo = wo;
-    }
-    k.Hs = k.H; k.Ws = k.W;
-    if (d.zs_h) k.Hs = d.h;
-    if (d.zs_w) k.Ws = d.w_;
-    if (d.phd_h) k.Hs = 2 * d.h;
-    if (d.phd_w) k.Ws = 2 * d.w_;
+    if (k111 && (d.sh != 1 || d.sw != 1 || d.up_h || d.up_w)) return RHO_E_ARG;
+    const int gridz = merge_batch(d, hv, wv, ho, wo, k);
+    k.Hs = d.zs_h ? d.h : d.phd_h ? 2 * d.h : k.H;
+    k.Ws = d.zs_w ? d.w_ : d.phd_w ? 2 * d.w_ : k.W;
     k.zs_h = d.zs_h; k.zs_w = d.zs_w;
     k.y2_cl = d.y2_cl; k.res2 = (const char*)d.res2;
-    if ((long long)d.n * d.d * d.h * d.w_ * (d.phd_h ? 2 : 1) * (d.phd_w ? 2 : 1) >= (1LL << 31) || (long long)d.n * dout * ho_out * wo_out >= (1LL << 31)) return RHO_E_SHAPE;
     k.S_in = (long long)d.d * d.h * d.w_ * (d.phd_h ? 2 : 1) * (d.phd_w ? 2 : 1);
-    k.S_out = (long long)dout * ho_out * wo_out;
-    k.Ho_out = (d.kd == 1 && d.kh == 1 && d.kw == 1) ? 1 : ho_out;
-    k.Wo_out = (d.kd == 1 && d.kh == 1 && d.kw == 1) ? k.Wo : wo_out;
+    k.S_out = (long long)d.d * ho_out * wo_out;
+    if (d.n * k.S_in >= (1LL << 31) || d.n * k.S_out >= (1LL << 31)) return RHO_E_SHAPE;
+    k.Ho_out = k111 ? 1 : ho_out;
+    k.Wo_out = k111 ? k.Wo : wo_out;
 
     // cout tile
     int BM = 32;
     if (d.coutp % 128 == 0 && (d.split % 128 == 0)) BM = 128;
     else if (d.coutp % 64 == 0 && (d.split % 64 == 0)) BM = 64;
+    if (BM == 128 && bm64_max_chunks() > 0 && d.kd == 3 && taps > 1 && cin / CK <= bm64_max_chunks()) BM = 64;
+    VariantKey& v = p.key;
+    v = VariantKey{d.dtype == RHO_BF16, d.kd, d.kh, d.kw, BM, 0, BM == 128 ? 8 : 4, false, false, false};
 
+    // position tile.  The weight ring is sized before the tile is known, for every launch the 16x16x32 layout could take
+    // (bf16, taps a multiple of 3, stride 1, no upsampling); the layout itself also needs the small halo, see below.
     const size_t lds_cap = 160 * 1024;
-    const int taps = d.kd * d.kh * d.kw;
-    {
-        // A/B knob: short contractions (<= N input-channel chunks) on the 4-wave 64-cout tile, two workgroups per CU, instead of the
-        // 8-wave 128-cout tile whose waves all sit in set-up / epilogue at the same time (0 = off)
-        static const int bm64_chunks = getenv("RHO_BM64_MAX_CHUNKS") ? atoi(getenv("RHO_BM64_MAX_CHUNKS")) : 0;
-        if (BM == 128 && bm64_chunks > 0 && d.kd == 3 && taps > 1 && cin / CK <= bm64_chunks) BM = 64;
-    }
-    const bool m16 = d.dtype == RHO_BF16 && taps > 1 && taps % 3 == 0 && d.sh == 1 && d.sw == 1 && !d.up_h && !d.up_w;
-    const int WSLOTS = (taps % 3 == 0) ? ((((BM == 128 && m16) || (RHO_GB_BM32 && BM == 32)) && RHO_GB_WIDE == 3 && taps % 9 == 0) ? 9 : 3) : 2;   // LDS weight-ring depth (matches the kernel's PIPE / RS)
+    const bool m16_geo = v.bf16 && taps > 1 && taps % 3 == 0 && d.sh == 1 && d.sw == 1 && !d.up_h && !d.up_w;
+    const int WSLOTS = (taps % 3 == 0) ? ((((BM == 128 && m16_geo) || (RHO_GB_BM32 && BM == 32)) && RHO_GB_WIDE == 3 && taps % 9 == 0) ? 9 : 3) : 2;   // LDS weight-ring depth (matches the kernel's PIPE / RS)
     int np_cap = (int)((lds_cap - (size_t)WSLOTS * BM * PITCH) / PITCH);
     if (np_cap > 28 * 64) np_cap = 28 * 64;
-    // prefer the small-halo (2 blocks / CU) configuration when it exists
-    TileChoice t = choose_tile(d, k.D, k.Do, k.Ho, k.Wo, 640);
-    if (!t.ok) t = choose_tile(d, k.D, k.Do, k.Ho, k.Wo, np_cap);
+    const TileChoice t = choose_tile_small_first(d, k.Do, k.Ho, k.Wo, np_cap);
     if (!t.ok) return RHO_E_SHAPE;
+    // np = halo positions of the chosen tile -> halo slots per thread: 5 (8 waves) / 10 for np <= 640, else 14 / 28
+    const bool small = t.NP <= 640;
+    v.MAXP = (BM == 128 ? 1 : 2) * (small ? 5 : 14);
+    v.M16 = m16_geo && m16_env_on() && small && BM >= 64;
 
     k.x1 = (const char*)d.x1; k.x2 = (const char*)d.x2; k.pre_a = d.pre_a; k.pre_b = d.pre_b;
     k.w = (const char*)d.w; k.bias = d.bias; k.res = (const char*)d.res; k.res_add = d.res_add;
@@ -1550,18 +1525,14 @@ static int conv_impl(const rho_conv_desc* dp, void* stream, int64_t* stats_tiles
     k.sh = d.sh; k.sw = d.sw; k.up_h = d.up_h; k.up_w = d.up_w; k.pre_silu = d.pre_silu; k.y2_f32 = d.y2_f32;
     k.TD = t.TD; k.TH = t.TH; k.TW = t.TW; k.ID = t.ID; k.IH = t.IH; k.IW = t.IW; k.NP = t.NP;
     k.tiles_h = cdiv(k.Ho, t.TH); k.tiles_w = cdiv(k.Wo, t.TW);
-    k.lgTW = 0; k.lgTH = 0;
-    while ((1 << k.lgTW) < t.TW) ++k.lgTW;
-    while ((1 << k.lgTH) < t.TH) ++k.lgTH;
+    k.lgTW = ilog2(t.TW); k.lgTH = ilog2(t.TH);
     if ((1 << k.lgTW) != t.TW || (1 << k.lgTH) != t.TH) return RHO_E_SHAPE;      // choose_tile only returns powers of two
     k.inv_ihw = 1.0f / (float)(t.IH * t.IW); k.inv_iw = 1.0f / (float)t.IW;
     // 8-wide tiles: pair rows (pd*TH + ph) differing in one bit whose halo offset is 8 (mod 16) positions
     k.pair_lg = -1;
     if (t.TW == 8 && d.sw == 1 && d.sh == 1 && !d.up_h && !d.up_w) {
-        int lgTH = 0;
-        while ((1 << lgTH) < t.TH) ++lgTH;
         for (int b = 0; b < 5 && k.pair_lg < 0; ++b) {
-            const long long delta = (b < lgTH) ? (long long)(1 << b) * t.IW : (long long)(1 << (b - lgTH)) * t.IH * t.IW;
+            const long long delta = (b < k.lgTH) ? (long long)(1 << b) * t.IW : (long long)(1 << (b - k.lgTH)) * t.IH * t.IW;
             if ((1 << b) < t.TD * t.TH && delta % 16 == 8) k.pair_lg = b;
         }
     }
@@ -1570,75 +1541,68 @@ static int conv_impl(const rho_conv_desc* dp, void* stream, int64_t* stats_tiles
     const long long tiles = (long long)cdiv(k.Do, t.TD) * k.tiles_h * k.tiles_w;
     if (tiles > 0x7FFFFFFFLL || d.coutp / BM > 65535 || gridz > 65535) return RHO_E_SHAPE;
     k.cofast = (d.coutp / BM > 1 && tiles % 8 == 0) ? 1 : 0;
-    dim3 grid((unsigned)tiles, (unsigned)(d.coutp / BM), (unsigned)gridz);
+    p.grid = dim3((unsigned)tiles, (unsigned)(d.coutp / BM), (unsigned)gridz);
     // fused output statistics: only where a tile belongs to one sample and the whole output is channels-last
     int64_t tps_geo = 0;                                 // tiles per sample where every tile lies in one sample, else 0
     if (d.kd == 3) tps_geo = tiles * n_phase;            // phases: the launches of one output share the buffer, each its own tile range
     else if (taps == 1 && k.S_out % 256 == 0 && t.TW == 256) tps_geo = k.S_out / 256;
-    const int64_t tps = (d.split == d.cout && d.split > 0) ? tps_geo : 0;
-    if (stats_tiles) { *stats_tiles = tps; return 0; }
+    p.stats_tiles = (d.split == d.cout && d.split > 0) ? tps_geo : 0;
+
+    p.stage = ST_KSPLIT;
     // k-split (rho_conv_desc.ws): merged-batch launches (2-D / 1-D kernels with taps) whose grid leaves most CUs idle
-    int ksplit = 1;
-    const long long positions = (long long)k.Do * k.Ho * k.Wo;
-    {
-        const long long wgs = tiles * (d.coutp / BM);
-        const int chunks = cin / CK;
-        static const bool split_env = !(getenv("RHO_CONV_SPLITK") && atoi(getenv("RHO_CONV_SPLITK")) == 0);
-        if (split_env && d.kd == 1 && (d.split == d.cout || d.y2_cl) && !d.stats && !d.gna_g && wgs <= 128 && chunks >= 4) {
-            int want = (int)(512 / wgs);                               // about two workgroups per CU
-            if (want > 16) want = 16;
-            const int per = taps == 1 ? 4 : 2;                         // chunks per split at least: the set-up of a tile is paid per split
-            if (want > chunks / per) want = chunks / per;
-            if (ws_want) { *ws_want = want >= 2 ? (int64_t)want * positions * d.coutp * (int64_t)sizeof(float) : 0; return 0; }
-            if (d.ws != nullptr && want >= 2) {
-                const long long fit = d.ws_bytes / (positions * d.coutp * (long long)sizeof(float));
-                if (fit < want) want = (int)fit;
-                if (want >= 2) ksplit = want;
-            }
-        } else if (ws_want) { *ws_want = 0; return 0; }
+    p.positions = (long long)k.Do * k.Ho * k.Wo;
+    const long long wgs = tiles * (d.coutp / BM);
+    const int chunks = cin / CK;
+    if (splitk_env_on() && d.kd == 1 && (d.split == d.cout || d.y2_cl) && !d.stats && !d.gna_g && wgs <= 128 && chunks >= 4) {
+        int want = (int)(512 / wgs);                               // about two workgroups per CU
+        if (want > 16) want = 16;
+        const int per = taps == 1 ? 4 : 2;                         // chunks per split at least: the set-up of a tile is paid per split
+        if (want > chunks / per) want = chunks / per;
+        const long long slab_bytes = p.positions * d.coutp * (long long)sizeof(float);
+        if (want >= 2) p.ws_want = want * slab_bytes;
+        if (d.ws != nullptr && want >= 2) {
+            if (d.ws_bytes / slab_bytes < want) want = (int)(d.ws_bytes / slab_bytes);
+            if (want >= 2) p.ksplit = want;
+        }
     }
-    k.ksplit = ksplit; k.slab = (float*)d.ws; k.slab_stride = positions * d.coutp;
-    if (ksplit > 1) grid.z = (unsigned)ksplit;
-    k.stats = nullptr; k.tps = 1;
+    k.ksplit = p.ksplit; k.slab = (float*)d.ws; k.slab_stride = p.positions * d.coutp;
+    if (p.ksplit > 1) p.grid.z = (unsigned)p.ksplit;
+
+    p.stage = ST_ATTACH;
+    k.tps = 1;
     if (d.stats) {
-        if (tps <= 0) return RHO_E_ARG;
-        k.stats = d.stats; k.tps = (int)tps;
+        if (p.stats_tiles <= 0) return RHO_E_ARG;
+        k.stats = d.stats; k.tps = (int)p.stats_tiles;
         k.stats_off = phase_idx * (int)tiles;
     }
-    k.gnb_x1 = nullptr;
-    k.gna_g = nullptr;
     if (d.gna_g) {
         // GroupNorm backward apply in the epilogue: both output regions on the transposed path, one sample per tile
-        const int pe = d.dtype == RHO_BF16 ? 8 : 4;
+        const int pe = v.bf16 ? 8 : 4;
         if (taps != 1 || d.res || d.res2 || d.stats || !d.gnb_x1 || !d.gnb_a || !d.gnb_b || !d.gna_cA || !d.gna_cP || !d.gna_cQ || d.split <= 0 || d.cout % 32 ||
             d.gnb_c1 <= 0 || d.gnb_c1 > d.cout || d.gnb_c1 % 32 || ((d.gnb_c1 < d.cout) != (d.gnb_x2 != nullptr)) || tps_geo <= 0 ||
             (d.split < d.cout && (!d.y2_cl || (d.cout - d.split) % pe != 0)) || d.gnb_silu < 0 || d.gnb_silu > 1 || n_phase != 1)
             return RHO_E_ARG;
-        k.gnb_x1 = (const char*)d.gnb_x1; k.gnb_x2 = (const char*)d.gnb_x2; k.gnb_a = d.gnb_a; k.gnb_b = d.gnb_b;
-        k.gnb_c1 = d.gnb_c1; k.gnb_silu = d.gnb_silu;
         k.gna_g = (const char*)d.gna_g; k.gna_cA = d.gna_cA; k.gna_cP = d.gna_cP; k.gna_cQ = d.gna_cQ;
         k.tps = (int)tps_geo;
     } else if (d.gnb_x1) {
         if (!d.stats || !d.gnb_a || !d.gnb_b || d.gnb_c1 <= 0 || d.gnb_c1 > d.split || d.gnb_c1 % 32 || (d.split - d.gnb_c1) % 32 ||
             ((d.gnb_c1 < d.split) != (d.gnb_x2 != nullptr)))
             return RHO_E_ARG;
+    }
+    if (d.gna_g || d.gnb_x1) {
         k.gnb_x1 = (const char*)d.gnb_x1; k.gnb_x2 = (const char*)d.gnb_x2; k.gnb_a = d.gnb_a; k.gnb_b = d.gnb_b;
         k.gnb_c1 = d.gnb_c1; k.gnb_silu = d.gnb_silu;
     }
     size_t lds = (size_t)t.NP * PITCH + (size_t)WSLOTS * BM * PITCH;
-    k.sk_w = nullptr;
     size_t lds_sk = 0;
     if (d.sk_w) {
         // folded 1x1x1 skip: the 16x16x32 3x3x3 variants only (bf16, stride 1, whole output channels-last, same-size input)
         if (!d.sk_x1 || d.sk_c1 <= 0 || d.sk_c1 % CK || d.sk_c2 < 0 || d.sk_c2 % CK || ((d.sk_c2 > 0) != (d.sk_x2 != nullptr))) return RHO_E_ARG;
-        if (!(m16 && m16_env_on() && d.kd == 3 && d.kh == 3 && d.kw == 3 && t.NP <= 640 && (BM == 64 || BM == 128) && d.split == d.cout &&
-              !d.zs_h && !d.zs_w && !d.ph_h && !d.ph_w && !d.phd_h && !d.phd_w))
-            return RHO_E_ARG;
+        if (!(v.M16 && d.kd == 3 && d.kh == 3 && d.kw == 3 && d.split == d.cout && !d.zs_h && !d.zs_w && !d.ph_h && !d.ph_w && !d.phd_h && !d.phd_w)) return RHO_E_ARG;
         k.sk_x1 = (const char*)d.sk_x1; k.sk_x2 = (const char*)d.sk_x2; k.sk_w = (const char*)d.sk_w; k.sk_bias = d.sk_bias;
         k.sk_c1 = d.sk_c1; k.sk_c2 = d.sk_c2;
         lds_sk = (size_t)2 * 256 * PITCH + (size_t)2 * BM * PITCH;
     }
-    k.coef_off = 0;
     if (taps > 1 && d.kd == 3 && d.pre_a && lds + (size_t)2 * cin * sizeof(float) <= (BM == 128 ? lds_cap : lds_cap / 2)) {
         k.coef_off = (int)lds;                                    // after the halo tile and the weight ring
         lds += (size_t)2 * cin * sizeof(float);
@@ -1650,40 +1614,70 @@ static int conv_impl(const rho_conv_desc* dp, void* stream, int64_t* stats_tiles
     if (d.stats) { const size_t lr = (size_t)(BM == 128 ? 512 : 256) * 16 * sizeof(float); if (lds < lr) lds = lr; }
     const size_t lds_epi = (size_t)256 * (BM * 4 + 16);       // epilogue transpose staging (fp32 rows, all 256 positions at once)
     if ((d.split > 0 || d.y2_cl) && lds < lds_epi) lds = lds_epi;
-    hipStream_t st = as_stream(stream);
-    const bool m16_env = m16_env_on();
-    const int rc = d.dtype == RHO_BF16 ? launch_taps<bf16_raw>(d, k, BM, t.NP, grid, lds, m16 && m16_env, st)
-                                       : launch_taps<float>(d, k, BM, t.NP, grid, lds, false, st);
-    if (rc != 0 || ksplit == 1 || g_variant != nullptr) return rc;
-    const long long items = positions * (d.coutp / 4);
+    p.lds = lds;
+
+    p.stage = ST_KEY;
+    v.FSK = k.sk_w != nullptr; v.GNA = k.gna_g != nullptr;
+    p.fn = conv_kernel(v);
+    if (p.fn == nullptr) {
+        // a tap shape that has only the small-halo tiles (the phase kernels) is a shape error, any other key has no kernel at all
+        VariantKey s = v;
+        s.MAXP = BM == 128 ? 5 : 10;
+        return conv_kernel(s) != nullptr ? RHO_E_SHAPE : RHO_E_ARG;
+    }
+    p.stage = ST_DONE;
+    return 0;
+}
+
+ConvPlan conv_plan(const rho_conv_desc* dp) {
+    ConvPlan p{};             // (stage = ST_DESC)
+    p.rc = dp ? conv_plan_stages(*dp, p) : RHO_E_ARG;
+    return p;
+}
+
+int launch_conv(const rho_conv_desc& d, const ConvPlan& p, hipStream_t st) {
+    if (p.kernel == K_CONV32) return launch_conv32(d, st);
+    if (p.kernel == K_GEMM1X1) return launch_gemm1x1(d, st);
+    const ConvK& k = p.k;
+    const int rc = launch_lds(p.fn, p.grid, dim3(p.key.NW * 64), p.lds, st, k);
+    if (rc != 0 || p.ksplit == 1) return rc;
+    const long long items = p.positions * (d.coutp / 4);
     const dim3 rgrid((unsigned)((items + 255) / 256));
     const SplitMap sm{k.Ho, k.Wo, k.Ho_out, k.Wo_out, k.oy_mul, k.oy_add, k.ox_mul, k.ox_add};
     const SplitOut so{d.cout, d.coutp, d.split, d.bias, d.res_add, (long long)k.res_add_stride, k.S_out, (const char*)d.res, (char*)d.y,
                       (const char*)d.res2, (char*)d.y2};
-    if (d.dtype == RHO_BF16) hipLaunchKernelGGL(k_splitk_reduce<bf16_raw>, rgrid, dim3(256), 0, st, k.slab, k.slab_stride, ksplit, positions, so, sm);
-    else hipLaunchKernelGGL(k_splitk_reduce<float>, rgrid, dim3(256), 0, st, k.slab, k.slab_stride, ksplit, positions, so, sm);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    if (d.dtype == RHO_BF16) hipLaunchKernelGGL(k_splitk_reduce<bf16_raw>, rgrid, dim3(256), 0, st, k.slab, k.slab_stride, p.ksplit, p.positions, so, sm);
+    else hipLaunchKernelGGL(k_splitk_reduce<float>, rgrid, dim3(256), 0, st, k.slab, k.slab_stride, p.ksplit, p.positions, so, sm);
+    return hip_status();
 }
 
-extern "C" int64_t rho_conv_workspace_bytes(const rho_conv_desc* dp) {
-    int64_t b = 0;
-    return conv_impl(dp, nullptr, nullptr, &b) == 0 ? b : 0;
+}  // namespace
+
+extern "C" int rho_conv_nd_fwd(const rho_conv_desc* dp, void* stream) {
+    const ConvPlan p = conv_plan(dp);
+    return p.rc != 0 ? p.rc : launch_conv(*dp, p, as_stream(stream));
 }
 
-extern "C" int rho_conv_nd_fwd(const rho_conv_desc* dp, void* stream) { return conv_impl(dp, stream, nullptr); }
-
+// The name of what rho_conv_nd_fwd launches, formatted from the plan's key
 extern "C" int rho_conv_variant(const rho_conv_desc* dp, char* buf, int cap) {
     if (!buf || cap < 64) return RHO_E_ARG;
     buf[0] = 0;
-    VariantOut vo{buf, cap};
-    g_variant = &vo;
-    const int rc = conv_impl(dp, nullptr, nullptr);
-    g_variant = nullptr;
-    return rc;
+    const ConvPlan p = conv_plan(dp);
+    const VariantKey& v = p.key;
+    if (p.rc != 0) return p.rc;
+    if (p.kernel == K_CONV32) snprintf(buf, (size_t)cap, "k_conv32<bf16>");
+    else if (p.kernel == K_GEMM1X1) snprintf(buf, (size_t)cap, "k_gemm1x1<bf16,256x%d>", G1_BN);
+    else snprintf(buf, (size_t)cap, "k_conv<%s,%d,%d,%d,BM=%d,MAXP=%d,NW=%d,M16=%d>%s%s", v.bf16 ? "bf16" : "f32", v.kd, v.kh, v.kw, v.BM,
+                  v.MAXP, v.NW, (int)v.M16, v.FSK ? "+skip" : "", v.GNA ? "+gn_apply" : "");
+    return 0;
 }
 
 extern "C" int64_t rho_conv_stats_tiles(const rho_conv_desc* dp) {
-    int64_t t = 0;
-    return conv_impl(dp, nullptr, &t) == 0 ? t : 0;
+    const ConvPlan p = conv_plan(dp);
+    return p.status(ST_GEOM) == 0 ? p.stats_tiles : 0;
+}
+
+extern "C" int64_t rho_conv_workspace_bytes(const rho_conv_desc* dp) {
+    const ConvPlan p = conv_plan(dp);
+    return p.status(ST_KSPLIT) == 0 ? p.ws_want : 0;
 }

@@ -1,5 +1,7 @@
 // Pieces shared by the forward/dgrad convolution (conv.hip) and the weight-gradient kernel (wgrad.hip).
 #pragma once
+#include <cstdlib>
+
 #include "common.h"
 
 #define PITCH 80  // bytes per LDS row (64 payload + 16 pad)
@@ -114,9 +116,57 @@ struct TileChoice {
 };
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+inline int ilog2(int v) {          // ceil(log2(v))
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return l;
+}
+
+// A plan (conv.hip, wgrad.hip) runs its stages in order and the first failure ends it: rc is the error of stage `stage`
+template <class S>
+struct PlanStatus {
+    int rc;
+    S stage;
+    int status(S s) const { return stage <= s ? rc : 0; }      // the error, if the plan failed in stage s or before it
+};
+
+inline int hip_status() {          // 0, or the error the last launch left behind
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+// fn<<<grid, block, lds, st>>>(arg), raising the kernel's limit where it asks for more than 64 KiB of dynamic LDS
+template <class K>
+inline int launch_lds(void (*fn)(const K), dim3 grid, dim3 block, size_t lds, hipStream_t st, const K& arg) {
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(fn, grid, block, lds, st, arg);
+    return hip_status();
+}
+
+inline bool env_on(const char* name) {          // a switch of the environment: on unless set to 0
+    const char* e = getenv(name);
+    return !(e && atoi(e) == 0);
+}
+
+// Axes that carry no kernel extent are merged with the batch so tiles stay full: 1x1x1: everything is one long W axis; 1xkxk:
+// depth * batch is the tile's depth axis.  Sets the input extents (hv x wv per depth slice) and the output extents (ho x wo) of a
+// ConvK / WgradK and returns the batch that is left for the grid.
+template <class K>
+inline int merge_batch(const rho_conv_desc& d, int hv, int wv, int ho, int wo, K& k) {
+    if (d.kd == 1 && d.kh == 1 && d.kw == 1) {
+        k.D = 1; k.H = 1; k.W = (int)((long long)d.n * d.d * d.h * d.w_);      // (the callers refuse 2^31 positions and more)
+        k.Do = 1; k.Ho = 1; k.Wo = k.W;
+        return 1;
+    }
+    k.D = d.kd == 1 ? d.n * d.d : d.d; k.H = hv; k.W = wv;
+    k.Do = k.D; k.Ho = ho; k.Wo = wo;
+    return d.kd == 1 ? 1 : d.n;
+}
 
 // pick the 256-position output tile: fewest tiles first, then the smallest halo, then the widest W
-inline TileChoice choose_tile(const rho_conv_desc& d, int Dm, int Do, int Ho, int Wo, int np_cap) {
+inline TileChoice choose_tile(const rho_conv_desc& d, int Do, int Ho, int Wo, int np_cap) {
     TileChoice best{};
     best.ok = false;
     double best_cost = 1e300;
@@ -138,9 +188,12 @@ inline TileChoice choose_tile(const rho_conv_desc& d, int Dm, int Do, int Ho, in
                 best = TileChoice{TD, TH, TW, ID, IH, IW, NP, tiles, true};
             }
         }
-    (void)Dm;
     return best;
 }
-
+// ... preferring the small-halo configuration (<= 640 halo positions: two workgroups per CU) where one exists
+inline TileChoice choose_tile_small_first(const rho_conv_desc& d, int Do, int Ho, int Wo, int np_cap) {
+    const TileChoice t = choose_tile(d, Do, Ho, Wo, 640);
+    return t.ok ? t : choose_tile(d, Do, Ho, Wo, np_cap);
+}
 
 }  // namespace rho_conv

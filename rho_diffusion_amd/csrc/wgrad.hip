@@ -1029,88 +1029,202 @@ __global__ __launch_bounds__(256) void k_wgrad1(const WgradK p, long long npos, 
 namespace {
 using namespace rho_conv;
 
-struct VariantOut {
-    char* buf;
-    int cap;
+// One weight-gradient launch, planned on the host from the descriptor and dy_width alone (as ConvPlan in conv.hip): both launch
+// forms and the two queries read it.  The stages run in this order and the first failure ends the plan:
+enum WStage {
+    WS_DESC,     // 1  descriptor validation
+    WS_GEOM,     // 2  geometry; k_wgrad1 or k_wgrad; tile, position slabs, grid, LDS bytes
+    WS_SLABS,    // 3  slabs of the deterministic flush                -> rho_conv_wgrad_workspace_bytes
+    WS_KEY,      // 4  variant key and its instantiation               -> rho_conv_wgrad_variant, the launches
+    WS_DONE
 };
-thread_local VariantOut* g_wvariant = nullptr;      // see rho_conv_variant (conv.hip)
+struct WgradKey { bool bf16; int kd, kh, kw, MAXP; bool PRE, GEO; };      // one instantiation of k_wgrad
+using WgradFn = void (*)(const WgradK);
+struct WgradPlan : PlanStatus<WStage> {
+    bool gemm;               // k_wgrad1 (bf16 1x1x1 without prologue) instead of k_wgrad<key>
+    WgradKey key;
+    WgradFn fn;
+    WgradK k;                // (dy, dw, dbias and slab belong to the launch)
+    dim3 grid;
+    size_t lds;
+    long long npos;          // positions of the input
+    int tiles_total, tiles_per_block;
+    int nslab;               // slabs of the deterministic flush, k.slab_stride floats each
+    long long nw;            // floats of dw
+    int64_t ws_bytes() const { return (int64_t)nslab * k.slab_stride * (int64_t)sizeof(float); }
+};
 
+// key -> instantiation; nullptr for a key that has none
 template <typename T, int KD, int KH, int KW>
-int launch_wgrad(const WgradK& k, int maxp, dim3 grid, size_t lds, hipStream_t st) {
-    // the compile-time tile geometry of k_wgrad<..., GEO = 1>
-    const bool geo488 = k.TD == 4 && k.TH == 8 && k.TW == 8 && k.IH == 10 && k.IW == 10 && k.sh == 1 && k.sw == 1;
-    if (g_wvariant != nullptr) {
-        snprintf(g_wvariant->buf, (size_t)g_wvariant->cap, "k_wgrad<%s,%d,%d,%d,MAXP=%d,PRE=%d%s>", sizeof(T) == 2 ? "bf16" : "f32", KD, KH,
-                 KW, maxp <= 10 ? 10 : 28, k.pre_a != nullptr ? 1 : 0,
-                 (geo488 && sizeof(T) == 2 && KD == 3 && KH == 3 && KW == 3 && maxp <= 10 && k.pre_a == nullptr) ? ",GEO=1" : "");
-        return 0;
+WgradFn wgrad_kernel_taps(const WgradKey& v) {
+    if constexpr (KH == 2 || KW == 2) {      // sub-pixel phases: stride 1, small halo, no prologue
+        return (v.MAXP == 10 && !v.PRE && !v.GEO) ? k_wgrad<T, KD, KH, KW, 10, false> : nullptr;
     }
-    auto go = [&](auto fn) -> int {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(fn, grid, dim3(256), lds, st, k);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : (int)e;
-    };
-    const bool pre = k.pre_a != nullptr;
-    if constexpr (KH == 2 || KW == 2) {      // sub-pixel phases: stride 1, small halo, no prologue (checked by the caller)
-        if (maxp > 10 || pre) return RHO_E_SHAPE;
-        return go(k_wgrad<T, KD, KH, KW, 10, false>);
+    // (deliberately no `else`: the lines below stay instantiated for the phase shapes too, so the library keeps its set of kernels)
+    if (v.GEO) {                             // the compile-time tile geometry (4 x 8 x 8, stride 1) of the bf16 3x3x3 layers
+        if constexpr (sizeof(T) == 2 && KD == 3 && KH == 3 && KW == 3) { if (v.MAXP == 10 && !v.PRE) return k_wgrad<T, KD, KH, KW, 10, false, 1>; }
+        return nullptr;
     }
-    if constexpr (sizeof(T) == 2 && KD == 3 && KH == 3 && KW == 3) {
-        if (geo488 && !pre && maxp <= 10) return go(k_wgrad<T, KD, KH, KW, 10, false, 1>);
-    }
-    if (maxp <= 10) return pre ? go(k_wgrad<T, KD, KH, KW, 10, true>) : go(k_wgrad<T, KD, KH, KW, 10, false>);
-    return pre ? go(k_wgrad<T, KD, KH, KW, 28, true>) : go(k_wgrad<T, KD, KH, KW, 28, false>);
+    if (v.MAXP == 10) return v.PRE ? k_wgrad<T, KD, KH, KW, 10, true> : k_wgrad<T, KD, KH, KW, 10, false>;
+    if (v.MAXP == 28) return v.PRE ? k_wgrad<T, KD, KH, KW, 28, true> : k_wgrad<T, KD, KH, KW, 28, false>;
+    return nullptr;
 }
-
 template <typename T>
-int launch_wgrad_taps(const rho_conv_desc& d, const WgradK& k, int maxp, dim3 grid, size_t lds, hipStream_t st) {
-    if (d.kd == 3 && d.kh == 3 && d.kw == 3) return launch_wgrad<T, 3, 3, 3>(k, maxp, grid, lds, st);
-    if (d.kd == 1 && d.kh == 3 && d.kw == 3) return launch_wgrad<T, 1, 3, 3>(k, maxp, grid, lds, st);
-    if (d.kd == 1 && d.kh == 1 && d.kw == 3) return launch_wgrad<T, 1, 1, 3>(k, maxp, grid, lds, st);
-    if (d.kd == 1 && d.kh == 1 && d.kw == 1) return launch_wgrad<T, 1, 1, 1>(k, maxp, grid, lds, st);
-    // sub-pixel phases of a conv behind a nearest x2 upsample
-    if (d.kd == 3 && d.kh == 2 && d.kw == 2) return launch_wgrad<T, 3, 2, 2>(k, maxp, grid, lds, st);
-    if (d.kd == 1 && d.kh == 2 && d.kw == 2) return launch_wgrad<T, 1, 2, 2>(k, maxp, grid, lds, st);
-    if (d.kd == 1 && d.kh == 1 && d.kw == 2) return launch_wgrad<T, 1, 1, 2>(k, maxp, grid, lds, st);
-    return RHO_E_ARG;
+WgradFn wgrad_kernel(const WgradKey& v) {
+    if (v.kd < 1 || v.kd > 3 || v.kh < 1 || v.kh > 3 || v.kw < 1 || v.kw > 3) return nullptr;
+    switch (v.kd * 100 + v.kh * 10 + v.kw) {
+        case 333: return wgrad_kernel_taps<T, 3, 3, 3>(v);
+        case 133: return wgrad_kernel_taps<T, 1, 3, 3>(v);
+        case 113: return wgrad_kernel_taps<T, 1, 1, 3>(v);
+        case 111: return wgrad_kernel_taps<T, 1, 1, 1>(v);
+        // sub-pixel phases of a conv behind a nearest x2 upsample
+        case 322: return wgrad_kernel_taps<T, 3, 2, 2>(v);
+        case 122: return wgrad_kernel_taps<T, 1, 2, 2>(v);
+        case 112: return wgrad_kernel_taps<T, 1, 1, 2>(v);
+    }
+    return nullptr;
 }
+WgradFn wgrad_kernel(const WgradKey& v) { return v.bf16 ? wgrad_kernel<bf16_raw>(v) : wgrad_kernel<float>(v); }
 
-inline int ilog2(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
+// the only runtime call of the planning side, once per process (256 CUs where there is no device to ask)
+int n_cu() {
+    static const int n = []() { hipDeviceProp_t pr; int dev = 0; return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
+    return n;
 }
-}  // namespace
+bool xcd_env_on() { static const bool on = env_on("RHO_WGRAD_XCD"); return on; }
 
+// The stages of a plan: returns the error of the stage that p.stage names, or 0 with p.stage = WS_DONE.
 // desc describes the FORWARD convolution (x1/x2, prologue, geometry); dy is its output gradient
 // (channels-last, row width dy_width >= cout, extra channels must be zero); dw is an fp32 buffer
-// [taps][coutp][c1+c2] that this call ACCUMULATES into (zero it first).  up_h/up_w are not supported:
+// [taps][coutp][c1+c2] that the launch ACCUMULATES into (zero it first).  up_h/up_w are not supported:
 // materialise the upsampled input (rho_upsample2x) and pass it as x1.
-static int wgrad_impl(const rho_conv_desc* dp, const void* dy, int64_t dy_width, float* dw, float* dbias, void* stream,
-                      float* ws = nullptr, int64_t ws_bytes = 0, int64_t* ws_want = nullptr);
+int wgrad_plan_stages(const rho_conv_desc& d, int64_t dy_width, WgradPlan& p) {
+    if (!d.x1) return RHO_E_ARG;
+    if (d.dtype != RHO_F32 && d.dtype != RHO_BF16) return RHO_E_ARG;
+    if (d.up_h || d.up_w || d.zs_h || d.zs_w) return RHO_E_ARG;
+    const bool bf16 = d.dtype == RHO_BF16;
+    const int CK = bf16 ? 32 : 16;
+    const int PE = bf16 ? 8 : 4;
+    const int COT = bf16 ? 64 : 32;
+    const int c2 = d.x2 ? d.c2 : 0;
+    const int cin = d.c1 + c2;
+    if (d.c1 <= 0 || d.c1 % CK || c2 % CK) return RHO_E_ALIGN;
+    if (dy_width <= 0 || dy_width % PE || d.coutp <= 0 || d.coutp % 32) return RHO_E_ALIGN;
+    if ((d.sh != 1 && d.sh != 2) || (d.sw != 1 && d.sw != 2)) return RHO_E_ARG;
+    if (d.pre_a && !d.pre_b) return RHO_E_ARG;
+    if (d.phd_h || d.phd_w || d.ph_h < 0 || d.ph_h > 2 || d.ph_w < 0 || d.ph_w > 2) return RHO_E_ARG;
+    if ((d.ph_h && (d.kh != 2 || d.sh != 1)) || (d.ph_w && (d.kw != 2 || d.sw != 1)) || (!d.ph_h && d.kh == 2) || (!d.ph_w && d.kw == 2) ||
+        ((d.ph_h || d.ph_w) && (d.pre_a || d.kd == 2)))
+        return RHO_E_ARG;
 
-extern "C" int rho_conv_nd_wgrad(const rho_conv_desc* dp, const void* dy, int64_t dy_width, float* dw, float* dbias, void* stream) {
-    if (!dp || !dy || !dw) return RHO_E_ARG;
-    return wgrad_impl(dp, dy, dy_width, dw, dbias, stream);
+    p.stage = WS_GEOM;
+    // (phases: the launch's output grid is the source grid; dY is the full-resolution gradient, read at one parity)
+    const int ho = d.ph_h ? d.h : (d.h + 2 * (d.kh / 2) - d.kh) / d.sh + 1;
+    const int wo = d.ph_w ? d.w_ : (d.w_ + 2 * (d.kw / 2) - d.kw) / d.sw + 1;
+    const int nt = d.kd * d.kh * d.kw;
+    const bool k111 = d.kd == 1 && d.kh == 1 && d.kw == 1;
+    WgradK& k = p.k;
+    k.pad_h = d.ph_h ? 2 - d.ph_h : d.kh / 2; k.pad_w = d.ph_w ? 2 - d.ph_w : d.kw / 2;
+    k.oy_mul = d.ph_h ? 2 : 1; k.oy_add = d.ph_h ? d.ph_h - 1 : 0;
+    k.ox_mul = d.ph_w ? 2 : 1; k.ox_add = d.ph_w ? d.ph_w - 1 : 0;
+    if (k111 && (d.sh != 1 || d.sw != 1)) return RHO_E_ARG;
+    const int nb = merge_batch(d, d.h, d.w_, ho, wo, k);
+    p.npos = (long long)d.n * d.d * d.h * d.w_;
+    if (p.npos * k.oy_mul * k.ox_mul >= (1LL << 31)) return RHO_E_SHAPE;
+    k.S_in = (long long)d.d * d.h * d.w_;
+    k.Ho_out = k.Ho * k.oy_mul; k.Wo_out = k.Wo * k.ox_mul;
+
+    // the workgroup grid: position slabs x cout tiles x input-channel chunks
+    p.gemm = bf16 && k111 && !d.pre_a;
+    int splits, gy, gz;
+    if (p.gemm) {
+        // 1x1x1 without prologue: the GEMM-shaped kernel on 128-position tiles, with an argument block of its own
+        k = WgradK{};
+        p.tiles_total = (int)((p.npos + 127) / 128);
+        gy = cdiv(d.coutp, 64); gz = cdiv(cin, 128);
+        splits = cdiv(1536, gy * gz);
+        if (splits >= 8) splits &= ~7;
+        p.lds = (size_t)(4 * 128 * XP + 128 * DYP);
+    } else {
+        const size_t lds_cap = 160 * 1024;
+        int np_cap = (int)((lds_cap - 256 * DYP) / XP);
+        if (np_cap > 28 * 64) np_cap = 28 * 64;
+        const TileChoice t = choose_tile_small_first(d, k.Do, k.Ho, k.Wo, np_cap);
+        if (!t.ok) return RHO_E_SHAPE;
+        k.pre_a = d.pre_a; k.pre_b = d.pre_b;
+        k.sh = d.sh; k.sw = d.sw; k.pre_silu = d.pre_silu;
+        k.TD = t.TD; k.TH = t.TH; k.TW = t.TW; k.ID = t.ID; k.IH = t.IH; k.IW = t.IW; k.NP = t.NP;
+        k.lgTW = ilog2(t.TW); k.lgTH = ilog2(t.TH);
+        k.tiles_d = cdiv(k.Do, t.TD); k.tiles_h = cdiv(k.Ho, t.TH); k.tiles_w = cdiv(k.Wo, t.TW);
+        k.n_batch = nb;
+        const long long tiles = (long long)nb * k.tiles_d * k.tiles_h * k.tiles_w;
+        if (tiles > 0x7FFFFFFFLL) return RHO_E_SHAPE;
+        p.tiles_total = (int)tiles;
+        // enough workgroups to fill 256 CUs, long enough slabs to amortise the 27x64x32 fp32 flush
+        // One workgroup per CU (144 KB of LDS) and equal slabs: the launch runs in rounds of n_cu workgroups.  Pick the slab count so
+        // that splits x pairs fills 3..6 whole rounds (was ceil(1024 / pairs): 6 pairs -> 1026 workgroups = a fifth round of two,
+        // 20 % of the launch, on every layer whose channel count is 3 * 2^k - the concatenated inputs of the output blocks).
+        // f32 1x1x1: a workgroup takes two input-channel chunks (k_wgrad's PAIRC), so the chunk axis of the grid halves
+        const bool pairc = !bf16 && nt == 1 && t.NP == 256 && cdiv(t.NP, 64) <= 10;
+        k.pairc = pairc ? 1 : 0;
+        gy = cdiv(d.coutp, COT); gz = pairc ? cdiv(cin / CK, 2) : cin / CK;
+        const int pairs = gy * gz, ncu = n_cu();
+        splits = cdiv(4 * ncu, pairs);
+        double best = -1.0;
+        static const int r_lo = getenv("RHO_WGRAD_ROUNDS_MIN") ? atoi(getenv("RHO_WGRAD_ROUNDS_MIN")) : 3;      // (A/B knobs)
+        static const int r_hi = getenv("RHO_WGRAD_ROUNDS_MAX") ? atoi(getenv("RHO_WGRAD_ROUNDS_MAX")) : 6;
+        for (int r = r_lo; r <= r_hi; ++r) {
+            int sp = (r * ncu) / pairs;
+            if (sp >= 8) sp &= ~7;                 // multiples of 8: the slab -> XCD map of the kernel needs whole groups of 8 slabs
+            if (sp < 1) continue;
+            const long long total = (long long)sp * pairs;
+            const double eff = (double)total / (double)(cdiv((int)total, ncu) * ncu) - 0.002 * (r > 4 ? r - 4 : 4 - r) * (r_lo == 3 && r_hi == 6 ? 1.0 : 0.0);
+            if (eff > best) { best = eff; splits = sp; }
+        }
+        // halo slots per thread, prologue and the compile-time tile geometry of k_wgrad<..., GEO = 1>: the variant's key
+        WgradKey& v = p.key;
+        v = WgradKey{bf16, d.kd, d.kh, d.kw, cdiv(t.NP, 64) <= 10 ? 10 : 28, d.pre_a != nullptr, false};
+        v.GEO = bf16 && d.kd == 3 && d.kh == 3 && d.kw == 3 && v.MAXP == 10 && !v.PRE && t.TD == 4 && t.TH == 8 && t.TW == 8 && t.IH == 10 && t.IW == 10 &&
+                d.sh == 1 && d.sw == 1;
+        p.lds = (size_t)v.MAXP * 64 * XP + 256 * DYP;
+        if (v.MAXP == 10 && !v.PRE) p.lds *= 2;   // LDS-DMA path (both dtypes since round 3): double-buffered tiles (2 x 72 KB)
+    }
+    k.x1 = (const char*)d.x1; k.x2 = (const char*)d.x2;
+    k.c1 = d.c1; k.c2 = c2; k.cin = cin; k.dyw = (int)dy_width; k.coutp = d.coutp;
+    // equal slabs of whole tiles
+    if (splits < 1) splits = 1;
+    if (splits > p.tiles_total) splits = p.tiles_total;
+    p.tiles_per_block = cdiv(p.tiles_total, splits);
+    splits = cdiv(p.tiles_total, p.tiles_per_block);
+    if (!p.gemm) { k.tiles_total = p.tiles_total; k.tiles_per_block = p.tiles_per_block; }      // (k_wgrad1 takes them as arguments)
+    if (gy > 65535 || gz > 65535) return RHO_E_SHAPE;
+    p.grid = dim3((unsigned)splits, (unsigned)gy, (unsigned)gz);
+    k.xcd_map = (xcd_env_on() && splits % 8 == 0 && (long long)splits * (gy * gz) < (1LL << 31)) ? 1 : 0;
+
+    p.stage = WS_SLABS;
+    // deterministic flush: one slab per accumulator owner (k_wgrad's TAPSPLIT decides whether that is the workgroup or the wave)
+    const bool tapsplit = bf16 ? (nt >= 9) : (nt > 9);
+    p.nslab = splits * (p.gemm || tapsplit ? 1 : 4);
+    p.nw = (long long)nt * d.coutp * cin;
+    k.slab_bias_off = p.nw; k.slab_stride = p.nw + d.coutp;
+
+    p.stage = WS_KEY;
+    if (!p.gemm && (p.fn = wgrad_kernel(p.key)) == nullptr) {
+        // a phase shape with a large halo or a prologue is a shape error, any other key has no kernel at all
+        const WgradKey s{bf16, d.kd, d.kh, d.kw, 10, false, false};
+        return wgrad_kernel(s) != nullptr ? RHO_E_SHAPE : RHO_E_ARG;
+    }
+    p.stage = WS_DONE;
+    return 0;
 }
 
-// Deterministic form: the same launch, flushed through ordered slabs in `ws` instead of fp32 atomics (bit-reproducible run to run
-// and across data-parallel replicas).  ws must hold rho_conv_wgrad_workspace_bytes(desc, dy_width) bytes; it is scratch.
-extern "C" int rho_conv_nd_wgrad_ws(const rho_conv_desc* dp, const void* dy, int64_t dy_width, float* dw, float* dbias, void* ws,
-                                    int64_t ws_bytes, void* stream) {
-    if (!dp || !dy || !dw || !ws || ws_bytes <= 0) return RHO_E_ARG;
-    return wgrad_impl(dp, dy, dy_width, dw, dbias, stream, (float*)ws, ws_bytes);
+WgradPlan wgrad_plan(const rho_conv_desc* dp, int64_t dy_width) {
+    WgradPlan p{};            // (stage = WS_DESC)
+    p.rc = dp ? wgrad_plan_stages(*dp, dy_width, p) : RHO_E_ARG;
+    return p;
 }
 
-extern "C" int64_t rho_conv_wgrad_workspace_bytes(const rho_conv_desc* dp, int64_t dy_width) {
-    if (!dp) return 0;
-    int64_t b = 0;
-    return wgrad_impl(dp, nullptr, dy_width, nullptr, nullptr, nullptr, nullptr, 0, &b) == 0 ? b : 0;
-}
+}  // namespace
 
 // dw[i] (+ dbias) += slab[0][i] + slab[1][i] + ... in slab order: the fixed summation order of the deterministic flush
 __global__ __launch_bounds__(256) void k_wgrad_slab_reduce(const float* __restrict__ slab, int nslab, long long stride, float* __restrict__ dw,
@@ -1125,169 +1239,50 @@ __global__ __launch_bounds__(256) void k_wgrad_slab_reduce(const float* __restri
     }
 }
 
-static int launch_slab_reduce(const float* ws, int nslab, long long stride, float* dw, long long nw, float* dbias, int nb, hipStream_t st) {
-    long long g = (nw + nb + 255) / 256;
+// Both launch forms: fp32 atomics into dw / dbias, or (ws) ordered slabs and their reduction
+static int launch_wgrad(const rho_conv_desc* dp, const void* dy, int64_t dy_width, float* dw, float* dbias, float* ws, int64_t ws_bytes, hipStream_t st) {
+    WgradPlan p = wgrad_plan(dp, dy_width);
+    if (p.status(WS_SLABS) == 0 && ws && ws_bytes < p.ws_bytes()) return RHO_E_ARG;      // (reported before a key without a kernel)
+    if (p.rc != 0) return p.rc;
+    WgradK& k = p.k;
+    k.dy = (const char*)dy; k.dw = dw; k.dbias = dbias; k.slab = ws;
+    if (p.gemm) hipLaunchKernelGGL(k_wgrad1, p.grid, dim3(256), p.lds, st, k, p.npos, p.tiles_total, p.tiles_per_block);
+    const int rc = p.gemm ? hip_status() : launch_lds(p.fn, p.grid, dim3(256), p.lds, st, k);
+    if (rc != 0 || !ws) return rc;
+    long long g = (p.nw + k.coutp + 255) / 256;
     if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(k_wgrad_slab_reduce, dim3((unsigned)g), dim3(256), 0, st, ws, nslab, stride, dw, nw, dbias, nb);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    hipLaunchKernelGGL(k_wgrad_slab_reduce, dim3((unsigned)g), dim3(256), 0, st, ws, p.nslab, k.slab_stride, dw, p.nw, dbias, k.coutp);
+    return hip_status();
 }
 
+extern "C" int rho_conv_nd_wgrad(const rho_conv_desc* dp, const void* dy, int64_t dy_width, float* dw, float* dbias, void* stream) {
+    if (!dp || !dy || !dw) return RHO_E_ARG;
+    return launch_wgrad(dp, dy, dy_width, dw, dbias, nullptr, 0, as_stream(stream));
+}
+
+// Deterministic form: the same launch, flushed through ordered slabs in `ws` instead of fp32 atomics (bit-reproducible run to run
+// and across data-parallel replicas).  ws must hold rho_conv_wgrad_workspace_bytes(desc, dy_width) bytes; it is scratch.
+extern "C" int rho_conv_nd_wgrad_ws(const rho_conv_desc* dp, const void* dy, int64_t dy_width, float* dw, float* dbias, void* ws,
+                                    int64_t ws_bytes, void* stream) {
+    if (!dp || !dy || !dw || !ws || ws_bytes <= 0) return RHO_E_ARG;
+    return launch_wgrad(dp, dy, dy_width, dw, dbias, (float*)ws, ws_bytes, as_stream(stream));
+}
+
+extern "C" int64_t rho_conv_wgrad_workspace_bytes(const rho_conv_desc* dp, int64_t dy_width) {
+    const WgradPlan p = wgrad_plan(dp, dy_width);
+    return p.status(WS_SLABS) == 0 ? p.ws_bytes() : 0;
+}
+
+// The name of what the launches run, formatted from the plan's key
 extern "C" int rho_conv_wgrad_variant(const rho_conv_desc* dp, int64_t dy_width, char* buf, int cap) {
     if (!dp || !buf || cap < 64) return RHO_E_ARG;
     buf[0] = 0;
-    VariantOut vo{buf, cap};
-    g_wvariant = &vo;
-    const int rc = wgrad_impl(dp, nullptr, dy_width, nullptr, nullptr, nullptr);
-    g_wvariant = nullptr;
-    return rc;
-}
-
-static int wgrad_impl(const rho_conv_desc* dp, const void* dy, int64_t dy_width, float* dw, float* dbias, void* stream, float* ws,
-                      int64_t ws_bytes, int64_t* ws_want) {
-    const rho_conv_desc& d = *dp;
-    if (!d.x1) return RHO_E_ARG;
-    if (d.dtype != RHO_F32 && d.dtype != RHO_BF16) return RHO_E_ARG;
-    if (d.up_h || d.up_w || d.zs_h || d.zs_w) return RHO_E_ARG;
-    const int CK = d.dtype == RHO_BF16 ? 32 : 16;
-    const int PE = d.dtype == RHO_BF16 ? 8 : 4;
-    const int COT = d.dtype == RHO_BF16 ? 64 : 32;
-    const int c2 = d.x2 ? d.c2 : 0;
-    const int cin = d.c1 + c2;
-    if (d.c1 <= 0 || d.c1 % CK || c2 % CK) return RHO_E_ALIGN;
-    if (dy_width <= 0 || dy_width % PE || d.coutp <= 0 || d.coutp % 32) return RHO_E_ALIGN;
-    if ((d.sh != 1 && d.sh != 2) || (d.sw != 1 && d.sw != 2)) return RHO_E_ARG;
-    if (d.pre_a && !d.pre_b) return RHO_E_ARG;
-
-    if (d.phd_h || d.phd_w || d.ph_h < 0 || d.ph_h > 2 || d.ph_w < 0 || d.ph_w > 2) return RHO_E_ARG;
-    if ((d.ph_h && (d.kh != 2 || d.sh != 1)) || (d.ph_w && (d.kw != 2 || d.sw != 1)) || (!d.ph_h && d.kh == 2) || (!d.ph_w && d.kw == 2) ||
-        ((d.ph_h || d.ph_w) && (d.pre_a || d.kd == 2)))
-        return RHO_E_ARG;
-    // (phases: the launch's output grid is the source grid; dY is the full-resolution gradient, read at one parity)
-    const int ho = d.ph_h ? d.h : (d.h + 2 * (d.kh / 2) - d.kh) / d.sh + 1;
-    const int wo = d.ph_w ? d.w_ : (d.w_ + 2 * (d.kw / 2) - d.kw) / d.sw + 1;
-    WgradK k{};
-    k.pad_h = d.ph_h ? 2 - d.ph_h : d.kh / 2; k.pad_w = d.ph_w ? 2 - d.ph_w : d.kw / 2;
-    k.oy_mul = d.ph_h ? 2 : 1; k.oy_add = d.ph_h ? d.ph_h - 1 : 0;
-    k.ox_mul = d.ph_w ? 2 : 1; k.ox_add = d.ph_w ? d.ph_w - 1 : 0;
-    int nb = d.n;
-    if (d.kd == 1 && d.kh == 1 && d.kw == 1) {
-        if (d.sh != 1 || d.sw != 1) return RHO_E_ARG;
-        k.D = 1; k.H = 1; k.W = d.n * d.d * d.h * d.w_;
-        k.Do = 1; k.Ho = 1; k.Wo = k.W;
-        nb = 1;
-    } else if (d.kd == 1) {
-        k.D = d.n * d.d; k.H = d.h; k.W = d.w_;
-        k.Do = k.D; k.Ho = ho; k.Wo = wo;
-        nb = 1;
-    } else {
-        k.D = d.d; k.H = d.h; k.W = d.w_;
-        k.Do = d.d; k.Ho = ho; k.Wo = wo;
-    }
-    if ((long long)d.n * d.d * d.h * d.w_ * k.oy_mul * k.ox_mul >= (1LL << 31)) return RHO_E_SHAPE;
-    k.S_in = (long long)d.d * d.h * d.w_;
-    k.Ho_out = k.Ho * k.oy_mul; k.Wo_out = k.Wo * k.ox_mul;
-
-    if (d.dtype == RHO_BF16 && d.kd == 1 && d.kh == 1 && d.kw == 1 && !d.pre_a) {
-        // 1x1x1 without prologue: the GEMM-shaped kernel
-        WgradK k1{};
-        k1.x1 = (const char*)d.x1; k1.x2 = (const char*)d.x2; k1.dy = (const char*)dy; k1.dw = dw; k1.dbias = dbias;
-        k1.c1 = d.c1; k1.c2 = c2; k1.cin = cin; k1.dyw = (int)dy_width; k1.coutp = d.coutp;
-        const long long npos = (long long)d.n * d.d * d.h * d.w_;
-        const int tiles_total = (int)((npos + 127) / 128);
-        const int pairs = cdiv(d.coutp, 64) * cdiv(cin, 128);
-        int splits = cdiv(1536, pairs);
-        if (splits >= 8) splits &= ~7;
-        if (splits < 1) splits = 1;
-        if (splits > tiles_total) splits = tiles_total;
-        const int tpb = cdiv(tiles_total, splits);
-        splits = cdiv(tiles_total, tpb);
-        static const bool xcd_env1 = !(getenv("RHO_WGRAD_XCD") && atoi(getenv("RHO_WGRAD_XCD")) == 0);
-        k1.xcd_map = (xcd_env1 && splits % 8 == 0 && (long long)splits * pairs < (1LL << 31)) ? 1 : 0;
-        if (cdiv(d.coutp, 64) > 65535 || cdiv(cin, 128) > 65535) return RHO_E_SHAPE;
-        dim3 grid((unsigned)splits, (unsigned)cdiv(d.coutp, 64), (unsigned)cdiv(cin, 128));
-        const long long nw1 = (long long)d.coutp * cin;
-        k1.slab_bias_off = nw1; k1.slab_stride = nw1 + d.coutp;
-        if (ws_want) { *ws_want = (int64_t)splits * k1.slab_stride * (int64_t)sizeof(float); return 0; }
-        if (g_wvariant != nullptr) {
-            snprintf(g_wvariant->buf, (size_t)g_wvariant->cap, "k_wgrad1<bf16>");
-            return 0;
-        }
-        if (ws) {
-            if (ws_bytes < (int64_t)splits * k1.slab_stride * (int64_t)sizeof(float)) return RHO_E_ARG;
-            k1.slab = ws;
-        }
-        hipLaunchKernelGGL(k_wgrad1, grid, dim3(256), (size_t)(4 * 128 * XP + 128 * DYP), as_stream(stream), k1, npos, tiles_total, tpb);
-        hipError_t e1 = hipGetLastError();
-        if (e1 != hipSuccess) return (int)e1;
-        return ws ? launch_slab_reduce(ws, splits, k1.slab_stride, dw, nw1, dbias, d.coutp, as_stream(stream)) : 0;
-    }
-    const size_t lds_cap = 160 * 1024;
-    int np_cap = (int)((lds_cap - 256 * DYP) / XP);
-    if (np_cap > 28 * 64) np_cap = 28 * 64;
-    TileChoice t = choose_tile(d, k.D, k.Do, k.Ho, k.Wo, 640);
-    if (!t.ok) t = choose_tile(d, k.D, k.Do, k.Ho, k.Wo, np_cap);
-    if (!t.ok) return RHO_E_SHAPE;
-
-    k.x1 = (const char*)d.x1; k.x2 = (const char*)d.x2; k.pre_a = d.pre_a; k.pre_b = d.pre_b;
-    k.dy = (const char*)dy; k.dw = dw; k.dbias = dbias;
-    k.c1 = d.c1; k.c2 = c2; k.cin = cin; k.dyw = (int)dy_width; k.coutp = d.coutp;
-    k.sh = d.sh; k.sw = d.sw; k.pre_silu = d.pre_silu;
-    k.TD = t.TD; k.TH = t.TH; k.TW = t.TW; k.ID = t.ID; k.IH = t.IH; k.IW = t.IW; k.NP = t.NP;
-    k.lgTW = ilog2(t.TW); k.lgTH = ilog2(t.TH);
-    k.tiles_d = cdiv(k.Do, t.TD); k.tiles_h = cdiv(k.Ho, t.TH); k.tiles_w = cdiv(k.Wo, t.TW);
-    k.n_batch = nb;
-    const long long tiles = (long long)nb * k.tiles_d * k.tiles_h * k.tiles_w;
-    if (tiles > 0x7FFFFFFFLL) return RHO_E_SHAPE;
-    k.tiles_total = (int)tiles;
-    // enough workgroups to fill 256 CUs, long enough slabs to amortise the 27x64x32 fp32 flush
-    // One workgroup per CU (144 KB of LDS) and equal slabs: the launch runs in rounds of n_cu workgroups.  Pick the slab count so
-    // that splits x pairs fills 3..6 whole rounds (was ceil(1024 / pairs): 6 pairs -> 1026 workgroups = a fifth round of two,
-    // 20 % of the launch, on every layer whose channel count is 3 * 2^k - the concatenated inputs of the output blocks).
-    // f32 1x1x1: a workgroup takes two input-channel chunks (k_wgrad's PAIRC), so the chunk axis of the grid halves
-    const bool pairc = d.dtype == RHO_F32 && d.kd * d.kh * d.kw == 1 && t.NP == 256 && cdiv(t.NP, 64) <= 10;
-    k.pairc = pairc ? 1 : 0;
-    const int nchunk = pairc ? cdiv(cin / CK, 2) : cin / CK;
-    const int pairs = cdiv(d.coutp, COT) * nchunk;
-    static const int n_cu = []() { hipDeviceProp_t pr; int dev = 0; return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-    int splits = cdiv(4 * n_cu, pairs);
-    double best = -1.0;
-    static const int r_lo = getenv("RHO_WGRAD_ROUNDS_MIN") ? atoi(getenv("RHO_WGRAD_ROUNDS_MIN")) : 3;      // (A/B knobs)
-    static const int r_hi = getenv("RHO_WGRAD_ROUNDS_MAX") ? atoi(getenv("RHO_WGRAD_ROUNDS_MAX")) : 6;
-    for (int r = r_lo; r <= r_hi; ++r) {
-        int sp = (r * n_cu) / pairs;
-        if (sp >= 8) sp &= ~7;                 // multiples of 8: the slab -> XCD map of the kernel needs whole groups of 8 slabs
-        if (sp < 1) continue;
-        const long long total = (long long)sp * pairs;
-        const double eff = (double)total / (double)(cdiv((int)total, n_cu) * n_cu) - 0.002 * (r > 4 ? r - 4 : 4 - r) * (r_lo == 3 && r_hi == 6 ? 1.0 : 0.0);
-        if (eff > best) { best = eff; splits = sp; }
-    }
-    if (splits < 1) splits = 1;
-    if (splits > k.tiles_total) splits = k.tiles_total;
-    k.tiles_per_block = cdiv(k.tiles_total, splits);
-    splits = cdiv(k.tiles_total, k.tiles_per_block);
-    if (cdiv(d.coutp, COT) > 65535 || nchunk > 65535) return RHO_E_SHAPE;
-    dim3 grid((unsigned)splits, (unsigned)cdiv(d.coutp, COT), (unsigned)nchunk);
-    static const bool xcd_env = !(getenv("RHO_WGRAD_XCD") && atoi(getenv("RHO_WGRAD_XCD")) == 0);
-    k.xcd_map = (xcd_env && splits % 8 == 0 && (long long)splits * pairs < (1LL << 31)) ? 1 : 0;
-    const int maxp = cdiv(t.NP, 64);
-    size_t lds = (size_t)(maxp <= 10 ? 10 : 28) * 64 * XP + 256 * DYP;
-    if (maxp <= 10 && !d.pre_a) lds *= 2;     // LDS-DMA path (both dtypes since round 3): double-buffered tiles (2 x 72 KB)
-    hipStream_t st = as_stream(stream);
-    // deterministic flush: one slab per accumulator owner (the kernel's TAPSPLIT decides whether that is the workgroup or the wave)
-    const int nt = d.kd * d.kh * d.kw;
-    const bool tapsplit = d.dtype == RHO_BF16 ? (nt >= 9) : (nt > 9);
-    const int nslab = splits * (tapsplit ? 1 : 4);
-    const long long nw = (long long)nt * d.coutp * cin;
-    k.slab_bias_off = nw; k.slab_stride = nw + d.coutp;
-    if (ws_want) { *ws_want = (int64_t)nslab * k.slab_stride * (int64_t)sizeof(float); return 0; }
-    if (ws && g_wvariant == nullptr) {
-        if (ws_bytes < (int64_t)nslab * k.slab_stride * (int64_t)sizeof(float)) return RHO_E_ARG;
-        k.slab = ws;
-    }
-    const int rc = d.dtype == RHO_BF16 ? launch_wgrad_taps<bf16_raw>(d, k, maxp, grid, lds, st) : launch_wgrad_taps<float>(d, k, maxp, grid, lds, st);
-    if (rc != 0 || !ws || g_wvariant != nullptr) return rc;
-    return launch_slab_reduce(ws, nslab, k.slab_stride, dw, nw, dbias, d.coutp, st);
+    const WgradPlan p = wgrad_plan(dp, dy_width);
+    const WgradKey& v = p.key;
+    if (p.rc != 0) return p.rc;
+    if (p.gemm) snprintf(buf, (size_t)cap, "k_wgrad1<bf16>");
+    else snprintf(buf, (size_t)cap, "k_wgrad<%s,%d,%d,%d,MAXP=%d,PRE=%d%s>", v.bf16 ? "bf16" : "f32", v.kd, v.kh, v.kw, v.MAXP, (int)v.PRE, v.GEO ? ",GEO=1" : "");
+    return 0;
 }
 
 // fp32 [taps][coutp][cin_buf] accumulation buffer -> parameter-gradient layout [cout][cin][taps] (fp32),
