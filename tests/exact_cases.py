@@ -4,7 +4,8 @@ test_gpu_exact_conv.py / test_gpu_exact_backward.py / test_gpu_exact_attention.p
 
 Every tensor is [N, C, D, H, W] on the CPU here (1-D / 2-D layers carry leading spatial axes of 1, as the kernels see them);
 geometries are the smallest ones of the tolerance tests' tables (CONV_CASES, WIDE_CONV, PHASE_CASES, S2_CASES, GEMM_CASES, the conv32
-edge geometries, the k-split CASES, BWD_CASES)."""
+edge geometries, the k-split CASES, BWD_CASES).  The GroupNorm passes (GN_CASES and below; test_gpu_exact_groupnorm.py) work on
+channels-last [N, S, C] tensors, as the kernels of groupnorm.hip see them."""
 from __future__ import annotations
 
 import math
@@ -12,6 +13,7 @@ import math
 import torch
 import torch.nn.functional as F
 
+from detdata import det_normal, det_uniform
 from exact_util import int_choice, int_tensor
 
 F32, BF16 = torch.float32, torch.bfloat16
@@ -191,16 +193,18 @@ def tile_ids(c, kind):
     return ((d // TD) * -(-Ho // TH) + (h // TH)) * -(-Wo // TW) + (w // TW)
 
 
-def stats_reference(y, ids):
-    """[N, tiles, 2, C] float64: per tile the channel sums and sums of squares of y [N, C, Do, Ho, Wo]."""
+def stats_reference(y, ids, x=None):
+    """[N, tiles, 2, C] float64: per tile the channel sums and sums of squares of y [N, C, Do, Ho, Wo]; with x (same shape) the
+    second row holds the sums of y * x instead (the product form a data-gradient launch writes through rho_conv_desc.gnb_*)."""
     N, C = y.shape[:2]
     tiles = int(ids.max()) + 1
     out = torch.zeros(N, tiles, 2, C, dtype=torch.float64)
     yf = y.double().reshape(N, C, -1).permute(0, 2, 1)          # [N, S, C]
+    xf = yf if x is None else x.double().reshape(N, C, -1).permute(0, 2, 1)
     idx = ids.reshape(-1)
     for n in range(N):
         out[n, :, 0].index_add_(0, idx, yf[n])
-        out[n, :, 1].index_add_(0, idx, yf[n] * yf[n])
+        out[n, :, 1].index_add_(0, idx, yf[n] * xf[n])
     return out
 
 
@@ -331,3 +335,259 @@ def attn_reference(o, ch):
     rest = logits.scatter(3, o["pi"].unsqueeze(-1), float("-inf"))
     gap = m - rest.max(-1).values if logits.shape[-1] > 1 else torch.full_like(m, float("inf"))
     return dict(logits=logits, m=m, gap=gap)
+
+
+# ----------------------------------------------------------------------------- GroupNorm passes (groupnorm.hip)
+# 32 groups over the channel concat of x1 (c1 channels) and x2 (c2), biased variance, eps = 1e-5.  Every tensor is channels-last
+# [N, S, C]; the references are plain reductions over (positions, channels of a group) and know nothing of position blocks, octets
+# or lanes.
+GN_EPS = 1e-5
+
+
+def _gcase(name, N, c1, c2, S, reach):
+    return dict(name=name, N=N, c1=c1, c2=c2, S=S, C=c1 + c2, cpg=(c1 + c2) // 32, reach=reach, dtypes=BOTH)
+
+
+GN_CASES = [
+    _gcase("one_pos", 1, 32, 0, 1, "one position, one live lane row"),
+    _gcase("cpg3_straddle", 3, 40, 56, 7, "cpg = 3, OCT = 12 does not divide 256, a group spans both sources, S < ppi"),
+    _gcase("nblk2_tails", 2, 64, 0, 257, "nblk = 2, odd tails of the 4x and 2x unrolled loops"),
+    _gcase("oct48", 2, 256, 128, 1600, "OCT = 48, ppi = 5, nblk = 7"),
+    # (N = 1 means gpb = 1 in k_gn_finalize2: CB = cpg there; its KP = 1 / CB = 256 and CB = 132 need N >= 32: the last two entries)
+    _gcase("c2048", 1, 2048, 0, 9, "ppi = 1 in the position passes; KP = 1, CB = 256 in k_gn_bwd_finalize (k_gn_finalize2: CB = 64, KP = 4)"),
+    _gcase("c2048_split", 1, 1024, 1024, 5, "as c2048 with the concat boundary at a workgroup edge of k_gn_bwd_finalize"),
+    _gcase("c1056_idle", 1, 1056, 0, 6, "OCT = 132: threads 132 - 255 idle in the position passes, cpg = 33; CB = 132, KP = 1 in "
+           "k_gn_bwd_finalize (k_gn_finalize2: CB = 33, KP = 7)"),
+    _gcase("gpb4", 32, 32, 0, 64, "gpb = 4 in k_gn_finalize2 (CB = 4, KP = 64)"),
+    _gcase("gpb4_straddle", 33, 40, 56, 9, "gpb = 4 with a group that spans both sources (CB = 12, KP = 21)"),
+    _gcase("gpb4_c2048", 32, 1000, 1048, 2, "gpb = 4 at C = 2048: KP = 1, CB = 256 in k_gn_finalize2, the concat boundary inside a workgroup"),
+    _gcase("gpb4_c1056", 32, 1056, 0, 2, "gpb = 4 at C = 1056: CB = 132, KP = 1 in k_gn_finalize2, threads 132 - 255 idle"),
+    _gcase("nblk_cap", 1, 32, 0, 65537, "the nblk = 256 cap of rho_gn_nblk, 257 positions per block"),
+]
+GN_BY_NAME = {c["name"]: c for c in GN_CASES}
+
+
+def gn_nblk(S):
+    """rho_gn_nblk: 256-position blocks, at most 256 of them."""
+    return max(1, min(256, -(-S // 256)))
+
+
+def gn_int(shape, tag, lo, hi):
+    """Deterministic float32 tensor of integers uniform on [lo, hi]."""
+    return det_uniform(tuple(shape), tag, 0.0, float(hi - lo + 1)).floor().clamp_(0, hi - lo) + lo
+
+
+def per_channel(v, cpg):
+    """[N, 32] per group -> [N, 1, C] per channel."""
+    return v.repeat_interleave(cpg, 1).unsqueeze(1)
+
+
+def gn_stats_operands(c):
+    """x = integers in +-4 plus an integer offset per (sample, group) in +-3 (so the means are not 0); real-valued gamma, beta
+    and FiLM rows [N, 2C] = (scale | shift)."""
+    nm, N, S, C = "gn_" + c["name"], c["N"], c["S"], c["C"]
+    x = gn_int((N, S, C), nm + "x", -4, 4) + per_channel(gn_int((N, 32), nm + "off", -3, 3), c["cpg"])
+    return dict(x=x, gamma=1 + 0.2 * det_uniform((C,), nm + "ga"), beta=0.1 * det_uniform((C,), nm + "be"),
+                film=0.3 * det_normal((N, 2 * C), nm + "film"))
+
+
+def gn_stats_reference(x, dtype=torch.float64):
+    """dict(sum, sumsq [N, C]; mean, rstd [N, 32]) of x [N, S, C]: two-pass biased variance in `dtype`."""
+    N, S, C = x.shape
+    xd = x.to(dtype)
+    xg = xd.reshape(N, S, 32, C // 32)
+    mean = xg.mean((1, 3))
+    var = ((xg - mean.reshape(N, 1, 32, 1)) ** 2).mean((1, 3))
+    return dict(sum=xd.sum(1), sumsq=(xd * xd).sum(1), mean=mean, rstd=1.0 / torch.sqrt(var + GN_EPS))
+
+
+def gn_fold_reference(mean, rstd, gamma, beta, scale=None, shift=None):
+    """The folded affine of rho_hip.h in fp64: a = rstd gamma (1 + scale), b = (beta - mean rstd gamma)(1 + scale) + shift, each
+    [N, C], and the sum of the magnitudes of b's terms (the scale of its rounding errors: the terms may cancel)."""
+    C = gamma.numel()
+    cpg = C // 32
+    mu, rs = per_channel(mean.double(), cpg)[:, 0], per_channel(rstd.double(), cpg)[:, 0]
+    ga, be = gamma.double().unsqueeze(0), beta.double().unsqueeze(0)
+    sc = 1.0 if scale is None else 1.0 + scale.double()
+    sh = 0.0 if shift is None else shift.double()
+    a = rs * ga * sc
+    b = (be - mu * rs * ga) * sc + sh
+    mag = (be.abs() + (mu * rs * ga).abs()) * abs(sc) + abs(sh)
+    return a, b, mag + torch.zeros_like(b)
+
+
+def gn_apply_operands(c, tag="ap"):
+    """Integer operands of the apply passes: x in +-4, folded affine a in +-2, b in +-3 per (sample, channel)."""
+    nm, N, S, C = f"gn{tag}_" + c["name"], c["N"], c["S"], c["C"]
+    return dict(x=gn_int((N, S, C), nm + "x", -4, 4), a=gn_int((N, C), nm + "a", -2, 2), b=gn_int((N, C), nm + "b", -3, 3))
+
+
+def gn_apply_reference(x, a, b, dtype=torch.float64):
+    """a x + b per (sample, channel) over [N, S, C] (act code 0)."""
+    return a.to(dtype).unsqueeze(1) * x.to(dtype) + b.to(dtype).unsqueeze(1)
+
+
+def gn_bwd_operands(c):
+    """Backward operands: g in +-2, x in +-4, SUPPLIED statistics (integer mean in +-3, rstd in {0.5, 1, 2}), integer gamma / beta in
+    +-2, FiLM rows [N, 2C] with an integer scale in -2 .. 2 (so 1 + scale may be 0 or negative), the folded affine (a, b) (read, but
+    without effect at act code 0), integer gradients that dgamma / dbeta accumulate onto, and the coefficients / addends of the
+    apply pass: cA in +-2 [N, C], cP in +-3, cQ in +-1 [N, 32], the running gradients dx and the residual addend in +-8."""
+    nm, N, S, C = "gnb_" + c["name"], c["N"], c["S"], c["C"]
+    o = gn_apply_operands(c, "bw")
+    o.update(g=gn_int((N, S, C), nm + "g", -2, 2), mean=gn_int((N, 32), nm + "mean", -3, 3),
+             rstd=int_choice((N, 32), nm + "rstd", (0.5, 1.0, 2.0)), gamma=gn_int((C,), nm + "ga", -2, 2),
+             beta=gn_int((C,), nm + "be", -2, 2),
+             film=torch.cat([gn_int((N, C), nm + "sc", -2, 2), gn_int((N, C), nm + "sh", -3, 3)], 1),
+             dgamma0=gn_int((C,), nm + "dg0", -16, 16), dbeta0=gn_int((C,), nm + "db0", -16, 16),
+             cA=gn_int((N, C), nm + "cA", -2, 2), cP=gn_int((N, 32), nm + "cP", -3, 3), cQ=gn_int((N, 32), nm + "cQ", -1, 1),
+             dx0=gn_int((N, S, C), nm + "dx0", -8, 8), add1=gn_int((N, S, c["c1"]), nm + "add1", -8, 8))
+    o["stats"] = torch.stack([o["mean"], o["rstd"]], -1).contiguous()
+    return o
+
+
+def gn_bwd_coeffs_reference(R1, R2, mean, rstd, gamma, beta, scale, S, dtype=torch.float64):
+    """What rho_gn_bwd_finalize derives from the per-(sample, channel) sums R1, R2 [N, C] (formulas: gn_bwd_reference)."""
+    N, C = R1.shape
+    cpg = C // 32
+    R1, R2, mean, rstd, gamma, beta = (t.to(dtype) for t in (R1, R2, mean, rstd, gamma, beta))
+    sc = torch.ones(N, C, dtype=dtype) if scale is None else 1.0 + scale.to(dtype)
+    gp = gamma.unsqueeze(0) * sc
+    M = float(cpg * S)
+    s1, s2 = (gp * R1).reshape(N, 32, cpg).sum(2), (gp * R2).reshape(N, 32, cpg).sum(2)
+    return dict(R1=R1, R2=R2, cA=per_channel(rstd, cpg)[:, 0] * gp, cP=(-rstd * s1 + rstd * rstd * s2 * mean) / M,
+                cQ=-rstd * rstd * s2 / M, dgamma=(R2 * sc).sum(0), dbeta=(R1 * sc).sum(0), dgamma_n=R2 * sc, dbeta_n=R1 * sc,
+                dscale=gamma.unsqueeze(0) * R2 + beta.unsqueeze(0) * R1, dshift=R1, M=M)
+
+
+def gn_bwd_reference(gq, x, mean, rstd, gamma, beta, scale=None, dtype=torch.float64):
+    """The formulas above k_gn_bwd_reduce, for gq = g act'(u) [N, S, C] (act code 0: g itself, times the dropout multiplier):
+        xhat = (x - mean) rstd, gamma' = gamma (1 + scale), R1 = sum_pos gq, R2 = sum_pos gq xhat, M = cpg S
+        dx = rstd (gamma' gq - mean_grp(gamma' gq) - xhat mean_grp(gamma' gq xhat)) = cA gq + cP + cQ x  with
+        cA = rstd gamma',  cQ = -rstd^2 sum_grp(gamma' R2) / M,  cP = (-rstd sum_grp(gamma' R1) + rstd^2 mean sum_grp(gamma' R2)) / M
+        dgamma = sum_n R2 (1 + scale), dbeta = sum_n R1 (1 + scale), dscale = gamma R2 + beta R1, dshift = R1.
+    absR2 = sum_pos |gq xhat| bounds every partial sum of R2."""
+    N, S, C = x.shape
+    cpg = C // 32
+    gq, x = gq.to(dtype), x.to(dtype)
+    xhat = (x - per_channel(mean.to(dtype), cpg)) * per_channel(rstd.to(dtype), cpg)
+    r = gn_bwd_coeffs_reference(gq.sum(1), (gq * xhat).sum(1), mean, rstd, gamma, beta, scale, S, dtype)
+    r["absR2"] = (gq * xhat).abs().sum(1)
+    return r
+
+
+def gn_bwd_apply_reference(gq, x, cA, cP, cQ, dtype=torch.float64):
+    """cA gq + cP + cQ x over [N, S, C] (cA per channel, cP / cQ per group)."""
+    cpg = x.shape[2] // 32
+    return (cA.to(dtype).unsqueeze(1) * gq.to(dtype) + per_channel(cP.to(dtype), cpg)
+            + per_channel(cQ.to(dtype), cpg) * x.to(dtype))
+
+
+def is_pow2(v):
+    return v >= 1 and (v & (v - 1)) == 0
+
+
+# (N, C, blocks): rho_gn_bwd_finalize fed synthetic per-tile sums (fmt 1) against the same sums as reduce partials (fmt 0)
+GN_FIN1_CASES = [(3, 96, 1), (3, 96, 1025), (33, 96, 3), (2, 1056, 3), (1, 2048, 3), (2, 64, 2)]
+# (N, c1, c2, blocks of source 1, blocks of source 2): rho_gn_finalize2 on synthetic partials.  k_gn_finalize2 gives a workgroup
+# CB = gpb * cpg channels and KP = 256 / CB lanes per channel, gpb = 4 from N = 32 on: 40 + 56 channels run CB = 3, KP = 85 (N = 3) and
+# CB = 12, KP = 21 (N = 32); 1000 + 1048 and 1024 + 1024 at N = 32 run KP = 1, CB = 256 (the concat boundary inside a workgroup / at
+# a workgroup edge); 520 + 536 at N = 32 runs CB = 132, KP = 1 with threads 132 - 255 idle; 1024 + 1024 at N = 3 runs CB = 64, KP = 4
+GN_FIN2_CASES = ([(N, 40, 56, b1, b2) for N in (3, 32) for b1, b2 in ((1, 3), (3, 1025), (1025, 1))]
+                 + [(32, 1000, 1048, 3, 1), (32, 1024, 1024, 1, 3), (32, 520, 536, 3, 1), (3, 1024, 1024, 3, 1)])
+
+
+def gn_fin2_operands(N, c1, c2, nb1, nb2):
+    """Integer per-block channel sums (+-8) and sums of squares (64 .. 127) of two sources (c1, c2 channels) and of one source of
+    c1 + c2 channels with nb1 blocks, as [N, blocks, C]; S positions per sample (only a divisor to the kernel); real gamma / beta /
+    FiLM rows."""
+    nm, C = f"gnf2_{N}_{c1}_{c2}_{nb1}_{nb2}", c1 + c2
+    o = dict(S=8 * max(nb1, nb2), C=C)
+    for key, nb, cc in (("1", nb1, c1), ("2", nb2, c2), ("0", nb1, C)):
+        o["s" + key] = gn_int((N, nb, cc), nm + "s" + key, -8, 8)
+        o["q" + key] = gn_int((N, nb, cc), nm + "q" + key, 64, 127)
+    o.update(gamma=1 + 0.2 * det_uniform((C,), nm + "ga"), beta=0.1 * det_uniform((C,), nm + "be"),
+             film=0.3 * det_normal((N, 2 * C), nm + "film"))
+    return o
+
+
+def gn_fin1_operands(N, C, nb):
+    """Integer per-tile sums dz (+-16) and dz * x (+-64) as [N, tiles, C], the statistics / parameters of gn_bwd_operands."""
+    nm = f"gnf1_{N}_{C}_{nb}"
+    g = gn_bwd_operands(dict(name=nm, N=N, S=1, C=C, c1=C, cpg=C // 32))
+    o = {k: g[k] for k in ("mean", "rstd", "stats", "gamma", "beta", "film", "dgamma0", "dbeta0")}
+    o.update(dz=gn_int((N, nb, C), nm + "dz", -16, 16), dzx=gn_int((N, nb, C), nm + "dzx", -64, 64), S=256 * nb)
+    return o
+
+
+def gn_moments_reference(sums, sumsq, S):
+    """mean, rstd [N, 32] in fp64 from exact integer channel sums / sums of squares [N, C] (one-pass form, exact operands)."""
+    N, C = sums.shape
+    cnt = float((C // 32) * S)
+    mean = sums.double().reshape(N, 32, -1).sum(2) / cnt
+    var = (sumsq.double().reshape(N, 32, -1).sum(2) / cnt - mean * mean).clamp_min(0.0)
+    return mean, 1.0 / torch.sqrt(var + GN_EPS)
+
+
+def partials_fmt0(s, q):
+    """[N, blocks, C] sums and second sums -> rho_gn_partial's layout [N, blocks, C / 8, 16] (8 sums, then 8 second sums)."""
+    N, nb, C = s.shape
+    return torch.cat([s.reshape(N, nb, C // 8, 8), q.reshape(N, nb, C // 8, 8)], 3).contiguous()
+
+
+def partials_fmt1(s, q):
+    """... -> the conv epilogue's layout [N, tiles, 2, C]."""
+    return torch.stack([s, q], 2).contiguous()
+
+
+# ----------------------------------------------------------------------------- GroupNorm backward inside data-gradient launches
+# rho_conv_desc.gnb_*: a 3x3x3 data gradient (the output = d act(a x0 + b) over the concat of two sources, gnb_c1 < split) that
+# also writes per tile sum dz and sum dz * x0; act code 0, so dz is the stored output.
+GNB_CASES = [
+    _bcase("gnb_bm64", 2, (4, 8, 8), 32, 32, c2=32),
+    _bcase("gnb_bm128", 1, (4, 8, 8), 64, 32, c2=64),
+    _bcase("gnb_ragged", 1, (5, 6, 7), 32, 32, c2=32),
+]
+
+
+def gnb_operands(c):
+    """bwd_operands of the launch plus the norm's forward input x0 [N, C, D, H, W] in +-4 and the GroupNorm-backward operands
+    (gn_bwd_operands' statistics, parameters and FiLM rows) for C = c1 + c2 channels."""
+    o = bwd_operands(c)
+    C = c["c1"] + c["c2"]
+    S = math.prod(c["spatial"])
+    o["x0"] = gn_int((c["N"], C) + c["spatial"], "gnbx0_" + c["name"], -4, 4)
+    g = gn_bwd_operands(dict(name="conv_" + c["name"], N=c["N"], S=1, C=C, c1=c["c1"], cpg=C // 32))
+    for k in ("a", "b", "mean", "rstd", "stats", "gamma", "beta", "film"):
+        o[k] = g[k]
+    o["S"] = S
+    return o
+
+
+def to_nsc(t):
+    """[N, C, D, H, W] -> [N, S, C]."""
+    return t.reshape(t.shape[0], t.shape[1], -1).permute(0, 2, 1)
+
+
+# rho_conv_desc.gna_*: the 1x1x1 skip convolution's data gradient (dy of cy channels -> both concat regions, y2 channels-last) plus
+# cA g + cQ x0 + cP in its epilogue.  (name, dtype, cy, c1, c2, BM, (N, D, H, W)): the geometries of GNA_CASES in
+# test_gpu_bench_shapes.py
+GNA_CASES = [("gna_bf16_bm32", BF16, 64, 64, 32, 32, (2, 4, 8, 8)), ("gna_bf16_bm64", BF16, 64, 128, 64, 64, (2, 8, 8, 8)),
+             ("gna_bf16_bm128", BF16, 128, 256, 128, 128, (3, 4, 8, 8)), ("gna_f32_bm32", F32, 32, 64, 32, 32, (2, 1, 16, 16)),
+             ("gna_f32_bm64", F32, 32, 64, 64, 64, (2, 1, 16, 16)), ("gna_f32_bm128", F32, 64, 128, 128, 128, (2, 1, 16, 16))]
+
+
+def gna_operands(case):
+    name, _, cy, c1, c2, _, (N, D, H, W) = case
+    C = c1 + c2
+    return dict(dy=int_tensor((N, D, H, W, cy), name + "dy", 0.45, 1), w=int_tensor((cy, C, 1, 1, 1), name + "w", 0.45, 1),
+                g=gn_int((N, D, H, W, C), name + "g", -2, 2), x0=gn_int((N, D, H, W, C), name + "x0", -4, 4),
+                a=gn_int((N, C), name + "a", -2, 2), b=gn_int((N, C), name + "b", -3, 3), cA=gn_int((N, C), name + "cA", -2, 2),
+                cP=gn_int((N, 32), name + "cP", -3, 3), cQ=gn_int((N, 32), name + "cQ", -1, 1))
+
+
+def gna_reference(o, dtype=torch.float64):
+    """conv + cA g + cQ x0 + cP, channels-last [N, D, H, W, C]."""
+    N, D, H, W, C = o["g"].shape
+    conv = torch.einsum("ndhwk,kc->ndhwc", o["dy"].to(dtype), o["w"].to(dtype).reshape(-1, C))
+    term = gn_bwd_apply_reference(o["g"].reshape(N, -1, C), o["x0"].reshape(N, -1, C), o["cA"], o["cP"], o["cQ"], dtype)
+    return conv + term.reshape(N, D, H, W, C)

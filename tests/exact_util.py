@@ -27,16 +27,22 @@ def int_choice(shape, tag: str, values) -> torch.Tensor:
     return v[idx]
 
 
+def _axis_lines(idx: torch.Tensor, shape) -> list:
+    """Per axis, the indices that hold a failing element (idx: the [k, dim] result of nonzero())."""
+    out = []
+    for ax in range(len(shape)):
+        u = torch.unique(idx[:, ax]).tolist()
+        out.append(f"  axis {ax} (extent {shape[ax]}): {len(u)} indices with a mismatch: {u[:16]}{' ...' if len(u) > 16 else ''}")
+    return out
+
+
 def mismatch_report(got: torch.Tensor, want: torch.Tensor, what: str) -> str:
     bad = ~(got == want)                      # NaN in either counts as a mismatch
     idx = bad.nonzero()
     first = tuple(int(i) for i in idx[0])
     lines = [f"{what}: {idx.shape[0]} of {got.numel()} elements differ; first at {first}: got {got[first].item()!r}, "
              f"want {want[first].item()!r}"]
-    for ax in range(got.dim()):
-        u = torch.unique(idx[:, ax]).tolist()
-        lines.append(f"  axis {ax} (extent {got.shape[ax]}): {len(u)} indices with a mismatch: {u[:16]}{' ...' if len(u) > 16 else ''}")
-    return "\n".join(lines)
+    return "\n".join(lines + _axis_lines(idx, got.shape))
 
 
 def assert_bit_equal(got: torch.Tensor, want: torch.Tensor, what: str) -> None:
@@ -48,6 +54,49 @@ def assert_bit_equal(got: torch.Tensor, want: torch.Tensor, what: str) -> None:
     if bool((got == want).all()):
         return
     raise AssertionError(mismatch_report(got, want, what))
+
+
+def f32_ulp(v: torch.Tensor) -> torch.Tensor:
+    """float64: the spacing of fp32 numbers at |v| (2^-149 below the smallest normal)."""
+    _, e = torch.frexp(v.double().abs())                      # |v| = m * 2^e, m in [0.5, 1)
+    e = torch.where(v == 0, torch.full_like(e, -125), e)
+    return torch.ldexp(torch.ones_like(v, dtype=torch.float64), (e - 24).clamp_min(-149))
+
+
+def assert_within_ulps(got: torch.Tensor, want64: torch.Tensor, ulps: float, what: str, mag: torch.Tensor = None) -> float:
+    """|got - want| <= ulps * ulp32(want) for EVERY element (fp32 spacing at the fp64 reference value; NaN fails; ulps = 0 is
+    bit equality).  `mag` (same shape, optional) replaces want as the magnitude whose spacing counts - for a sum of terms that may
+    cancel, the sum of the terms' magnitudes.  The failure report has the shape of mismatch_report; returns the largest error met,
+    in those units."""
+    got, want = got.detach().cpu().double(), want64.detach().cpu().double()
+    assert tuple(got.shape) == tuple(want.shape), f"{what}: shape {tuple(got.shape)} vs {tuple(want.shape)}"
+    unit = f32_ulp(want if mag is None else mag.detach().cpu().double().expand_as(want))
+    err = (got - want).abs() / unit
+    ok = err <= ulps
+    if bool(ok.all()):
+        return float(err.max()) if err.numel() else 0.0
+    idx = (~ok).nonzero()
+    first = tuple(int(i) for i in idx[0])
+    worst = float(torch.where(ok | torch.isnan(err), torch.zeros_like(err), err).max())
+    lines = [f"{what}: {idx.shape[0]} of {got.numel()} elements are more than {ulps} fp32 ulp(s) off (worst {worst:.3g}); first at {first}: "
+             f"got {got[first].item()!r}, want {want[first].item()!r}"]
+    raise AssertionError("\n".join(lines + _axis_lines(idx, got.shape)))
+
+
+def assert_within_abs(got: torch.Tensor, want64: torch.Tensor, bound: torch.Tensor, what: str) -> float:
+    """|got - want| <= bound for EVERY element (bound: a number or a tensor of want's shape); reports like assert_within_ulps and
+    returns the largest |got - want| met."""
+    got, want = got.detach().cpu().double(), want64.detach().cpu().double()
+    assert tuple(got.shape) == tuple(want.shape), f"{what}: shape {tuple(got.shape)} vs {tuple(want.shape)}"
+    err = (got - want).abs()
+    ok = err <= (bound.detach().cpu().double() if torch.is_tensor(bound) else float(bound))
+    if bool(ok.all()):
+        return float(err.max()) if err.numel() else 0.0
+    idx = (~ok).nonzero()
+    first = tuple(int(i) for i in idx[0])
+    lines = [f"{what}: {idx.shape[0]} of {got.numel()} elements are outside their bound; first at {first}: got {got[first].item()!r}, "
+             f"want {want[first].item()!r}"]
+    raise AssertionError("\n".join(lines + _axis_lines(idx, got.shape)))
 
 
 def guarded(shape, dtype, device="cuda"):
@@ -83,3 +132,11 @@ def check_f32_exact(ref: torch.Tensor, what: str = "reference") -> None:
     m = float(ref.abs().max()) if ref.numel() else 0.0
     assert m < 2 ** 24, f"{what}: max |value| {m} is not exactly representable in fp32"
     assert bool((ref == ref.round()).all()), f"{what}: not integer-valued"
+
+
+def check_f32_grid(ref: torch.Tensor, step: float, what: str = "reference") -> None:
+    """Multiples of a power of two `step` with fewer than 2^24 steps are exact in fp32 (halves arise where rstd = 0.5)."""
+    k = ref.double() / step
+    m = float(k.abs().max()) if k.numel() else 0.0
+    assert m < 2 ** 24, f"{what}: max |value| {m * step} is not exactly representable in fp32 on a grid of {step}"
+    assert bool((k == k.round()).all()), f"{what}: not a multiple of {step}"

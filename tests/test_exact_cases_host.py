@@ -9,7 +9,8 @@ import torch
 import torch.nn.functional as F
 
 import exact_cases as X
-from exact_util import assert_bit_equal, check_bf16_exact, check_f32_exact, int_tensor, mismatch_report
+from exact_util import (assert_bit_equal, assert_within_abs, assert_within_ulps, check_bf16_exact, check_f32_exact, check_f32_grid, f32_ulp, int_tensor,
+                        mismatch_report)
 
 
 def _ids(cases):
@@ -152,3 +153,162 @@ def test_attention_case_is_one_hot(B, T, heads, ch):
     # raw logits and dP = dO . V are exact integers in fp32
     check_f32_exact(torch.einsum("bhct,bhcs->bhts", o["q"].double(), o["k"].double()), "raw logits")
     check_f32_exact(torch.einsum("bhct,bhcs->bhts", o["do"].double(), o["v"].double()), "dP")
+
+
+# ----------------------------------------------------------------------------- GroupNorm passes
+def test_assert_within_ulps_is_per_element_and_names_the_index():
+    want = torch.tensor([[1.0, 3.0, 0.0], [2.0 ** -130, -1024.0, 0.75]], dtype=torch.float64)
+    assert f32_ulp(want).tolist() == [[2.0 ** -23, 2.0 ** -22, 2.0 ** -149], [2.0 ** -149, 2.0 ** -13, 2.0 ** -24]]
+    got = want.float()
+    assert assert_within_ulps(got, want, 0, "equal") == 0.0
+    got[1, 1] = torch.nextafter(got[1, 1], torch.tensor(-2048.0))
+    assert assert_within_ulps(got, want, 1, "one ulp") == 1.0
+    with pytest.raises(AssertionError) as e:
+        assert_within_ulps(got, want, 0.5, "probe")
+    msg = str(e.value)
+    assert "1 of 6" in msg and "(1, 1)" in msg and "axis 1 (extent 3): 1 indices with a mismatch: [1]" in msg and msg.count("\n") == 2
+    got[0, 2] = float("nan")
+    with pytest.raises(AssertionError, match=r"1 of 6 .*first at \(0, 2\): got nan"):
+        assert_within_ulps(got, want, 1, "NaN never passes")
+    # a magnitude other than want's: 1e-3 off is far inside one ulp of 2^20, far outside one ulp of 1
+    assert_within_ulps(torch.tensor([1.001]), torch.tensor([1.0], dtype=torch.float64), 1, "mag", mag=torch.tensor([2.0 ** 20]))
+
+
+def test_assert_within_abs_is_per_element_and_names_the_index():
+    want = torch.zeros(2, 3, 4, dtype=torch.float64)
+    got = want.float()
+    got[1, 2, 3] = 0.25
+    assert assert_within_abs(got, want, 0.25, "scalar bound") == 0.25
+    bound = torch.full_like(want, 0.1)
+    bound[1, 2, 3] = 0.5
+    assert assert_within_abs(got, want, bound, "a bound per element") == 0.25
+    got[0, 1, 3] = 0.2
+    got[0, 0, 0] = float("nan")
+    with pytest.raises(AssertionError) as e:
+        assert_within_abs(got, want, bound, "probe")
+    msg = str(e.value)
+    assert "probe: 2 of 24 elements are outside their bound; first at (0, 0, 0): got nan" in msg and msg.count("\n") == 3
+    assert "axis 1 (extent 3): 2 indices with a mismatch: [0, 1]" in msg and "axis 2 (extent 4): 2 indices with a mismatch: [0, 3]" in msg
+    with pytest.raises(AssertionError, match="shape"):
+        assert_within_abs(got[0], want, 1.0, "shape")
+
+
+def _gn_dropped(g, tag):
+    """g under a stand-in keep mask at p = 0.5 (inv_keep = 2): the GPU tests use the mask the kernels draw and repeat these checks."""
+    return g * 2.0 * X.gn_int(tuple(g.shape), tag, 0, 1)
+
+
+@pytest.mark.parametrize("c", X.GN_CASES, ids=_ids(X.GN_CASES))
+def test_groupnorm_case_references_are_exactly_representable(c):
+    N, S, C, cpg = c["N"], c["S"], c["C"], c["cpg"]
+    assert C % 32 == 0 and c["c1"] % 8 == 0 and c["c2"] % 8 == 0 and C <= 2048
+    # statistics: integer x of at most 7, channel sums and sums of squares (and every partial sum of them) below 2^24
+    o = X.gn_stats_operands(c)
+    check_bf16_exact(o["x"], "x")
+    assert float(o["x"].abs().max()) <= 7
+    r, r32 = X.gn_stats_reference(o["x"]), X.gn_stats_reference(o["x"], torch.float32)
+    for k in ("sum", "sumsq"):
+        check_f32_exact(r[k], k)
+        assert_bit_equal(r32[k], r[k], f"{c['name']} {k}: fp32 vs fp64 on the CPU")
+    check_f32_exact(o["x"].abs().double().sum(1), "sum of |x| (bounds every partial sum)")
+    # apply: a x + b
+    o = X.gn_apply_operands(c)
+    y = X.gn_apply_reference(o["x"], o["a"], o["b"])
+    assert_bit_equal(X.gn_apply_reference(o["x"], o["a"], o["b"], torch.float32), y, "apply: fp32 vs fp64")
+    check_bf16_exact(y, "a x + b")
+    check_bf16_exact(2 * y, "dropout(a x + b) at p = 0.5")
+    # backward: reduce -> finalize -> apply, plain and under a p = 0.5 mask
+    o = X.gn_bwd_operands(c)
+    for k in ("g", "x", "mean", "gamma", "beta", "film", "a", "b", "cA", "cP", "cQ", "dx0", "add1", "dgamma0", "dbeta0"):
+        check_bf16_exact(o[k], k)
+    assert set(o["rstd"].unique().tolist()) <= {0.5, 1.0, 2.0}
+    scale = o["film"][:, :C]
+    for drop in (False, True):
+        gq = _gn_dropped(o["g"], "hostmask" + c["name"]) if drop else o["g"]
+        r = X.gn_bwd_reference(gq, o["x"], o["mean"], o["rstd"], o["gamma"], o["beta"], scale)
+        r32 = X.gn_bwd_reference(gq, o["x"], o["mean"], o["rstd"], o["gamma"], o["beta"], scale, torch.float32)
+        check_f32_exact(r["R1"], "R1")
+        check_f32_grid(r["absR2"], 0.5, "sum of |gq xhat| (bounds every partial sum of R2)")
+        for k in ("R2", "dgamma_n", "dbeta_n", "dgamma", "dbeta", "dscale", "dshift", "cA"):
+            check_f32_grid(r[k], 0.5, k)
+            assert_bit_equal(r32[k], r[k], f"{c['name']} {k}: fp32 vs fp64 on the CPU")
+        check_f32_grid(r["dgamma_n"].abs().sum(0) + o["dgamma0"].abs().double(), 0.5, "running sums of dgamma over the samples")
+        check_f32_grid(r["dbeta_n"].abs().sum(0) + o["dbeta0"].abs().double(), 0.5, "running sums of dbeta over the samples")
+        if X.is_pow2(cpg * S):                                      # the division by M = cpg S is exact: cP, cQ fit fp32
+            for k in ("cP", "cQ"):
+                assert_bit_equal(r[k].float(), r[k], f"{c['name']} {k}: representable in fp32")
+                assert_bit_equal(r32[k], r[k], f"{c['name']} {k}: fp32 vs fp64 on the CPU")
+        # apply: cA gq + cP + cQ x on top of a running gradient and a residual addend
+        t = X.gn_bwd_apply_reference(gq, o["x"], o["cA"], o["cP"], o["cQ"])
+        assert_bit_equal(X.gn_bwd_apply_reference(gq, o["x"], o["cA"], o["cP"], o["cQ"], torch.float32), t, "bwd apply: fp32 vs fp64")
+        full = t + o["dx0"].double()
+        full[..., :c["c1"]] += o["add1"].double()
+        check_bf16_exact(t, "apply term")
+        check_bf16_exact(o["dx0"][..., :c["c1"]] + o["add1"], "running gradient + residual addend (rounded to the storage type first)")
+        check_bf16_exact(full, "apply term + running gradient + residual addend")
+
+
+@pytest.mark.parametrize("N,c1,c2,nb1,nb2", X.GN_FIN2_CASES)
+def test_finalize2_synthetic_partials_are_exact(N, c1, c2, nb1, nb2):
+    o = X.gn_fin2_operands(N, c1, c2, nb1, nb2)
+    assert c1 % 8 == 0 and c2 % 8 == 0 and (c1 + c2) % 32 == 0 and c1 + c2 <= 2048
+    for key in ("0", "1", "2"):
+        check_f32_exact(o["s" + key].abs().double().sum(1), "channel sums")
+        check_f32_exact(o["q" + key].double().sum(1), "channel sums of squares")
+        assert torch.equal(X.partials_fmt0(o["s" + key], o["q" + key])[..., :8].reshape(o["s" + key].shape), o["s" + key])
+        assert torch.equal(X.partials_fmt1(o["s" + key], o["q" + key])[:, :, 1], o["q" + key])
+    s = torch.cat([o["s1"].sum(1), o["s2"].sum(1)], 1)
+    q = torch.cat([o["q1"].sum(1), o["q2"].sum(1)], 1)
+    mean, rstd = X.gn_moments_reference(s, q, o["S"])
+    assert bool((rstd < 100.0).all()) and bool((rstd > 0.1).all())     # a positive variance: nothing rests on the clamp at 0
+
+
+@pytest.mark.parametrize("N,C,nb", X.GN_FIN1_CASES)
+def test_bwd_finalize_synthetic_tile_sums_are_exact(N, C, nb):
+    o = X.gn_fin1_operands(N, C, nb)
+    mu, rs = X.per_channel(o["mean"], C // 32).double(), X.per_channel(o["rstd"], C // 32).double()
+    r2 = rs * (o["dzx"].double() - mu * o["dz"].double())                # per tile: what fmt 0 holds in its second row
+    check_f32_grid(r2.abs().sum(1), 0.5, "R2 per channel")
+    check_f32_exact(o["dz"].abs().double().sum(1), "R1 per channel")
+    assert_bit_equal(r2.float(), r2, "per-tile R2 in fp32")
+    sc = 1.0 + o["film"][:, :C].double()
+    for v, k in ((r2.sum(1) * sc, "dgamma_n"), (o["dz"].double().sum(1) * sc, "dbeta_n")):
+        check_f32_grid(v.abs().sum(0), 0.5, k + " summed over the samples")
+    check_f32_grid(o["gamma"].double() * r2.sum(1) + o["beta"].double() * o["dz"].double().sum(1), 0.5, "dscale")
+
+
+@pytest.mark.parametrize("c", X.GNB_CASES, ids=_ids(X.GNB_CASES))
+def test_gnb_case_references_are_exactly_representable(c):
+    o = X.gnb_operands(c)
+    r, r32 = X.bwd_reference(c, o), X.bwd_reference(c, o, torch.float32)
+    assert_bit_equal(r32["dx"], r["dx"], "dX: fp32 vs fp64")
+    check_bf16_exact(r["dx"], "dX")
+    check_bf16_exact(o["x0"], "x0")
+    C = c["c1"] + c["c2"]
+    assert c["c1"] % 32 == 0 and c["c2"] % 32 == 0
+    st = X.stats_reference(r["dx"], X.tile_ids(c, "k_conv"), o["x0"])
+    check_f32_exact(st, "per-tile sum dz, sum dz x0")
+    check_f32_exact(X.stats_reference(r["dx"].abs(), X.tile_ids(c, "k_conv"), o["x0"].abs()), "per-tile sums of magnitudes")
+    assert_bit_equal(st.sum(1)[:, 1], (r["dx"] * o["x0"].double()).sum((2, 3, 4)), "tile rows partition the sample")
+    dz, x0 = X.to_nsc(r["dx"]), X.to_nsc(o["x0"])
+    scale = o["film"][:, :C]
+    q = X.gn_bwd_reference(dz, x0, o["mean"], o["rstd"], o["gamma"], o["beta"], scale)
+    q32 = X.gn_bwd_reference(dz, x0, o["mean"], o["rstd"], o["gamma"], o["beta"], scale, torch.float32)
+    check_f32_grid(q["absR2"], 0.5, "sum of |dz xhat|")
+    for k in ("R1", "R2", "dgamma", "dbeta", "dscale", "dshift", "cA"):
+        check_f32_grid(q[k], 0.5, k)
+        assert_bit_equal(q32[k], q[k], f"{k}: fp32 vs fp64")
+    if X.is_pow2((C // 32) * o["S"]):
+        for k in ("cP", "cQ"):
+            assert_bit_equal(q[k].float(), q[k], f"{k}: representable in fp32")
+
+
+@pytest.mark.parametrize("case", X.GNA_CASES, ids=[c[0] for c in X.GNA_CASES])
+def test_gna_case_reference_is_exactly_representable(case):
+    o = X.gna_operands(case)
+    for k in ("dy", "w", "g", "x0", "cA", "cP", "cQ"):
+        check_bf16_exact(o[k], k)
+    y = X.gna_reference(o)
+    assert_bit_equal(X.gna_reference(o, torch.float32), y, "fp32 vs fp64")
+    check_bf16_exact(y, "conv + cA g + cQ x0 + cP")
+    assert case[3] % 32 == 0 and case[4] % 32 == 0

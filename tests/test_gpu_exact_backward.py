@@ -5,7 +5,8 @@ most 256), dW and dbias stay in fp32 (integers far below 2^24), so neither the a
 gradient may differ from the reference in a single bit.  Every output lies between guard bands; outputs that are written (not
 accumulated into) are prefilled with NaN.
 
-Left out on purpose: SiLU in the prologue and the fused GroupNorm-backward reduction / apply epilogues (rstd-derived coefficients)."""
+Left out on purpose: SiLU in the prologue.  The fused GroupNorm-backward reduction / apply epilogues (gnb_* / gna_*) are pinned with
+integer coefficients in test_gpu_exact_groupnorm.py."""
 import pytest
 import torch
 import torch.nn.functional as F

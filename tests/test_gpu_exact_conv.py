@@ -8,8 +8,9 @@ the failure names the index.  Every output (and statistics buffer, and k-split w
 guard bands: an unwritten element and an out-of-range store both fail without faulting.  tests/exact_cases.py holds the cases;
 tests/test_exact_cases_host.py proves on the CPU that the references stay inside the representability caps.
 
-Left out on purpose: SiLU in the prologue, the +gn_apply epilogue and the fused GroupNorm-backward reduction (gnb_*): their
-coefficients are rstd-derived, not integers.  The tolerance tests keep them."""
+Left out on purpose: only SiLU inside the conv loaders (pre_silu / gnb_silu = 1), which the tolerance tests keep.  The +gn_apply
+epilogue and the fused GroupNorm-backward reduction (gnb_*) take their coefficients as inputs, so integer ones pin them bit for bit:
+test_gpu_exact_groupnorm.py, next to the GroupNorm passes themselves."""
 import pytest
 import torch
 
