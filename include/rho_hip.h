@@ -448,7 +448,10 @@ int64_t rho_conv_workspace_bytes(const rho_conv_desc* desc);
 /* Test / profiling aid: the name of the kernel instantiation rho_conv_nd_fwd would launch for `desc`
  * ("k_conv<bf16,3,3,3,BM=128,MAXP=5,NW=8,M16=1>"), written NUL-terminated into buf (cap >= 64).  Nothing is launched.
  * Lets the parity tests assert that the variants they check against the oracle cover every variant a benchmark
- * plan (BASELINE configs c3 / c5) launches.  Same return codes as rho_conv_nd_fwd. */
+ * plan (BASELINE configs c3 / c5) launches.  Same return codes as rho_conv_nd_fwd.
+ * Behind the name's terminating NUL (where cap leaves room) follows a second NUL-terminated string, "geo=1" where the launch runs
+ * the compile-time 4 x 8 x 8 tile form of that instantiation (whole tiles of a stride-1 bf16 3x3x3 layer; RHO_CONV_GEO=0 turns it
+ * off) and "geo=0" otherwise: the name itself does not change with the form. */
 int rho_conv_variant(const rho_conv_desc* desc, char* buf, int cap);
 
 /* ------------------------------------------------------------------ synthetic data */

@@ -20,6 +20,7 @@
 // Replaces conv_nd at every call site of rho_diffusion/models/unet_v2.py (see include/rho_hip.h).
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "conv_common.h"
@@ -92,7 +93,19 @@ struct ConvK {
     const float* gna_cA;
     const float* gna_cP;
     const float* gna_cQ;
+    // GEO instantiations (compile-time 4 x 8 x 8 tile): floor(a / d) of a workgroup-uniform a as one scalar multiply-high, for
+    // d = tiles_w, tiles_w * tiles_h and the number of cout tiles (see geo_div)
+    unsigned mg_tw, mg_thw, mg_ct;
 };
+
+// The geometry the GEO instantiations of k_conv bake in: a 4 x 8 x 8 output tile of a stride-1 3x3x3 layer (10 x 10 halo rows per
+// depth slice, 600 halo positions), whole tiles only, one sample per tile, row bit 2 pairing the 8-wide halo rows (the host loop in
+// conv_plan_stages finds pair_lg = 2 for IW = 10: 4 rows = 40 positions = 8 mod 16)
+struct Geo488 {
+    static constexpr int TD = 4, TH = 8, TW = 8, ID = 6, IH = 10, IW = 10, NP = 600, LGTW = 3, LGTH = 3, PAIR_LG = 2;
+};
+// floor(a / d) = umulhi(a + 1, floor((2^32 - 1) / d)) for d >= 1 and d * (a + 1) <= 2^32 (the plan keeps a and d below 2^16)
+__device__ __forceinline__ int geo_div(int a, unsigned magic) { return (int)__umulhi((unsigned)a + 1u, magic); }
 
 // floor(a / d) for 0 <= a < 2^20 with inv = 1.0f / d: (a + 0.5) * inv is at least 0.5 / d away from an integer, the
 // float error is ~1e-7 * a / d.  (The integer division sequence costs ~20 VALU instructions; the per-tile setup of the
@@ -107,7 +120,7 @@ __device__ __forceinline__ int fdiv_small(int a, float inv) { return (int)(((flo
 // offset is 8 (mod 16) -- the row bit `pair_lg` chosen on the host.  (PMC before this map: SQ_LDS_BANK_CONFLICT was
 // 40-50 % of SQ_LDS_IDX_ACTIVE in this kernel.)
 // position of rank k (0..15) of 16-position unit u (0..15): 16 positions whose halo rows are distinct mod 16
-__device__ __forceinline__ int unit_position(int u, int k, int TW, int pair_lg) {
+__host__ __device__ constexpr __forceinline__ int unit_position(int u, int k, int TW, int pair_lg) {
     if (TW == 8 && pair_lg >= 0) {
         const int lo = u & ((1 << pair_lg) - 1);
         const int row = ((u >> pair_lg) << (pair_lg + 1)) | lo | ((k >> 3) << pair_lg);
@@ -127,15 +140,31 @@ __device__ __forceinline__ int tile_position(int m, int c, int TW, int pair_lg) 
 // pitch that is conflict-free iff both 8-row halves have distinct halo rows (mod 16) of ONE parity: column tile m16 takes
 // the ranks of parity (m16 & 1) of the two units of pair m16 >> 1 - half A (i in 0-3, 12-15) from the even unit, half B
 // (i in 4-11) from the odd one.  The same 32 positions as the 32-wide tile m16 >> 1 of the other layout.
-__device__ __forceinline__ int m16_hb(int i) { return (0x0FF0 >> i) & 1; }
-__device__ __forceinline__ int m16_k8(int i) { return m16_hb(i) ? i - 4 : (i < 4 ? i : i - 8); }
-__device__ __forceinline__ int tile_position16(int m16, int i, int TW, int pair_lg) {
+__host__ __device__ constexpr __forceinline__ int m16_hb(int i) { return (0x0FF0 >> i) & 1; }
+__host__ __device__ constexpr __forceinline__ int m16_k8(int i) { return m16_hb(i) ? i - 4 : (i < 4 ? i : i - 8); }
+__host__ __device__ constexpr __forceinline__ int tile_position16(int m16, int i, int TW, int pair_lg) {
     return unit_position(2 * (m16 >> 1) + m16_hb(i), 2 * m16_k8(i) + (m16 & 1), TW, pair_lg);
+}
+
+// GEO epilogue: a thread's item k is staged row lr0 + 32 * k (lr0 = its item-0 row, 0..31).  With TW = 8 and pair_lg = 2 the bits
+// of the tile position that k sets (row bit 1, depth) are disjoint from those lr0 sets (row bits 0 and 2, the column), so
+// position(lr0 + 32 k) = position(lr0) + geo_item_delta(k) with no carry between the (depth, row, column) fields.
+__host__ __device__ constexpr int geo_row_position(int lr) { return tile_position16((lr >> 6) * 4 + ((lr >> 4) & 3), lr & 15, 8, 2); }
+__host__ __device__ constexpr int geo_item_delta(int k) { return geo_row_position(32 * k); }
+__host__ __device__ constexpr bool geo_items_additive(int nit) {
+    for (int k = 0; k < nit; ++k)
+        for (int lr0 = 0; lr0 < 32; ++lr0)
+            if (geo_row_position(lr0 + 32 * k) != (geo_row_position(lr0) | geo_item_delta(k)) || (geo_row_position(lr0) & geo_item_delta(k)) != 0) return false;
+    return true;
 }
 
 // GNA: the 1x1x1 instantiations whose epilogue carries the GroupNorm backward apply (rho_conv_desc.gna_*; no residual operand there:
 // its 32 registers are what the extra operand takes)
-template <typename T, int KD, int KH, int KW, int BM, int MAXP, int NW, bool M16 = false, bool FSK = false, bool GNA = false>
+// GEO: the tile geometry of Geo488 is a compile-time constant (the bf16 3x3x3 16x16x32 instantiations; conv_plan_stages selects it
+// for whole 4 x 8 x 8 tiles of a stride-1 layer).  Halo decode, tap offsets and output offsets become constants or instruction
+// immediates, the bounds tests of ragged tiles go, and a chunk's halo is staged in straight-line code.  The order of the MFMAs, of the
+// statistics sums and of the prologue expressions is that of the generic form: outputs and statistics are bit-identical.
+template <typename T, int KD, int KH, int KW, int BM, int MAXP, int NW, bool M16 = false, bool FSK = false, bool GNA = false, bool GEO = false>
 // (second launch bound = waves per SIMD the register allocation must allow: 2 for the 8-wave variants and for the 4-wave 1x1x1
 //  variant, which without it took 241 VGPRs + 64 AGPRs = one workgroup per CU and left its HBM-bound layers at 3.3 TB/s)
 __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 10)) ? 2 : 1) void k_conv(const ConvK p) {
@@ -148,9 +177,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
     constexpr int WCO = NW / 4;            // waves along cout
     constexpr int MT = BM / 32 / WCO;      // 32-row cout tiles per wave
     constexpr int WROWS = (BM + RPP - 1) / RPP;  // weight-tile rows per thread
+    static_assert(!GEO || (M16 && sizeof(T) == 2 && KD == 3 && KH == 3 && KW == 3 && !GNA), "GEO: the bf16 3x3x3 16x16x32 variants");
+    static_assert(!GEO || ((MAXP - 1) * RPP < Geo488::NP && MAXP * RPP >= Geo488::NP), "GEO: only the last halo slot is partial");
+    // tile geometry: constants under GEO, launch parameters otherwise
+    const int gTD = GEO ? Geo488::TD : p.TD, gTH = GEO ? Geo488::TH : p.TH, gTW = GEO ? Geo488::TW : p.TW;
+    const int gIH = GEO ? Geo488::IH : p.IH, gIW = GEO ? Geo488::IW : p.IW, gNP = GEO ? Geo488::NP : p.NP;
+    const int gLGTW = GEO ? Geo488::LGTW : p.lgTW, gLGTH = GEO ? Geo488::LGTH : p.lgTH, gPAIR = GEO ? Geo488::PAIR_LG : p.pair_lg;
 
     char* const halo = smem;
-    char* const wbuf = smem + (size_t)p.NP * PITCH;
+    char* const wbuf = smem + (size_t)gNP * PITCH;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -170,8 +205,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
         // slots of the same XCD, so the input tile they all read comes from HBM once and from that L2 afterwards
         const int L = blockIdx.x + gridDim.x * blockIdx.y;
         const int slot = L >> 3;
-        ct = slot % (int)gridDim.y;
-        bt = (L & 7) * ((int)gridDim.x >> 3) + slot / (int)gridDim.y;
+        const int sq = GEO ? geo_div(slot, p.mg_ct) : slot / (int)gridDim.y;
+        ct = slot - sq * (int)gridDim.y;
+        bt = (L & 7) * ((int)gridDim.x >> 3) + sq;
     } else {
         const int nt = gridDim.x, per = nt >> 3;
         if (per > 0) {
@@ -179,23 +215,48 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
             if (bt < full) bt = (bt & 7) * per + (bt >> 3);
         }
     }
-    const int tw_i = bt % p.tiles_w;
-    const int th_i = (bt / p.tiles_w) % p.tiles_h;
-    const int td_i = bt / (p.tiles_w * p.tiles_h);
+    int tw_i, th_i, td_i;
+    if constexpr (GEO) {
+        const int row = geo_div(bt, p.mg_tw);          // td_i * tiles_h + th_i
+        td_i = geo_div(bt, p.mg_thw);
+        tw_i = bt - row * p.tiles_w;
+        th_i = row - td_i * p.tiles_h;
+    } else {
+        tw_i = bt % p.tiles_w;
+        th_i = (bt / p.tiles_w) % p.tiles_h;
+        td_i = bt / (p.tiles_w * p.tiles_h);
+    }
     const int co0 = ct * BM;
     const bool splitk = (KD != 3) && p.ksplit > 1;            // (2-D / 1-D launches have gridDim.z = 1 otherwise: z carries the k-split)
     const int n = splitk ? 0 : (int)blockIdx.z;
-    const int od0 = td_i * p.TD, oh0 = th_i * p.TH, ow0 = tw_i * p.TW;
+    const int od0 = td_i * gTD, oh0 = th_i * gTH, ow0 = tw_i * gTW;
     const int gd_base = od0 - (KD / 2);
-    const int gh_base = p.up_h ? (oh0 / 2 - 1) : (oh0 * p.sh - p.pad_h);
-    const int gw_base = p.up_w ? (ow0 / 2 - 1) : (ow0 * p.sw - p.pad_w);
+    const int gh_base = GEO ? oh0 - 1 : p.up_h ? (oh0 / 2 - 1) : (oh0 * p.sh - p.pad_h);
+    const int gw_base = GEO ? ow0 - 1 : p.up_w ? (ow0 / 2 - 1) : (ow0 * p.sw - p.pad_w);
 
     // ---- halo slots owned by this thread: global linear input position (or -1 = zero padding,
     //      -2 = beyond the tile) and sample index for the prologue coefficients
     constexpr int NSMP = (KD == 3) ? 1 : MAXP;  // 3-D tiles never straddle samples: the sample is blockIdx.z
     int spos[MAXP];
     int ssmp[NSMP];
-    {
+    // GEO: whether this thread's last slot lies inside the 600 halo positions (every earlier slot does)
+    const bool last_in = !GEO || (tid >> 2) + RPP * (MAXP - 1) < Geo488::NP;
+    if constexpr (GEO) {
+        // slot -> (id, ih, iw) by constant division; the position is the tile's first halo position (one scalar) plus id * H * W +
+        // ih * W + iw; -1 = zero padding (and the slots past the tile, which are never written)
+        const int hw = p.H * p.W;
+        const int pos0 = ((n * p.D + gd_base) * p.H + gh_base) * p.W + gw_base;
+#pragma unroll
+        for (int i = 0; i < MAXP; ++i) {
+            const unsigned hp = (unsigned)(tid >> 2) + RPP * i;
+            const unsigned id = hp / (Geo488::IH * Geo488::IW), r = hp - id * (Geo488::IH * Geo488::IW);
+            const unsigned ih = r / Geo488::IW, iw = r - ih * Geo488::IW;
+            bool ok = ((unsigned)(gd_base + (int)id) < (unsigned)p.D) & ((unsigned)(gh_base + (int)ih) < (unsigned)p.H) &
+                      ((unsigned)(gw_base + (int)iw) < (unsigned)p.W);
+            if (i == MAXP - 1) ok = ok && last_in;
+            spos[i] = ok ? pos0 + (int)id * hw + (int)ih * p.W + (int)iw : -1;
+        }
+    } else {
         const int ihw = p.IH * p.IW;
 #pragma unroll
         for (int i = 0; i < MAXP; ++i) {
@@ -228,20 +289,20 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
     int offd[2], offh[2][KH], offw[2][KW];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int pp = M16 ? tile_position16(2 * (wpos * 2 + j), lane & 15, p.TW, p.pair_lg)
-                           : tile_position(wpos * 2 + j, lane & 31, p.TW, p.pair_lg);
-        const int pw = pp & (p.TW - 1);
-        const int ph = (pp >> p.lgTW) & (p.TH - 1);
-        const int pd = pp >> (p.lgTW + p.lgTH);
-        offd[j] = pd * p.IH * p.IW * PITCH + 16 * (M16 ? (lane >> 4) : half);
+        const int pp = M16 ? tile_position16(2 * (wpos * 2 + j), lane & 15, gTW, gPAIR)
+                           : tile_position(wpos * 2 + j, lane & 31, gTW, gPAIR);
+        const int pw = pp & (gTW - 1);
+        const int ph = (pp >> gLGTW) & (gTH - 1);
+        const int pd = pp >> (gLGTW + gLGTH);
+        offd[j] = pd * gIH * gIW * PITCH + 16 * (M16 ? (lane >> 4) : half);
 #pragma unroll
         for (int kh = 0; kh < KH; ++kh) {
-            const int ih = p.up_h ? (((ph + kh - 1) >> 1) + 1) : (ph * p.sh + kh);
-            offh[j][kh] = ih * p.IW * PITCH;
+            const int ih = GEO ? ph + kh : p.up_h ? (((ph + kh - 1) >> 1) + 1) : (ph * p.sh + kh);
+            offh[j][kh] = ih * gIW * PITCH;
         }
 #pragma unroll
         for (int kw = 0; kw < KW; ++kw) {
-            const int iw = p.up_w ? (((pw + kw - 1) >> 1) + 1) : (pw * p.sw + kw);
+            const int iw = GEO ? pw + kw : p.up_w ? (((pw + kw - 1) >> 1) + 1) : (pw * p.sw + kw);
             offw[j][kw] = iw * PITCH;
         }
     }
@@ -333,7 +394,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
     // trip per chunk; a 3-D tile lies in one sample, so that sample's coefficients are staged in LDS once per tile.
     const float* coef = nullptr;
     if constexpr (NT != 1 && KD == 3) {
-        if (p.coef_off > 0 && p.pre_a != nullptr) {
+        if ((GEO || p.coef_off > 0) && p.pre_a != nullptr) {      // (GEO: the plan refuses the path without staged coefficients)
             float* cw_ = reinterpret_cast<float*>(smem + p.coef_off);
             for (int i = tid; i < p.cin; i += NTHR) {
                 cw_[i] = p.pre_a[(size_t)n * p.cin + i];
@@ -360,14 +421,14 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
 #pragma unroll
         for (int i = 0; i < XR; ++i) {
             const int r = (tid >> 2) + RPP * i;
-            const int od = od0 + (r >> (p.lgTW + p.lgTH)), oh = oh0 + ((r >> p.lgTW) & (p.TH - 1)), ow = ow0 + (r & (p.TW - 1));
-            const bool ok = od < p.Do && oh < p.Ho && ow < p.Wo;
+            const int od = od0 + (r >> (gLGTW + gLGTH)), oh = oh0 + ((r >> gLGTW) & (gTH - 1)), ow = ow0 + (r & (gTW - 1));
+            const bool ok = GEO || (od < p.Do && oh < p.Ho && ow < p.Wo);
             gp[i] = ok ? ((n * p.Do + od) * p.Ho + oh) * p.Wo + ow : -1;
         }
         int cb[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-            cb[j] = tile_position16(2 * (wpos * 2 + j), lane & 15, p.TW, p.pair_lg) * PITCH + 16 * (lane >> 4);
+            cb[j] = tile_position16(2 * (wpos * 2 + j), lane & 15, gTW, gPAIR) * PITCH + 16 * (lane >> 4);
         const unsigned skw_voff = (unsigned)(tid >> 2) * (unsigned)skc * (unsigned)sizeof(T) + (unsigned)piece * 16u;
         const char* const skw0 = p.sk_w + (size_t)co0 * skc * sizeof(T);
         uint4 xr[XR], wr0 = make_uint4(0u, 0u, 0u, 0u), wr1 = make_uint4(0u, 0u, 0u, 0u);
@@ -378,7 +439,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
             if (ch < p.sk_c1) { src = p.sk_x1; cs = p.sk_c1; csrc = ch; } else { src = p.sk_x2; cs = p.sk_c2; csrc = ch - p.sk_c1; }
 #pragma unroll
             for (int i = 0; i < XR; ++i) {
-                const int ps = gp[i] > 0 ? gp[i] : 0;
+                const int ps = (GEO || gp[i] > 0) ? gp[i] : 0;
                 xr[i] = *reinterpret_cast<const uint4*>(src + ((size_t)ps * cs + csrc) * sizeof(T) + piece * 16);
             }
             const char* ws_ = skw0 + (size_t)c * 64;
@@ -389,7 +450,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
 #pragma unroll
             for (int i = 0; i < XR; ++i) {
                 const int r = (tid >> 2) + RPP * i;
-                *reinterpret_cast<uint4*>(sa + (slot * 256 + r) * PITCH + piece * 16) = gp[i] >= 0 ? xr[i] : make_uint4(0u, 0u, 0u, 0u);
+                *reinterpret_cast<uint4*>(sa + (slot * 256 + r) * PITCH + piece * 16) = (GEO || gp[i] >= 0) ? xr[i] : make_uint4(0u, 0u, 0u, 0u);
             }
             char* const wd = sw + slot * BM * PITCH + w_dst0;
             if (w_active) *reinterpret_cast<uint4*>(wd) = wr0;
@@ -483,7 +544,57 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
         //      barrier that closed its last tap)
         {
             const int c = (ck_lo + ck) * CK;
-            if constexpr (HPF) {
+            if constexpr (GEO) {
+                // Straight-line staging: the thread's prologue coefficients (its channel piece of this chunk) are read from LDS
+                // once per chunk, every slot is loaded (padding slots read position 0), activated and then zeroed by a select - no
+                // branch per slot, so the slots' SiLU chains interleave (conv32.h, "one exec-masked block per row").  The load
+                // shape is the generic one: the whole halo early (HPF) or two batches of five.
+                const bool has_pre = p.pre_a != nullptr;
+                f32x2_t av[4] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}}, bv[4] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
+                if (has_pre) {
+                    const float* const ca = coef + c + piece * PE;
+                    const float* const cb = ca + p.cin;
+                    const float4 a0 = *reinterpret_cast<const float4*>(ca), a1 = *reinterpret_cast<const float4*>(ca + 4);
+                    const float4 b0 = *reinterpret_cast<const float4*>(cb), b1 = *reinterpret_cast<const float4*>(cb + 4);
+                    av[0] = f32x2_t{a0.x, a0.y}; av[1] = f32x2_t{a0.z, a0.w}; av[2] = f32x2_t{a1.x, a1.y}; av[3] = f32x2_t{a1.z, a1.w};
+                    bv[0] = f32x2_t{b0.x, b0.y}; bv[1] = f32x2_t{b0.z, b0.w}; bv[2] = f32x2_t{b1.x, b1.y}; bv[3] = f32x2_t{b1.z, b1.w};
+                }
+                const char* src = nullptr;
+                int cs = 0, csrc = 0;
+                if constexpr (!HPF) halo_src(ck, src, cs, csrc);
+                constexpr int NB = HPF ? MAXP : 5;           // slots per batch (divides MAXP)
+                static_assert(MAXP % NB == 0, "whole batches");
+#pragma unroll
+                for (int i0 = 0; i0 < MAXP; i0 += NB) {
+                    uint4 v[NB];
+#pragma unroll
+                    for (int q = 0; q < NB; ++q) {
+                        if constexpr (HPF) {
+                            v[q] = hv[i0 + q];
+                        } else {
+                            const int ps = spos[i0 + q] > 0 ? spos[i0 + q] : 0;
+                            v[q] = *reinterpret_cast<const uint4*>(src + ((size_t)ps * cs + csrc) * sizeof(T) + piece * 16);
+                        }
+                    }
+                    if (has_pre) {                           // (wave-uniform, as is pre_silu: one branch per batch)
+                        if (p.pre_silu) {
+#pragma unroll
+                            for (int q = 0; q < NB; ++q) v[q] = apply_pre_regs<true>(v[q], av, bv);
+                        } else {
+#pragma unroll
+                            for (int q = 0; q < NB; ++q) v[q] = apply_pre_regs<false>(v[q], av, bv);
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < NB; ++q) {
+                        const int i = i0 + q;
+                        const bool in = spos[i] >= 0;
+                        const uint4 u = make_uint4(in ? v[q].x : 0u, in ? v[q].y : 0u, in ? v[q].z : 0u, in ? v[q].w : 0u);
+                        const int hp = (tid >> 2) + RPP * i;
+                        if (i < MAXP - 1 || last_in) *reinterpret_cast<uint4*>(halo + hp * PITCH + piece * 16) = u;
+                    }
+                }
+            } else if constexpr (HPF) {
 #pragma unroll
                 for (int i = 0; i < MAXP; ++i) {
                     if (spos[i] != -2) {
@@ -566,8 +677,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
             const int bbase[2] = {offd[0] + offh[0][0] + offw[0][0], offd[1] + offh[1][0] + offw[1][0]};
             // (opaque per chunk: computed by the scalar ALU at each use - hoisted out of the chunk loop the 27 offsets and the 27
             //  weight bases overflow the SGPR file and come back as v_readlane per use)
-            int ihs = p.IH, iws = p.IW;
-            asm volatile("" : "+s"(ihs), "+s"(iws));
+            // (GEO: the 27 offsets are constants below 2^16 and ride in the offset field of the ds_read instructions)
+            int ihs = gIH, iws = gIW;
+            if constexpr (!GEO) asm volatile("" : "+s"(ihs), "+s"(iws));
             auto rdB = [&](int tap, int jp, u32x4_t (&fb)[2]) {
                 const int kd = tap / (KH * KW), kh = (tap / KW) % KH, kw = tap % KW;
                 const char* b = halo + (bbase[jp] + ((kd * ihs + kh) * iws + kw) * PITCH);
@@ -985,7 +1097,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
                 const int gC = gna_on ? q.cout : q.split;
                 const int gcs = g_first ? q.gnb_c1 : gC - q.gnb_c1, gch = g_first ? gco : gco - q.gnb_c1;
                 if (gnb_on) {
-                    const int nsg = n + bt / q.tps;         // the tile's sample (statistics are only fused for one-sample tiles)
+                    const int nsg = GEO ? n : n + bt / q.tps;   // the tile's sample (statistics are only fused for one-sample tiles)
 #pragma unroll
                     for (int e = 0; e < PE; ++e) {
                         gna[e] = q.gnb_a[(size_t)nsg * gC + gco + e];
@@ -1019,8 +1131,26 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
                         }
                     }
                 }
+                // GEO: item k of a thread lies a compile-time offset from its item 0 (geo_item_delta), so an output row is the tile's
+                // first row (scalar) + the thread's row inside the tile + a scalar per item; whole tiles: no bounds tests but the
+                // channel-piece test of the second region, which does not depend on the item
+                const bool pc_ok = rc0 + piece * PE + PE <= rw;     // (the last tile of the second region may reach past its tensor)
+                int L0 = 0;
+                if constexpr (GEO) {
+                    static_assert(!GEO || (NTHR / PPR == 32 && geo_items_additive(NIT)), "GEO: item k = item 0 + a constant");
+                    const int lr0 = tid / PPR;
+                    const int pp0 = geo_row_position(lr0);
+                    L0 = ((n * q.Do + od0 + (pp0 >> 6)) * q.Ho + oh0 + ((pp0 >> 3) & 7)) * q.Wo + ow0 + (pp0 & 7);
+                }
 #pragma unroll
                 for (int k = 0; k < NIT; ++k) {
+                    int L;
+                    bool ok;
+                    if constexpr (GEO) {
+                        const int dk = geo_item_delta(k);
+                        L = L0 + ((dk >> 6) * q.Ho + ((dk >> 3) & 7)) * q.Wo + (dk & 7);
+                        ok = pc_ok;
+                    } else {
                     const int lr = tid / PPR + k * (NTHR / PPR);
                     const int pp = M16 ? tile_position16((lr >> 6) * 4 + ((lr >> 4) & 3), lr & 15, q.TW, q.pair_lg)
                                        : tile_position((lr >> 6) * 2 + ((lr >> 5) & 1), lr & 31, q.TW, q.pair_lg);
@@ -1028,10 +1158,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
                     const int ph = (pp >> q.lgTW) & (q.TH - 1);
                     const int pd = pp >> (q.lgTW + q.lgTH);
                     const int od = od0 + pd, oh = oh0 + ph, ow = ow0 + pw;
-                    // (the last tile of the second region may reach past its tensor)
-                    const bool ok = od < q.Do && oh < q.Ho && ow < q.Wo && (rc0 + piece * PE + PE <= rw);
-                    const int L = ((n * q.Do + od) * q.Ho_out + (oh * q.oy_mul + q.oy_add)) * q.Wo_out + (ow * q.ox_mul + q.ox_add);
-                    eoff[k] = ok ? L : -1;
+                    ok = od < q.Do && oh < q.Ho && ow < q.Wo && pc_ok;
+                    L = ((n * q.Do + od) * q.Ho_out + (oh * q.oy_mul + q.oy_add)) * q.Wo_out + (ow * q.ox_mul + q.ox_add);
+                    }
+                    eoff[k] = (GEO || ok) ? L : -1;
                     if constexpr (!GNA) {
                         rres[k] = make_uint4(0u, 0u, 0u, 0u);
                         if (ok && rrp != nullptr)   // (32 x 32 -> 64-bit multiply: one v_mad_u64_u32 instead of a 64 x 64 sequence)
@@ -1046,9 +1176,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
                 }
             }
             __syncthreads();
+            if (!GEO || rc0 + (tid % PPR) * PE + PE <= rw) {
 #pragma unroll
             for (int k = 0; k < NIT; ++k) {
-                if (eoff[k] < 0) continue;
+                if (!GEO && eoff[k] < 0) continue;
                 const int lr = tid / PPR + k * (NTHR / PPR), piece = tid % PPR;
                 const int L = eoff[k];
                 const int co = co0 + piece * PE;
@@ -1151,6 +1282,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
                     }
                 }
             }
+            }
         }
         if (q.stats != nullptr) {
             // threads tid = piece (mod PPR) hold partials of the same channels: combine through LDS in thread order
@@ -1163,7 +1295,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
                 red[tid * (2 * PE) + PE + e] = ssq[e];
             }
             __syncthreads();
-            const int ns = n + bt / q.tps, ts = bt % q.tps + q.stats_off;
+            // (GEO: no phases, so a sample's tps tiles are this launch's own tiles)
+            const int ns = GEO ? n : n + bt / q.tps, ts = GEO ? bt : bt % q.tps + q.stats_off;
             for (int item = tid; item < PPR * 2 * PE; item += NTHR) {
                 const int piece = item / (2 * PE), e2 = item % (2 * PE);
                 float accv = 0.0f;
@@ -1174,6 +1307,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || (KD * KH * KW == 1 && MAXP <= 
         }
         return;
     }
+    if constexpr (GEO) return;       // (the plan gives GEO launches channels-last regions only)
 #pragma unroll
     for (int jx = 0; jx < (M16 ? 4 : 2); ++jx) {
         const int pp = M16 ? tile_position16(wpos * 4 + jx, lane & 15, q.TW, q.pair_lg) : tile_position(wpos * 2 + jx, lane & 31, q.TW, q.pair_lg);
@@ -1343,7 +1477,7 @@ enum Stage {
     ST_DONE
 };
 enum Kernel { K_CONV, K_CONV32, K_GEMM1X1 };
-struct VariantKey { bool bf16; int kd, kh, kw, BM, MAXP, NW; bool M16, FSK, GNA; };      // one instantiation of k_conv
+struct VariantKey { bool bf16; int kd, kh, kw, BM, MAXP, NW; bool M16, FSK, GNA, GEO; };      // one instantiation of k_conv
 using ConvFn = void (*)(const ConvK);
 struct ConvPlan : PlanStatus<Stage> {
     Kernel kernel;
@@ -1360,12 +1494,12 @@ struct ConvPlan : PlanStatus<Stage> {
 
 // key -> instantiation; nullptr for a key that has none.  The cout tiles of one flavour: 128 couts on 8 waves with S / 2 halo slots
 // per thread, 64 (and 32, where the flavour has it) couts on 4 waves with S
-template <typename T, int KD, int KH, int KW, int S, bool M16, bool FSK, bool GNA, bool BM32>
+template <typename T, int KD, int KH, int KW, int S, bool M16, bool FSK, bool GNA, bool BM32, bool GEO = false>
 ConvFn conv_tiles(const VariantKey& v) {
     if (v.MAXP != (v.BM == 128 ? S / 2 : S) || v.NW != (v.BM == 128 ? 8 : 4)) return nullptr;
-    if (v.BM == 128) return k_conv<T, KD, KH, KW, 128, S / 2, 8, M16, FSK, GNA>;
-    if (v.BM == 64) return k_conv<T, KD, KH, KW, 64, S, 4, M16, FSK, GNA>;
-    if constexpr (BM32) { if (v.BM == 32) return k_conv<T, KD, KH, KW, 32, S, 4, M16, FSK, GNA>; }
+    if (v.BM == 128) return k_conv<T, KD, KH, KW, 128, S / 2, 8, M16, FSK, GNA, GEO>;
+    if (v.BM == 64) return k_conv<T, KD, KH, KW, 64, S, 4, M16, FSK, GNA, GEO>;
+    if constexpr (BM32) { if (v.BM == 32) return k_conv<T, KD, KH, KW, 32, S, 4, M16, FSK, GNA, GEO>; }
     return nullptr;
 }
 // ... and the flavours of one tap shape.  Every shape has the small-halo tiles (np <= 640: S = 10); the sub-pixel phase shapes (2-tap
@@ -1375,6 +1509,12 @@ ConvFn conv_kernel_taps(const VariantKey& v) {
     constexpr int NT = KD * KH * KW;
     constexpr bool PHASE = (KH == 2 || KW == 2 || (KD == 3 && KH == 1 && KW == 1));
     constexpr bool HAS_M16 = sizeof(T) == 2 && NT > 1 && NT % 3 == 0;      // the 16x16x32 MFMA layout (holds a higher clock under load)
+    if (v.GEO) {              // compile-time 4 x 8 x 8 tile: the 16x16x32 3x3x3 variants, with and without the folded skip
+        if constexpr (HAS_M16 && NT == 27) {
+            if (v.M16 && !v.GNA) return v.FSK ? conv_tiles<T, KD, KH, KW, 10, true, true, false, false, true>(v) : conv_tiles<T, KD, KH, KW, 10, true, false, false, false, true>(v);
+        }
+        return nullptr;
+    }
     if (v.FSK) {              // folded skip: the 16x16x32 3x3x3 variants
         if constexpr (HAS_M16 && NT == 27) { if (v.M16 && !v.GNA) return conv_tiles<T, KD, KH, KW, 10, true, true, false, false>(v); }
         return nullptr;
@@ -1417,6 +1557,9 @@ bool m16_env_on() { static const bool on = env_on("RHO_CONV_M16"); return on; }
 // 8-wave 128-cout tile whose waves all sit in set-up / epilogue at the same time (0 = off)
 int bm64_max_chunks() { static const int n = getenv("RHO_BM64_MAX_CHUNKS") ? atoi(getenv("RHO_BM64_MAX_CHUNKS")) : 0; return n; }
 bool splitk_env_on() { static const bool on = env_on("RHO_CONV_SPLITK"); return on; }
+// A/B knob: the compile-time-geometry instantiations (GEO) for whole 4 x 8 x 8 tiles of stride-1 bf16 3x3x3 layers (0 = generic form)
+bool geo_env_on() { static const bool on = env_on("RHO_CONV_GEO"); return on; }
+unsigned geo_magic(long long d) { return (unsigned)(0xFFFFFFFFull / (unsigned long long)d); }      // see geo_div
 
 // The stages of a plan: returns the error of the stage that p.stage names, or 0 with p.stage = ST_DONE
 int conv_plan_stages(const rho_conv_desc& d, ConvPlan& p) {
@@ -1500,7 +1643,7 @@ int conv_plan_stages(const rho_conv_desc& d, ConvPlan& p) {
     else if (d.coutp % 64 == 0 && (d.split % 64 == 0)) BM = 64;
     if (BM == 128 && bm64_max_chunks() > 0 && d.kd == 3 && taps > 1 && cin / CK <= bm64_max_chunks()) BM = 64;
     VariantKey& v = p.key;
-    v = VariantKey{d.dtype == RHO_BF16, d.kd, d.kh, d.kw, BM, 0, BM == 128 ? 8 : 4, false, false, false};
+    v = VariantKey{d.dtype == RHO_BF16, d.kd, d.kh, d.kw, BM, 0, BM == 128 ? 8 : 4, false, false, false, false};
 
     // position tile.  The weight ring is sized before the tile is known, for every launch the 16x16x32 layout could take
     // (bf16, taps a multiple of 3, stride 1, no upsampling); the layout itself also needs the small halo, see below.
@@ -1537,10 +1680,17 @@ int conv_plan_stages(const rho_conv_desc& d, ConvPlan& p) {
         }
     }
     if (d.pre_a && !d.pre_b) return RHO_E_ARG;
+    // the compile-time form of this tile (Geo488): stride 1 and no upsampling (the 16x16x32 layout already asks for that), no
+    // zero-stuffing, no phases, whole tiles, every output region channels-last in whole 16-byte pieces
+    v.GEO = geo_env_on() && v.M16 && d.kd == 3 && d.kh == 3 && d.kw == 3 && t.TD == 4 && t.TH == 8 && t.TW == 8 && k.pair_lg == 2 &&
+            !d.zs_h && !d.zs_w && !d.ph_h && !d.ph_w && !d.phd_h && !d.phd_w && k.Do % 4 == 0 && k.Ho % 8 == 0 && k.Wo % 8 == 0 &&
+            (d.split == d.cout || (d.y2_cl && (d.cout - d.split) % 8 == 0));
 
     const long long tiles = (long long)cdiv(k.Do, t.TD) * k.tiles_h * k.tiles_w;
     if (tiles > 0x7FFFFFFFLL || d.coutp / BM > 65535 || gridz > 65535) return RHO_E_SHAPE;
     k.cofast = (d.coutp / BM > 1 && tiles % 8 == 0) ? 1 : 0;
+    if (tiles * (d.coutp / BM) >= 65536) v.GEO = false;      // (geo_div's range: tile index, cofast slot and every divisor below 2^16)
+    k.mg_tw = geo_magic(k.tiles_w); k.mg_thw = geo_magic((long long)k.tiles_w * k.tiles_h); k.mg_ct = geo_magic(d.coutp / BM);
     p.grid = dim3((unsigned)tiles, (unsigned)(d.coutp / BM), (unsigned)gridz);
     // fused output statistics: only where a tile belongs to one sample and the whole output is channels-last
     int64_t tps_geo = 0;                                 // tiles per sample where every tile lies in one sample, else 0
@@ -1610,6 +1760,7 @@ int conv_plan_stages(const rho_conv_desc& d, ConvPlan& p) {
     if (taps == 1)        // 1x1x1: double-buffered activations + weights + the prologue coefficients of one sample
         lds = (size_t)2 * 256 * PITCH + (size_t)2 * BM * PITCH + (d.pre_a ? (size_t)2 * k.cin * sizeof(float) : 0);
     if (k.coef_off > 0 && (size_t)k.coef_off < lds_sk) { lds -= (size_t)2 * cin * sizeof(float); k.coef_off = 0; }   // (the skip phase's buffers would overlap them)
+    if (d.pre_a && k.coef_off == 0) v.GEO = false;             // (its staging reads the prologue coefficients from LDS only)
     if (lds < lds_sk) lds = lds_sk;
     if (d.stats) { const size_t lr = (size_t)(BM == 128 ? 512 : 256) * 16 * sizeof(float); if (lds < lr) lds = lr; }
     const size_t lds_epi = (size_t)256 * (BM * 4 + 16);       // epilogue transpose staging (fp32 rows, all 256 positions at once)
@@ -1669,6 +1820,10 @@ extern "C" int rho_conv_variant(const rho_conv_desc* dp, char* buf, int cap) {
     else if (p.kernel == K_GEMM1X1) snprintf(buf, (size_t)cap, "k_gemm1x1<bf16,256x%d>", G1_BN);
     else snprintf(buf, (size_t)cap, "k_conv<%s,%d,%d,%d,BM=%d,MAXP=%d,NW=%d,M16=%d>%s%s", v.bf16 ? "bf16" : "f32", v.kd, v.kh, v.kw, v.BM,
                   v.MAXP, v.NW, (int)v.M16, v.FSK ? "+skip" : "", v.GNA ? "+gn_apply" : "");
+    // the name is the contract; behind its terminating NUL a second string tells which form of the instantiation runs
+    // ("geo=1": compile-time 4 x 8 x 8 tile geometry), for tests and the --dump-ops table
+    const size_t len = strlen(buf);
+    if (len + 8 <= (size_t)cap) snprintf(buf + len + 1, (size_t)cap - len - 1, "geo=%d", (p.kernel == K_CONV && v.GEO) ? 1 : 0);
     return 0;
 }
 

@@ -64,6 +64,31 @@ __device__ __forceinline__ uint4 apply_pre<bf16_raw>(uint4 v, const float* __res
     return make_uint4(r[0], r[1], r[2], r[3]);
 }
 
+// apply_pre<bf16_raw> with the coefficients already in registers (the caller reads them once for many pieces) and the SiLU test a
+// template argument (the caller branches once for many pieces): the same operation sequence per element, bit-identical results.
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+template <bool SILU>
+__device__ __forceinline__ uint4 apply_pre_regs(uint4 v, const f32x2_t (&av)[4], const f32x2_t (&bv)[4]) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const f32x2_t x = {__uint_as_float(w[j] << 16), __uint_as_float(w[j] & 0xFFFF0000u)};
+        f32x2_t y = __builtin_elementwise_fma(av[j], x, bv[j]);
+        if constexpr (SILU) {
+            const f32x2_t t = y * -1.4426950408889634f;
+            const f32x2_t e = {__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
+            const f32x2_t d = e + 1.0f;
+            const f32x2_t q = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+            y = y * q;
+        }
+        const bf16x2_t h = {(__bf16)y.x, (__bf16)y.y};
+        r[j] = __builtin_bit_cast(uint32_t, h);
+    }
+    return make_uint4(r[0], r[1], r[2], r[3]);
+}
+
 template <>
 __device__ __forceinline__ uint4 apply_pre<float>(uint4 v, const float* __restrict__ a, const float* __restrict__ b, int silu) {
     const float4 a0 = *reinterpret_cast<const float4*>(a);

@@ -1084,6 +1084,14 @@ def conv_variant(desc: ConvDesc) -> str:
     return buf.value.decode()
 
 
+def conv_variant_detail(desc: ConvDesc) -> str:
+    """The string rho_conv_variant leaves behind the variant name's terminating NUL: ``"geo=1"`` where the launch runs the
+    compile-time 4 x 8 x 8 tile form of its instantiation, ``"geo=0"`` otherwise."""
+    buf = C.create_string_buffer(128)
+    check(hip.lib().rho_conv_variant(C.byref(desc), buf, 128), "rho_conv_variant")
+    return buf.raw[len(buf.value) + 1:].split(b"\0", 1)[0].decode()
+
+
 def conv_wgrad_variant(desc: ConvDesc, dy_width: int) -> str:
     buf = C.create_string_buffer(128)
     check(hip.lib().rho_conv_wgrad_variant(C.byref(desc), dy_width, buf, 128), "rho_conv_wgrad_variant")

@@ -48,7 +48,7 @@ Tensor = torch.Tensor
 
 
 PlanSwitches = namedtuple("PlanSwitches", "materialize_act materialize_min_cout phase_upsample phase_upsample_bwd phase_min_wgs fold_skip "
-                                     "s2_split s2_split_bwd fuse_gn_bwd gemm_ends direct_ends fuse_skip_dgrad gemm1x1")
+                                     "s2_split s2_split_bwd fuse_gn_bwd gemm_ends direct_ends fuse_skip_dgrad gemm1x1 conv_geo")
 
 
 class UNetEngine:
@@ -279,10 +279,11 @@ class UNetEngine:
 
     # environment switches a plan reads while it is built (A/B knobs): part of the plan key, so flipping one rebuilds the plan
     # (exactly the names _plan_switches reads, the engine's only reads - tests/test_host_logic.py holds the two together; the library's
-    #  own RHO_CONV_SPLITK is latched at its first launch, so no rebuild could follow it and it is not part of the key)
+    #  own RHO_CONV_SPLITK is latched at its first launch, so no rebuild could follow it and it is not part of the key; RHO_CONV_GEO is
+    #  latched the same way and listed all the same, so that plans built under different settings never share a key)
     _PLAN_ENV = ("RHO_TRAIN_MATERIALIZE", "RHO_MATERIALIZE_MIN_COUT", "RHO_PHASE_UPSAMPLE", "RHO_PHASE_UPSAMPLE_BWD", "RHO_PHASE_MIN_WGS",
                  "RHO_FOLD_SKIP", "RHO_S2_SPLIT", "RHO_S2_SPLIT_BWD", "RHO_FUSE_GN_BWD", "RHO_GEMM_ENDS", "RHO_DIRECT_ENDS",
-                 "RHO_FUSE_SKIP_DGRAD", "RHO_GEMM1X1")
+                 "RHO_FUSE_SKIP_DGRAD", "RHO_GEMM1X1", "RHO_CONV_GEO")
 
     @staticmethod
     def _plan_switches() -> PlanSwitches:
@@ -308,7 +309,10 @@ class UNetEngine:
             fuse_skip_dgrad=os.environ.get("RHO_FUSE_SKIP_DGRAD", "1") != "0",
             # read by the library at every conv query and launch (gemm1x1.h: k_gemm1x1 for the wide bf16 1x1x1 convs, 0 = k_conv);
             # recorded here so that a plan - its variant names and statistics rows - is rebuilt when the switch flips
-            gemm1x1=os.environ.get("RHO_GEMM1X1", "1") != "0")
+            gemm1x1=os.environ.get("RHO_GEMM1X1", "1") != "0",
+            # read by the library and latched at its first conv query (conv.hip: the compile-time 4 x 8 x 8 tile form of the bf16
+            # 3x3x3 k_conv variants, 0 = the generic form); recorded here so that plans are keyed on it like the other knobs
+            conv_geo=os.environ.get("RHO_CONV_GEO", "1") != "0")
 
     def _plan_signature(self) -> tuple:
         """Everything besides (shape, labels, mode) that is baked into a plan when it is built: the per-ResBlock ``use_checkpoint``
