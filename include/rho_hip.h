@@ -38,7 +38,7 @@ extern "C" {
  * rho_conv_desc grew; 3: round-3 additions; 9: the rho_gd_* / metrics entry points of csrc/gaussian.hip;
  * 10: learned variances - RHO_GD_LOG_BETA, the *_lv / strided / hybrid-loss entry points; the dataset entry points added since -
  * rho_crop_resize, rho_line_profile, rho_pil_resize_taps, rho_u8_image_batch, the guidance trio rho_p_sample_step_cfg,
- * rho_cond_keep_mask, rho_cond_drop - change no existing signature or struct, so by this
+ * rho_cond_keep_mask, rho_cond_drop, and the query rho_attention_variant - change no existing signature or struct, so by this
  * rule they leave it at 10: a binding that lacks them fails on the missing symbol).  A loader must compare rho_abi_version() with the header it was written against
  * before calling anything else (hip.py does; a build with all symbols but older signatures would be called with shifted arguments). */
 #define RHO_ABI_VERSION 10
@@ -860,6 +860,13 @@ int rho_add_inplace(void* dst, const void* src, int dtype, int64_t n, void* stre
 int rho_attention_bwd(const void* qk, const void* vt, const void* o, const void* dout, const float* lse,
                       float* delta_ws, void* dqk, int64_t dqk_row_stride, void* dv, int64_t dv_row_stride, int dtype,
                       int64_t batch, int64_t t, int64_t heads, int64_t ch, void* stream);
+
+/* Names of the kernels rho_attention_fwd (backward = 0) or rho_attention_bwd (backward != 0) launches for (dtype, ch), joined with
+ * '+' in launch order and written NUL-terminated into buf (cap >= 96): "k_attn_bf16<64,64>",
+ * "k_attn_delta<bf16>+k_attn_dq<64,64>+k_attn_dkv_fused<64,64>".  Answered on the host from the selection the launches themselves
+ * use (RHO_ATTN_F32_VALU and RHO_ATTN_DKV_SPLIT included, as latched on first use); nothing is launched and no GPU is needed.
+ * Returns what the launch would return for that (dtype, ch): 0, RHO_E_ARG (dtype) or RHO_E_SHAPE (head width). */
+int rho_attention_variant(int dtype, int64_t ch, int backward, char* buf, int cap);
 
 /* ------------------------------------------------------------------ legacy UNet ("UNet v1", rho_diffusion/models/unet.py:30-269)
  * The tail of AbstractUNetBlock.forward (unet.py:117-135) on channels-last [N, S, C] tensors of `dtype`:

@@ -14,8 +14,7 @@
 //   O^T[c][query] += V^T[c][key] * P^T[key][query]
 // with V^T read as plain 16-byte rows of 8 consecutive keys (A operand) -- no transposes, no LDS
 // round trip for P (cdna_hip_programming.md section 3, "An accumulator tile as the next MFMA's operand").
-#include <cstdlib>
-
+#include "attention_plan.h"
 #include "common.h"
 
 // max / sum of a value over the two half-waves of a column (lanes l and l ^ 32), in every lane: one v_permlane32_swap (gfx950: the
@@ -508,68 +507,64 @@ __global__ __launch_bounds__(256) void k_attn_f32m(const float* __restrict__ qk,
 extern "C" int rho_attention_fwd(const void* qk, const void* vt, void* out, float* lse, int dtype, int64_t batch, int64_t t,
                                  int64_t heads, int64_t ch, void* stream) {
     if (!qk || !vt || !out || batch <= 0 || t <= 0 || heads <= 0) return RHO_E_ARG;
-    if (dtype != RHO_BF16 && dtype != RHO_F32) return RHO_E_ARG;
+    const AttnPlan p = attn_plan(dtype, ch, false);
+    if (p.rc != 0) return p.rc;
     const int C = (int)(heads * ch);
     const float sl2 = (float)(1.4426950408889634 / sqrt((double)ch));
     hipStream_t st = as_stream(stream);
-    if (dtype == RHO_F32) {
-        // exact-f32 MFMA kernel (RHO_ATTN_F32_VALU=1 selects the round-1 VALU kernel: A/B and cross-check)
-        static const bool valu_env = getenv("RHO_ATTN_F32_VALU") && atoi(getenv("RHO_ATTN_F32_VALU")) != 0;
-        if (!valu_env) {
-            dim3 grid((unsigned)((t + 127) / 128), (unsigned)heads, (unsigned)batch), block(256);
-#define RHO_ATT32M(chv, ktv)                                                                                             \
-    case chv:                                                                                                            \
-        hipLaunchKernelGGL((k_attn_f32m<chv, ktv>), grid, block, 0, st, (const float*)qk, (const float*)vt, (float*)out, \
-                           (int)t, C, sl2, lse);                                                                         \
+    dim3 grid((unsigned)((t + p.rows - 1) / p.rows), (unsigned)heads, (unsigned)batch), block(256);
+    // the plan names (kind, ch, tile); the switches below only map it to the instantiation
+#define RHO_ATT(kernel, T_, chv, ktv)                                                                                        \
+    case RHO_ATTN_KEY(chv, ktv):                                                                                             \
+        hipLaunchKernelGGL((kernel<chv, ktv>), grid, block, 0, st, (const T_*)qk, (const T_*)vt, (T_*)out, (int)t, C, sl2, lse); \
         break;
-            switch (ch) {
-                RHO_ATT32M(16, 64)
-                RHO_ATT32M(32, 64)
-                RHO_ATT32M(64, 64)
-                RHO_ATT32M(128, 32)
-                RHO_ATT32M(256, 32)
+    switch (p.kind) {
+        case ATTN_FWD_BF16:
+            switch (RHO_ATTN_KEY(p.ch, p.kt)) {
+                RHO_ATT(k_attn_bf16, bf16_raw, 16, 64)
+                RHO_ATT(k_attn_bf16, bf16_raw, 32, 64)
+                RHO_ATT(k_attn_bf16, bf16_raw, 64, 64)
+                RHO_ATT(k_attn_bf16, bf16_raw, 128, 64)
+                RHO_ATT(k_attn_bf16, bf16_raw, 256, 32)
                 default:
                     return RHO_E_SHAPE;
             }
-#undef RHO_ATT32M
-            RHO_LAUNCH_CHECK();
-            return 0;
-        }
-        dim3 grid((unsigned)((t + 63) / 64), (unsigned)heads, (unsigned)batch), block(256);
-#define RHO_ATT32(chv, ktv)                                                                                             \
-    case chv:                                                                                                           \
-        hipLaunchKernelGGL((k_attn_f32<chv, ktv>), grid, block, 0, st, (const float*)qk, (const float*)vt, (float*)out, \
-                           (int)t, C, sl2, lse);                                                                        \
-        break;
-        switch (ch) {
-            RHO_ATT32(16, 64)
-            RHO_ATT32(32, 64)
-            RHO_ATT32(64, 64)
-            RHO_ATT32(128, 32)
-            RHO_ATT32(256, 16)
-            default:
-                return RHO_E_SHAPE;
-        }
-#undef RHO_ATT32
-        RHO_LAUNCH_CHECK();
-        return 0;
-    }
-    dim3 grid((unsigned)((t + 127) / 128), (unsigned)heads, (unsigned)batch), block(256);
-#define RHO_ATT(chv)                                                                                                      \
-    case chv:                                                                                                             \
-        hipLaunchKernelGGL((k_attn_bf16<chv, (chv >= 256 ? 32 : 64)>), grid, block, 0, st, (const bf16_raw*)qk,              \
-                           (const bf16_raw*)vt, (bf16_raw*)out, (int)t, C, sl2, lse);                                     \
-        break;
-    switch (ch) {
-        RHO_ATT(16)
-        RHO_ATT(32)
-        RHO_ATT(64)
-        RHO_ATT(128)
-        RHO_ATT(256)
+            break;
+        case ATTN_FWD_F32M:
+            switch (RHO_ATTN_KEY(p.ch, p.kt)) {
+                RHO_ATT(k_attn_f32m, float, 16, 64)
+                RHO_ATT(k_attn_f32m, float, 32, 64)
+                RHO_ATT(k_attn_f32m, float, 64, 64)
+                RHO_ATT(k_attn_f32m, float, 128, 32)
+                RHO_ATT(k_attn_f32m, float, 256, 32)
+                default:
+                    return RHO_E_SHAPE;
+            }
+            break;
+        case ATTN_FWD_F32:
+            switch (RHO_ATTN_KEY(p.ch, p.kt)) {
+                RHO_ATT(k_attn_f32, float, 16, 64)
+                RHO_ATT(k_attn_f32, float, 32, 64)
+                RHO_ATT(k_attn_f32, float, 64, 64)
+                RHO_ATT(k_attn_f32, float, 128, 32)
+                RHO_ATT(k_attn_f32, float, 256, 16)
+                default:
+                    return RHO_E_SHAPE;
+            }
+            break;
         default:
             return RHO_E_SHAPE;
     }
 #undef RHO_ATT
     RHO_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int rho_attention_variant(int dtype, int64_t ch, int backward, char* buf, int cap) {
+    if (!buf || cap < 96) return RHO_E_ARG;
+    buf[0] = 0;
+    const AttnPlan p = attn_plan(dtype, ch, backward != 0);
+    if (p.rc != 0) return p.rc;
+    attn_plan_name(p, buf, cap);
     return 0;
 }

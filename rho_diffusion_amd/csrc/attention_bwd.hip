@@ -14,8 +14,7 @@
 // used directly as the next MFMA's B operand (accumulator-as-operand, rows permuted by pi), and every
 // operand that needs the contraction index contiguous is fetched from the row-major LDS tiles with the
 // transposing read ds_read_b64_tr_b16.
-#include <cstdlib>
-
+#include "attention_plan.h"
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
@@ -1066,14 +1065,14 @@ extern "C" int rho_attention_bwd(const void* qk, const void* vt, const void* o, 
                                  float* delta_ws, void* dqk, int64_t dqk_row_stride, void* dv, int64_t dv_row_stride, int dtype,
                                  int64_t batch, int64_t t, int64_t heads, int64_t ch, void* stream) {
     if (!qk || !vt || !o || !dout || !lse || !delta_ws || !dqk || !dv || batch <= 0 || t <= 0 || heads <= 0) return RHO_E_ARG;
-    if (dtype != RHO_BF16 && dtype != RHO_F32) return RHO_E_ARG;
+    const AttnPlan p = attn_plan(dtype, ch, true);
+    if (p.rc != 0) return p.rc;
     const int C = (int)(heads * ch);
     const int qrs = (int)(dqk_row_stride > 0 ? dqk_row_stride : 2 * C), vrs = (int)(dv_row_stride > 0 ? dv_row_stride : C);
     const float scale = (float)(1.0 / sqrt((double)ch));
     const float sl2 = (float)(1.4426950408889634 / sqrt((double)ch));
     hipStream_t st = as_stream(stream);
-    const int pe = dtype == RHO_BF16 ? 8 : 4;
-    if (ch % pe != 0 || ch / pe > 64 || ((ch / pe) & (ch / pe - 1)) != 0) return RHO_E_SHAPE;
+    const int pe = dtype == RHO_BF16 ? 8 : 4;      // elements per 16-byte piece; ch / pe lanes per head, a power of two <= 64
     const int64_t nd = batch * t * heads * (ch / pe);
     if (dtype == RHO_BF16)
         hipLaunchKernelGGL(k_attn_delta<bf16_raw>, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, (const bf16_raw*)o,
@@ -1082,10 +1081,10 @@ extern "C" int rho_attention_bwd(const void* qk, const void* vt, const void* o, 
         hipLaunchKernelGGL(k_attn_delta<float>, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, (const float*)o,
                            (const float*)dout, delta_ws, batch * t, (int)heads, (int)ch, t);
     RHO_LAUNCH_CHECK();
-    if (dtype == RHO_BF16) {
-        dim3 grid((unsigned)((t + 127) / 128), (unsigned)heads, (unsigned)batch), block(256);
+    dim3 grid((unsigned)((t + p.rows - 1) / p.rows), (unsigned)heads, (unsigned)batch), block(256);
+    // the plan names (kind, ch, tile); the switches below only map it to the instantiations
 #define RHO_ATTB(chv, ktv)                                                                                                     \
-    case chv:                                                                                                                  \
+    case RHO_ATTN_KEY(chv, ktv):                                                                                               \
         hipLaunchKernelGGL((k_attn_dq<chv, ktv>), grid, block, 0, st, (const bf16_raw*)qk, (const bf16_raw*)vt,                  \
                            (const bf16_raw*)dout, lse, delta_ws, (bf16_raw*)dqk, (int)t, C, sl2, scale, qrs);                   \
         hipLaunchKernelGGL((k_attn_dkv<chv, ktv, 0>), grid, block, 0, st, (const bf16_raw*)qk, (const bf16_raw*)vt,              \
@@ -1093,23 +1092,30 @@ extern "C" int rho_attention_bwd(const void* qk, const void* vt, const void* o, 
         hipLaunchKernelGGL((k_attn_dkv<chv, ktv, 1>), grid, block, 0, st, (const bf16_raw*)qk, (const bf16_raw*)vt,              \
                            (const bf16_raw*)dout, lse, delta_ws, (bf16_raw*)dqk, (int)t, C, sl2, scale, qrs, C);                 \
         break;
-        // ch = 64 (c5's heads): dQ + the fused dK / dV kernel; RHO_ATTN_DKV_SPLIT=1 keeps the r2 pair (A/B).  ch = 128 (c3) stays on the
-        // pair: fused it needs 128 accumulator + 32 K-fragment + 32 score registers + operands > 256 per wave at two waves per SIMD
-        // (hipcc: 276 bytes of scratch per lane), and one wave per SIMD is what r2 measured as slower than the extra S recompute.
-        static const bool split_env = getenv("RHO_ATTN_DKV_SPLIT") && atoi(getenv("RHO_ATTN_DKV_SPLIT")) != 0;
 #define RHO_ATTBF(chv, ktv)                                                                                                    \
-    case chv:                                                                                                                  \
+    case RHO_ATTN_KEY(chv, ktv):                                                                                               \
         hipLaunchKernelGGL((k_attn_dq<chv, ktv>), grid, block, 0, st, (const bf16_raw*)qk, (const bf16_raw*)vt,                  \
                            (const bf16_raw*)dout, lse, delta_ws, (bf16_raw*)dqk, (int)t, C, sl2, scale, qrs);                   \
         hipLaunchKernelGGL((k_attn_dkv_fused<chv, ktv>), grid, block, 0, st, (const bf16_raw*)qk, (const bf16_raw*)vt,           \
                            (const bf16_raw*)dout, lse, delta_ws, (bf16_raw*)dqk, (bf16_raw*)dv, (int)t, C, sl2, scale, qrs, vrs); \
         break;
-        if (!split_env && ch == 64) {
-            switch (ch) {
+#define RHO_ATTB32(dqk_, dkv_, chv, ktv)                                                                                       \
+    case RHO_ATTN_KEY(chv, ktv):                                                                                               \
+        hipLaunchKernelGGL((dqk_<chv, ktv>), grid, block, 0, st, (const float*)qk, (const float*)vt,                           \
+                           (const float*)dout, lse, delta_ws, (float*)dqk, (int)t, C, sl2, scale, qrs);                        \
+        hipLaunchKernelGGL((dkv_<chv, ktv>), grid, block, 0, st, (const float*)qk, (const float*)vt,                           \
+                           (const float*)dout, lse, delta_ws, (float*)dqk, (float*)dv, (int)t, C, sl2, scale, qrs, vrs);       \
+        break;
+    switch (p.kind) {
+        case ATTN_BWD_FUSED:
+            switch (RHO_ATTN_KEY(p.ch, p.kt)) {
                 RHO_ATTBF(64, 64)
+                default:
+                    return RHO_E_SHAPE;
             }
-        } else {
-            switch (ch) {
+            break;
+        case ATTN_BWD_PAIR:
+            switch (RHO_ATTN_KEY(p.ch, p.kt)) {
                 RHO_ATTB(16, 64)
                 RHO_ATTB(32, 64)
                 RHO_ATTB(64, 64)
@@ -1118,48 +1124,34 @@ extern "C" int rho_attention_bwd(const void* qk, const void* vt, const void* o, 
                 default:
                     return RHO_E_SHAPE;
             }
-        }
+            break;
+        case ATTN_BWD_F32M:
+            switch (RHO_ATTN_KEY(p.ch, p.kt)) {
+                RHO_ATTB32(k_attn_dq_f32m, k_attn_dkv_f32m, 16, 64)
+                RHO_ATTB32(k_attn_dq_f32m, k_attn_dkv_f32m, 32, 64)
+                RHO_ATTB32(k_attn_dq_f32m, k_attn_dkv_f32m, 64, 32)
+                RHO_ATTB32(k_attn_dq_f32m, k_attn_dkv_f32m, 128, 32)
+                default:
+                    return RHO_E_SHAPE;
+            }
+            break;
+        case ATTN_BWD_F32:
+            switch (RHO_ATTN_KEY(p.ch, p.kt)) {
+                RHO_ATTB32(k_attn_dq_f32, k_attn_dkv_f32, 16, 64)
+                RHO_ATTB32(k_attn_dq_f32, k_attn_dkv_f32, 32, 64)
+                RHO_ATTB32(k_attn_dq_f32, k_attn_dkv_f32, 64, 64)
+                RHO_ATTB32(k_attn_dq_f32, k_attn_dkv_f32, 128, 32)
+                RHO_ATTB32(k_attn_dq_f32, k_attn_dkv_f32, 256, 16)
+                default:
+                    return RHO_E_SHAPE;
+            }
+            break;
+        default:
+            return RHO_E_SHAPE;
+    }
+#undef RHO_ATTB32
 #undef RHO_ATTBF
 #undef RHO_ATTB
-    } else if (!(getenv("RHO_ATTN_F32_VALU") && atoi(getenv("RHO_ATTN_F32_VALU")) != 0) && ch <= 128) {
-        // exact-f32 MFMA pair (ch = 256 keeps the VALU pair: two 128-register accumulators + fragments do not fit a wave)
-        dim3 grid((unsigned)((t + 127) / 128), (unsigned)heads, (unsigned)batch), block(256);
-#define RHO_ATTB32M(chv, ktv)                                                                                                 \
-    case chv:                                                                                                                 \
-        hipLaunchKernelGGL((k_attn_dq_f32m<chv, ktv>), grid, block, 0, st, (const float*)qk, (const float*)vt,                 \
-                           (const float*)dout, lse, delta_ws, (float*)dqk, (int)t, C, sl2, scale, qrs);                        \
-        hipLaunchKernelGGL((k_attn_dkv_f32m<chv, ktv>), grid, block, 0, st, (const float*)qk, (const float*)vt,                \
-                           (const float*)dout, lse, delta_ws, (float*)dqk, (float*)dv, (int)t, C, sl2, scale, qrs, vrs);       \
-        break;
-        switch (ch) {
-            RHO_ATTB32M(16, 64)
-            RHO_ATTB32M(32, 64)
-            RHO_ATTB32M(64, 32)
-            RHO_ATTB32M(128, 32)
-            default:
-                return RHO_E_SHAPE;
-        }
-#undef RHO_ATTB32M
-    } else {
-        dim3 grid((unsigned)((t + 63) / 64), (unsigned)heads, (unsigned)batch), block(256);
-#define RHO_ATTB32(chv, ktv)                                                                                                  \
-    case chv:                                                                                                                 \
-        hipLaunchKernelGGL((k_attn_dq_f32<chv, ktv>), grid, block, 0, st, (const float*)qk, (const float*)vt,                  \
-                           (const float*)dout, lse, delta_ws, (float*)dqk, (int)t, C, sl2, scale, qrs);                        \
-        hipLaunchKernelGGL((k_attn_dkv_f32<chv, ktv>), grid, block, 0, st, (const float*)qk, (const float*)vt,                 \
-                           (const float*)dout, lse, delta_ws, (float*)dqk, (float*)dv, (int)t, C, sl2, scale, qrs, vrs);       \
-        break;
-        switch (ch) {
-            RHO_ATTB32(16, 64)
-            RHO_ATTB32(32, 64)
-            RHO_ATTB32(64, 64)
-            RHO_ATTB32(128, 32)
-            RHO_ATTB32(256, 16)
-            default:
-                return RHO_E_SHAPE;
-        }
-#undef RHO_ATTB32
-    }
     RHO_LAUNCH_CHECK();
     return 0;
 }

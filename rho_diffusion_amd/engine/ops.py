@@ -1132,6 +1132,14 @@ def attention(qk: Tensor, vt: Tensor, heads: int, out: Optional[Tensor] = None, 
     return out
 
 
+def attention_variant(dtype: torch.dtype, ch: int, backward: bool = False) -> str:
+    """Names of the kernels ``attention`` (``attention_bwd`` with ``backward``) launches for this dtype and head width, joined
+    with ``+`` in launch order (nothing is launched, no GPU is needed)."""
+    buf = C.create_string_buffer(128)
+    check(hip.lib().rho_attention_variant(dtype_code(dtype), int(ch), int(bool(backward)), buf, 128), "rho_attention_variant")
+    return buf.value.decode()
+
+
 # ============================================================================= backward ops
 def prep_conv_weight_dgrad(w: Tensor, dtype: torch.dtype, col_src: Optional[Tensor] = None,
                            out: Optional[Tensor] = None) -> Tensor:

@@ -132,6 +132,7 @@ SIGNATURES = {
     "rho_tap_gather_sum": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int64, c_void_p, c_void_p,
                                    c_void_p]),
     "rho_attention_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "rho_attention_variant": (c_int, [c_int, c_int64, c_int, C.c_char_p, c_int]),
     # ---- backward
     "rho_conv_nd_wgrad": (c_int, [C.POINTER(ConvDesc), c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "rho_conv_nd_wgrad_ws": (c_int, [C.POINTER(ConvDesc), c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
