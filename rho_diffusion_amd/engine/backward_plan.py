@@ -152,29 +152,20 @@ class BackwardBuilder:
             return
         entries, params = self.fin_entries, self.fin_params
         self.fin_entries, self.fin_params, self.fin_bytes = [], [], 0
-        state = {"sig": None, "dev": None, "blocks": 0}
-        L, dev = self.L, self.dev
+        table = ops.WfinTable(self.dev)
+        for e in entries:
+            table.add(**e)
+        state = {"sig": None}
 
         def run(s):
+            # (pointers resolved at launch time: the arena is allocated after the plan is built, optimizers may re-home .grad)
             sig = (self.arena.data_ptr(),) + tuple(pgrad(e["param"]) for e in entries)
             if sig != state["sig"]:
-                raw, blk = [], 0
-                for e in entries:
-                    op = hip.WfinOp()
-                    op.dw, op.grad, op.row_src = self.arena.data_ptr() + 4 * e["off"], pgrad(e["param"]), e["rs"]
-                    op.cout, op.cin, op.coutp, op.cinb = e["cout"], e["cin"], e["coutp"], e["cinb"]
-                    op.kd, op.kh, op.kw = e["k"]
-                    op.total = e["cout"] * e["cin"] * e["k"][0] * e["k"][1] * e["k"][2]
-                    op.kind, op.up_h, op.up_w, op.phase_stride = e["kind"], e.get("up_h", 0), e.get("up_w", 0), e.get("stride", 0)
-                    op.nblk = max(1, min((op.total + 255) // 256, 512))
-                    op.blk0 = blk
-                    blk += op.nblk
-                    raw.append(bytes(op))
-                state["dev"] = torch.frombuffer(bytearray(b"".join(raw)), dtype=torch.uint8).to(dev)
-                state["blocks"], state["sig"] = blk, sig
-            return L.rho_wgrad_finalize_batch(state["dev"].data_ptr(), len(entries), state["blocks"], s)
+                table.build(sig[0], sig[1:])
+                state["sig"] = sig
+            return table.launch(s)
         self.emit(run, "wgrad_finalize", nbytes=12.0 * sum(e["cout"] * e["cin"] * e["k"][0] * e["k"][1] * e["k"][2] for e in entries))
-        self.plan.keep.append(state)
+        self.plan.keep.append(table)
         self.mark(params)
 
     def wgrad_call(self, d, dy_ptr: int, w_: int, dw_ptr: Callable[[], int], db_ptr: Callable[[], int]):

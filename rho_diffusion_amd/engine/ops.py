@@ -936,6 +936,56 @@ class PrepTable:
         check(hip.lib().rho_prep_batch(self._dev.data_ptr(), len(self.ops), self._blocks, stream()), "rho_prep_batch")
 
 
+class WfinTable:
+    """Device table of rho_wfin_op for rho_wgrad_finalize_batch: the accumulation regions of one arena into parameter gradients in
+    one launch.  ``add`` records one region (offsets in floats from the arena's base), ``build`` resolves the pointers - the arena
+    and the gradients may move between launches - and uploads the table, ``launch`` runs it."""
+
+    def __init__(self, device):
+        self.device = device
+        self.entries: list = []
+        self._dev = None
+        self._blocks = 0
+
+    def add(self, *, kind, off, cout, cin, coutp, cinb, k, rs=None, up_h=0, up_w=0, stride=0, nblk=None, **extra):
+        """kind 0: [taps][coutp][cinb] -> grad[row_src(r)][ci][tap] (``rs``: pointer of an int32 row table or None);  kind 1: all
+        sub-pixel phases (``stride`` floats apart) into the 3-tap gradient;  kind 2: the one-channel head's [tap][ci] rows with
+        mirrored taps.  ``nblk`` overrides the op's share of the launch; other keywords (the owning parameter) are kept with the
+        entry and not read here."""
+        self.entries.append(dict(extra, kind=kind, off=off, rs=rs, cout=cout, cin=cin, coutp=coutp, cinb=cinb, k=tuple(k), up_h=up_h,
+                                 up_w=up_w, stride=stride, nblk=nblk))
+        self._dev = None
+
+    def records(self, arena_ptr: int, grad_ptrs) -> list:
+        """The host-side rho_wfin_op records (blk0 ascending and contiguous, op 0 at 0) and, as a side effect, the launch's blocks."""
+        if len(grad_ptrs) != len(self.entries):
+            raise RhoHipError(f"WfinTable: {len(grad_ptrs)} gradient pointers for {len(self.entries)} entries")
+        recs, blk = [], 0
+        for e, g in zip(self.entries, grad_ptrs):
+            op = hip.WfinOp()
+            op.dw, op.grad, op.row_src = arena_ptr + 4 * e["off"], g, e["rs"]
+            op.cout, op.cin, op.coutp, op.cinb = e["cout"], e["cin"], e["coutp"], e["cinb"]
+            op.kd, op.kh, op.kw = e["k"]
+            op.total = e["cout"] * e["cin"] * e["k"][0] * e["k"][1] * e["k"][2]
+            op.kind, op.up_h, op.up_w, op.phase_stride = e["kind"], e["up_h"], e["up_w"], e["stride"]
+            op.nblk = max(1, min((op.total + 255) // 256, 512)) if e["nblk"] is None else int(e["nblk"])
+            op.blk0 = blk
+            blk += op.nblk
+            recs.append(op)
+        self._blocks = blk
+        return recs
+
+    def build(self, arena_ptr: int, grad_ptrs) -> None:
+        raw = b"".join(bytes(op) for op in self.records(arena_ptr, grad_ptrs))
+        self._dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
+
+    def launch(self, s=None) -> int:
+        """Enqueue the launch on stream ``s`` (default: the current one) and return the library's status code."""
+        if self._dev is None:
+            raise RhoHipError("WfinTable.launch before build")
+        return hip.lib().rho_wgrad_finalize_batch(self._dev.data_ptr(), len(self.entries), self._blocks, stream() if s is None else s)
+
+
 # ----------------------------------------------------------------------------- GroupNorm
 def gn_nblk(s: int) -> int:
     return int(hip.lib().rho_gn_nblk(s))

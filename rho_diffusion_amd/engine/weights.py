@@ -143,6 +143,7 @@ class _ConvW:
                 if self.row_src is not None:
                     b = b[self.row_src.long()]           # gather (data movement only)
                 t[: b.numel()].copy_(b)
+                t[b.numel():].zero_()                    # (the padded rows, as the batched gather writes them)
             elif kind == "dgrad":
                 ops.prep_conv_weight_dgrad(w, self.dtype, self.row_src, out=t)
             elif kind == "phase":
