@@ -38,7 +38,8 @@ extern "C" {
  * rho_conv_desc grew; 3: round-3 additions; 9: the rho_gd_* / metrics entry points of csrc/gaussian.hip;
  * 10: learned variances - RHO_GD_LOG_BETA, the *_lv / strided / hybrid-loss entry points; the dataset entry points added since -
  * rho_crop_resize, rho_line_profile, rho_pil_resize_taps, rho_u8_image_batch, the guidance trio rho_p_sample_step_cfg,
- * rho_cond_keep_mask, rho_cond_drop, and the query rho_attention_variant - change no existing signature or struct, so by this
+ * rho_cond_keep_mask, rho_cond_drop, the query rho_attention_variant, and the spaced-walk pair rho_p_sample_step_spaced,
+ * rho_spaced_advance - change no existing signature or struct, so by this
  * rule they leave it at 10: a binding that lacks them fails on the missing symbol).  A loader must compare rho_abi_version() with the header it was written against
  * before calling anything else (hip.py does; a build with all symbols but older signatures would be called with shifted arguments). */
 #define RHO_ABI_VERSION 10
@@ -78,6 +79,28 @@ int rho_p_sample_step_cfg(float* x2, const float* eps2, const float* z, const fl
 /* Device-resident loop state of reverse_process (ddpm.py:195): *t_dev -= 1 and *offset_dev += delta,
  * so that one captured HIP graph replays every step without host involvement. Either may be NULL. */
 int rho_step_advance(int32_t* t_dev, uint64_t* offset_dev, uint64_t delta, void* stream);
+
+/* One reverse update of a few-step walk on a spaced timestep sequence tau_0 < ... < tau_{S-1} (DDIM with eta, Song et al. 2021; the
+ * reference's DDPM, ddpm.py:132-229, can only walk every timestep).  rows float32 [S, 8] on the device, row k for t = tau_k with
+ * ab = alpha_bar[tau_k], ab_prev = alpha_bar[tau_{k-1}] (1 for k = 0):
+ *   {c_recip = sqrt(1/ab), c_recipm1 = sqrt(1/ab - 1), sqrt_ab, inv_sqrt_1mab = 1/sqrt(1 - ab) (0 where 1 - ab == 0),
+ *    sqrt_abp = sqrt(ab_prev), sigma (0 where 1 - ab == 0), coef_eps = sqrt(max(1 - ab_prev - sigma^2, 0)), 0}.
+ * k is read from *k_dev (int32[1], device): one captured graph serves every step; k outside [0, S) writes nothing.
+ * guided == 0: x, eps_hat float32 [n], e = eps_hat.  guided != 0: both float32 [2, n] as in rho_p_sample_step_cfg,
+ * e = fma(scale, e_c - e_u, e_u), the result stored to both rows of x.  z float32 [n] or NULL; noise enters iff z != NULL and the
+ * row's sigma != 0, otherwise z is not read.  The arithmetic, one contraction shared by the 16-byte body, its tail and the scalar loop
+ * (the 16-byte form needs 16-byte aligned x / eps_hat / z and, guided, n % 4 == 0; every other case gives the same bits):
+ *   x0 = fma(c_recip, x, -(c_recipm1 * e))
+ *   clip != 0:  x0 = clamp(x0, -1, 1);  ep = fma(-sqrt_ab, x0, x) * inv_sqrt_1mab        clip == 0:  ep = e
+ *   x <- fma(sqrt_abp, x0, fma(coef_eps, ep, sigma * z))
+ * and x <- sqrt_abp * x0, ep not formed, where the row has coef_eps == 0 and sigma == 0 (always row 0: the last step returns the
+ * x0 estimate; at alpha_bar == 1 ep would be 0 * NaN). */
+int rho_p_sample_step_spaced(float* x, const float* eps_hat, const float* z, const float* rows, const int32_t* k_dev, int32_t S,
+                             int64_t n, int guided, float scale, int clip, void* stream);
+
+/* Loop state of the spaced walk: k = *k_dev - 1; *k_dev = k; if k >= 0, *t_dev = taus[k] (int32 [S], device; taus[-1] is never read,
+ * *t_dev keeps its last value); if offset_dev != NULL, *offset_dev += delta.  k_dev, t_dev and taus must not be NULL. */
+int rho_spaced_advance(int32_t* k_dev, int32_t* t_dev, const int32_t* taus, uint64_t* offset_dev, uint64_t delta, void* stream);
 
 /* Counter-based Philox4x32-10 standard normals (Box-Muller), replaces torch.randn_like at
  * ddpm.py:101-102,171,197.  out float32[n]; stream of (seed, offset) is reproducible and

@@ -223,6 +223,115 @@ extern "C" int rho_step_advance(int32_t* t_dev, uint64_t* offset_dev, uint64_t d
     return 0;
 }
 
+// ----------------------------------------------------------------------------- p_sample_step on a spaced timestep sequence
+// Few-step sampling (DDIM with eta; the reference's DDPM has no such sampler).  rows = float32 [S, 8], row k for t = tau_k:
+// {sqrt(1/ab), sqrt(1/ab - 1), sqrt(ab), 1/sqrt(1 - ab), sqrt(ab_prev), sigma, sqrt(1 - ab_prev - sigma^2), 0}; k read on the device
+// so that one captured graph serves every step, k outside [0, S) => nothing is written.  Noise enters iff z != NULL and the row's
+// sigma != 0, else z is not read.  One written-out contraction for the 16-byte body, its tail and the scalar loop:
+//   x0 = fma(c_recip, x, -(c_recipm1 * e));   clip: x0 = clamp(x0, -1, 1), ep = fma(-sqrt_ab, x0, x) * inv_sqrt_1mab;   else ep = e
+//   r  = fma(sqrt_abp, x0, fma(coef_eps, ep, sigma * z))
+// and r = sqrt_abp * x0 where the row has coef_eps == 0 and sigma == 0 (row 0 always; ep is not formed: at alpha_bar == 1 it is 0/0).
+struct SpacedRow {
+    float c_recip, c_recipm1, sqrt_ab, inv_sqrt_1mab, sqrt_abp, sigma, coef_eps;
+    int clip, x0_only;
+};
+__device__ __forceinline__ float spaced_update(const SpacedRow& c, float x, float e, float z) {
+    float x0 = __fmaf_rn(c.c_recip, x, -(c.c_recipm1 * e));
+    if (c.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    if (c.x0_only) return c.sqrt_abp * x0;
+    const float ep = c.clip ? __fmaf_rn(-c.sqrt_ab, x0, x) * c.inv_sqrt_1mab : e;
+    return __fmaf_rn(c.sqrt_abp, x0, __fmaf_rn(c.coef_eps, ep, c.sigma * z));
+}
+__device__ __forceinline__ float cfg_mix(float s, float ec, float eu) { return __fmaf_rn(s, ec - eu, eu); }
+// GUIDED: x and eh hold [2, n] as in k_p_sample_cfg - row 1 starts n elements behind row 0, so the caller grants the 16-byte form
+// (vec) only for n % 4 == 0 there; the plain form takes any n with aligned bases and finishes with a scalar tail.
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void k_p_sample_spaced(float* __restrict__ x, const float* __restrict__ eh,
+                                                         const float* __restrict__ z, const float* __restrict__ rows,
+                                                         const int32_t* __restrict__ k_dev, int32_t S, float s, int64_t n, int clip,
+                                                         int vec) {
+    const int k = *k_dev;
+    if (k < 0 || k >= S) return;
+    const float* row = rows + 8 * (int64_t)k;
+    // the whole row up front, unconditionally: one scalar load behind k instead of a chain of dependent ones behind each test
+    const float r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3], r4 = row[4], r5 = row[5], r6 = row[6];
+    SpacedRow c;
+    c.c_recip = r0, c.c_recipm1 = r1, c.sqrt_ab = r2, c.inv_sqrt_1mab = r3, c.sqrt_abp = r4;
+    c.coef_eps = r6;
+    c.clip = clip;
+    c.x0_only = ((r6 == 0.0f) & (r5 == 0.0f)) ? 1 : 0;
+    const bool noisy = (z != nullptr) & (r5 != 0.0f);
+    c.sigma = noisy ? r5 : 0.0f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t done = 0;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        float4* xa = (float4*)x;
+        float4* xb = (float4*)(x + n);
+        const float4* ea = (const float4*)eh;
+        const float4* eb = (const float4*)(eh + n);
+        const float4* z4 = (const float4*)z;
+        for (int64_t i = tid; i < n4; i += stride) {
+            float4 a = xa[i];
+            float4 e = ea[i];
+            if (GUIDED) {
+                const float4 eu = eb[i];
+                e.x = cfg_mix(s, e.x, eu.x), e.y = cfg_mix(s, e.y, eu.y), e.z = cfg_mix(s, e.z, eu.z), e.w = cfg_mix(s, e.w, eu.w);
+            }
+            float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (noisy) zz = z4[i];
+            a.x = spaced_update(c, a.x, e.x, zz.x);
+            a.y = spaced_update(c, a.y, e.y, zz.y);
+            a.z = spaced_update(c, a.z, e.z, zz.z);
+            a.w = spaced_update(c, a.w, e.w, zz.w);
+            xa[i] = a;
+            if (GUIDED) xb[i] = a;
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + tid; i < n; i += stride) {
+        const float zz = noisy ? z[i] : 0.0f;
+        const float e = GUIDED ? cfg_mix(s, eh[i], eh[n + i]) : eh[i];
+        const float r = spaced_update(c, x[i], e, zz);
+        x[i] = r;
+        if (GUIDED) x[n + i] = r;
+    }
+}
+
+extern "C" int rho_p_sample_step_spaced(float* x, const float* eps_hat, const float* z, const float* rows, const int32_t* k_dev,
+                                        int32_t S, int64_t n, int guided, float scale, int clip, void* stream) {
+    if (!x || !eps_hat || !rows || !k_dev || S <= 0 || n <= 0) return RHO_E_ARG;
+    const bool aligned = (((uintptr_t)x | (uintptr_t)eps_hat | (uintptr_t)z) & 15) == 0;
+    const int vec = (aligned && (!guided || n % 4 == 0)) ? 1 : 0;
+    const dim3 grid(grid_for(vec ? (n + 3) / 4 : n, 256)), block(256);
+    if (guided)
+        hipLaunchKernelGGL(k_p_sample_spaced<true>, grid, block, 0, as_stream(stream), x, eps_hat, z, rows, k_dev, S, scale, n,
+                           clip ? 1 : 0, vec);
+    else
+        hipLaunchKernelGGL(k_p_sample_spaced<false>, grid, block, 0, as_stream(stream), x, eps_hat, z, rows, k_dev, S, 0.0f, n,
+                           clip ? 1 : 0, vec);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
+// k <- k - 1, t <- taus[k] while k >= 0 (taus[-1] is never read; t keeps its last value), philox offset += delta
+__global__ void k_spaced_advance(int32_t* k_dev, int32_t* t_dev, const int32_t* taus, uint64_t* offset_dev, uint64_t delta) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const int32_t k = *k_dev - 1;
+        *k_dev = k;
+        if (k >= 0) *t_dev = taus[k];
+        if (offset_dev) *offset_dev += delta;
+    }
+}
+extern "C" int rho_spaced_advance(int32_t* k_dev, int32_t* t_dev, const int32_t* taus, uint64_t* offset_dev, uint64_t delta,
+                                  void* stream) {
+    if (!k_dev || !t_dev || !taus) return RHO_E_ARG;
+    hipLaunchKernelGGL(k_spaced_advance, dim3(1), dim3(64), 0, as_stream(stream), k_dev, t_dev, taus, offset_dev, delta);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
 // ----------------------------------------------------------------------------- Philox4x32-10 normals
 __device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float& a, float& b) {
     const float f0 = ((float)(u0 >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)

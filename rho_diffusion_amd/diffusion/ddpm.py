@@ -11,6 +11,8 @@ The arithmetic runs in the HIP kernels of librho_hip.so:
   * loss           -> rho_mse
   * guidance       -> classifier-free (not in the reference): label dropout in training_step (rho_cond_keep_mask draws, the
                       engine's rho_cond_drop applies), guided sampling at batch 2B with rho_p_sample_step_cfg
+  * few steps      -> DDIM with eta on a spaced timestep sequence (not in the reference): reverse_process(num_steps=, eta=) walks
+                      S of the T timesteps with rho_p_sample_step_spaced / rho_spaced_advance; host side in spaced.py
 Reference quirks are kept deliberately: 0.8*sqrt(beta) noise scale, z = 0 for t <= 1,
 no update at t = 0 although the backbone is evaluated, clamp to [-1, 1] after every update,
 checkpoint spacing T // 10.
@@ -28,6 +30,7 @@ from ..engine import ops
 from ..registry import registry
 from ..utils import sample_from_discrete_parameter_space, save_model_checkpoint
 from .abstract_diffusion import AbstractDiffusionPipeline
+from .spaced import resolve_timesteps, spaced_checkpoints, spaced_coefficients
 
 __all__ = ["DDPM"]
 
@@ -37,7 +40,7 @@ class DDPM(AbstractDiffusionPipeline):
                  cond_fn: str = None, cond_fn_kwargs: dict = None, optimizer=None,
                  opt_kwargs: Union[Mapping[str, Any], None] = {}, t_checkpoints=None, sampling_batch_size=10,
                  sample_every_n_epochs=5, sample_parameter_space=None, save_checkpoint_every_n_epochs=10,
-                 guidance_scale=None, cond_drop_prob: float = 0.0):
+                 sampling_steps=None, sampling_eta: float = 0.0, guidance_scale=None, cond_drop_prob: float = 0.0):
         super().__init__(backbone=backbone, backbone_kwargs=backbone_kwargs, schedule=schedule, timesteps=timesteps,
                          cond_fn=cond_fn, cond_fn_kwargs=cond_fn_kwargs, optimizer=optimizer, opt_kwargs=opt_kwargs)
         if isinstance(loss_func, str):
@@ -59,6 +62,12 @@ class DDPM(AbstractDiffusionPipeline):
             raise ValueError(f"cond_drop_prob must lie in [0, 1): got {cond_drop_prob} (at 1 no sample would ever see its labels)")
         self.cond_drop_prob = cond_drop_prob
         self.guidance_scale = None if guidance_scale is None else float(guidance_scale)
+        # few-step sampling: the defaults of reverse_process(num_steps=, eta=), so generate() / p_sample() / on_train_epoch_end
+        # follow them.  None walks every timestep with the reference's update; a count or an explicit increasing sequence of
+        # timesteps takes the DDIM update on those (eta = 0 deterministic, eta = 1 the ancestral variance).  Checked on first use.
+        self.sampling_steps = sampling_steps
+        self.sampling_eta = float(sampling_eta)
+        self._spaced_cache = {}
         # counter-based RNG state: one stream per rank (seed + rank), offset advances per draw
         self.noise_seed = int(os.environ.get("RHO_SEED", "777")) + int(os.environ.get("RANK", "0"))
         self._noise_offset = 0
@@ -118,15 +127,27 @@ class DDPM(AbstractDiffusionPipeline):
             raise ValueError("guidance_scale needs a class-conditional backbone (num_classes is None)")
 
     @torch.no_grad()  # (reference: inference_mode; no_grad keeps the plan buffers usable in training too)
-    def reverse_process(self, x_T: Tensor, conditions=None, t_checkpoints=None, guidance_scale=None) -> dict:
+    def reverse_process(self, x_T: Tensor, conditions=None, t_checkpoints=None, guidance_scale=None, num_steps=None, eta=None,
+                        clip_denoised: bool = True) -> dict:
         """ddpm.py:132-229.  ``x_T`` is only a shape/device template (:171).  ``guidance_scale`` (default: the attribute of that
         name; None = the reference's loop) samples with classifier-free guidance: the engine runs at batch 2B on
         cat(x_t, x_t) with cat(embedded labels, zeros), rho_p_sample_step_cfg combines the two predictions, applies the update
         and writes it to both halves.  The noise draws, their Philox offsets and the returned shapes are those of the unguided
-        call."""
+        call.
+
+        ``num_steps`` (default: the attribute ``sampling_steps``; None = every timestep, the loop above) samples in few steps:
+        a count S takes spaced_timesteps(T, S), a strictly increasing sequence is taken as given, and the walk applies the DDIM
+        update with ``eta`` (default: ``sampling_eta``) on those timesteps - _reverse_process_spaced.  ``clip_denoised`` clamps its x0
+        estimate to [-1, 1]; the full loop clamps x_t itself and has no such switch."""
         scale = self.guidance_scale if guidance_scale is None else float(guidance_scale)
         if scale is not None:
             self._refuse_unguidable(conditions)
+        num_steps = self.sampling_steps if num_steps is None else num_steps
+        spaced = None
+        if num_steps is not None:
+            spaced = self._spaced_host(num_steps, self.sampling_eta if eta is None else eta)      # ValueError before any draw
+        elif not clip_denoised:
+            raise ValueError("clip_denoised=False needs num_steps: the full loop clamps x_t after every update as the reference does")
         hip.require_gpu(x_T, "x_T")
         dev = x_T.device
         batch_size = x_T.size(0)
@@ -156,7 +177,7 @@ class DDPM(AbstractDiffusionPipeline):
         cc = self._preembed_conditions(cc)
 
         engine = self.backbone.engine() if hasattr(self.backbone, "engine") else None
-        t_dev = torch.full((1,), denoise_steps - 1, dtype=torch.int32, device=dev)
+        t_dev = torch.full((1,), denoise_steps - 1 if spaced is None else spaced["taus"][-1], dtype=torch.int32, device=dev)
         if scale is None:
             x_all = x_t                                     # what the backbone reads
 
@@ -176,6 +197,8 @@ class DDPM(AbstractDiffusionPipeline):
 
             def update(pred, z):
                 ops.p_sample_step_cfg(x_all, pred, z, tables["coef"], t_dev, scale)
+        if spaced is not None:
+            return self._reverse_process_spaced(x_all, x_t, cc, engine, scale, spaced, bool(clip_denoised), t_dev, buf)
         t_idx = 0
         if (self.hip_graph_sampling and engine is not None and denoise_steps > 2 and "noise" not in self.__dict__
                 and type(self).noise is DDPM.noise):
@@ -245,6 +268,114 @@ class DDPM(AbstractDiffusionPipeline):
             graph.replay()
             checkpoint(t)
         self._noise_offset += delta * max(denoise_steps - 2, 0)      # eager-loop bookkeeping: one draw per t > 1
+        return True
+
+    # ------------------------------------------------------------------ few-step sampling
+    def _spaced_host(self, num_steps, eta) -> dict:
+        """Timesteps and coefficient rows of a spaced walk, cached per (taus, eta): host work only, refusals included."""
+        T = len(self.schedule["alpha_bar_t"])
+        taus = tuple(resolve_timesteps(T, num_steps))
+        eta = float(eta)
+        key = (taus, eta)
+        if key not in self._spaced_cache:
+            with self.schedule:                                                      # float32 tables whatever the data dtype
+                ab = self.schedule["alpha_bar_t"].clone()
+            self._spaced_cache[key] = {"taus": taus, "eta": eta, "rows": spaced_coefficients(ab, taus, eta), "T": T, "dev": {}}
+        return self._spaced_cache[key]
+
+    def _spaced_device(self, spaced: dict, dev):
+        """(rows [S, 8] float32, taus [S] int32) on ``dev``, uploaded once per (device, taus, eta)."""
+        key = str(torch.device(dev))
+        if key not in spaced["dev"]:
+            spaced["dev"][key] = (spaced["rows"].contiguous().to(dev), torch.tensor(spaced["taus"], dtype=torch.int32).to(dev))
+        return spaced["dev"][key]
+
+    def _reverse_process_spaced(self, x_all, x_t, cc, engine, scale, spaced, clip, t_dev, buf) -> dict:
+        """The walk over ``spaced["taus"]`` from the top, k = S-1 .. 0: draw z (eta > 0 and k >= 1 only, before the backbone call as
+        in the full loop), evaluate the backbone at t = tau_k, rho_p_sample_step_spaced on row k, checkpoint, rho_spaced_advance.
+        ``x_all`` is what the backbone reads and the update writes: ``x_t``, or under guidance the doubled batch whose first half
+        ``x_t`` is (``cc`` then carries the null rows).  k and t live on the device, so one captured graph serves every step
+        (_reverse_process_spaced_graph)."""
+        taus, eta = spaced["taus"], spaced["eta"]
+        S = len(taus)
+        dev = x_all.device
+        batch_size = x_t.size(0)
+        rows, taus_dev = self._spaced_device(spaced, dev)
+        k_dev = torch.full((1,), S - 1, dtype=torch.int32, device=dev)
+        ckpt = spaced_checkpoints(spaced["T"], taus) if buf is not None else ()
+        num_checkpoints = buf.size(1) if buf is not None else 0
+        noisy = eta > 0.0
+        result = {"buffer": buf, "denoised": x_t}
+        if (self.hip_graph_sampling and engine is not None and S > 2 and "noise" not in self.__dict__
+                and type(self).noise is DDPM.noise):
+            if self._reverse_process_spaced_graph(x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt):
+                self._check_backbone_errors()
+                return result
+            k_dev.fill_(S - 1)
+            t_dev.fill_(taus[-1])
+        t_idx = 0
+        for k in range(S - 1, -1, -1):
+            z = self.noise(x_t) if (noisy and k >= 1) else None
+            if engine is not None:
+                pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
+            else:
+                pred = self.backbone(x_t, torch.full((batch_size,), taus[k], device=dev, dtype=torch.long), cc)
+            ops.p_sample_step_spaced(x_all, pred.contiguous(), z, rows, k_dev, scale, clip)
+            if buf is not None and taus[k] in ckpt and t_idx < num_checkpoints:
+                buf[:, t_idx].copy_(x_t)
+                t_idx += 1
+            ops.spaced_advance(k_dev, t_dev, taus_dev, None, 0)
+        self._check_backbone_errors()
+        return result
+
+    def _reverse_process_spaced_graph(self, x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt) -> bool:
+        """_reverse_process_graph for the spaced walk: step S-1 runs eagerly (it builds the engine plan), one captured step is
+        replayed S-1 times.  With eta > 0 the captured step draws z at every replay from the device-side offset; the draw of k = 0
+        is ignored by the kernel (row 0 has sigma = 0) and not counted, so the offset ends where the eager loop leaves it.  With
+        eta = 0 no Philox kernel is in the graph.  Returns False (nothing modified) if the capture fails."""
+        dev = x_t.device
+        S = len(taus)
+        delta = (x_t.numel() + 3) // 4
+        z = torch.empty_like(x_t) if noisy else None
+        off_dev = torch.full((1,), self._noise_offset, dtype=torch.int64, device=dev) if noisy else None
+        x_save = x_all.clone()
+        num_checkpoints = buf.size(1) if buf is not None else 0
+
+        def step():
+            if noisy:
+                ops.philox_normal(z, self.noise_seed, 0, offset_dev=off_dev)
+            pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
+            ops.p_sample_step_spaced(x_all, pred, z, rows, k_dev, scale, clip)
+            ops.spaced_advance(k_dev, t_dev, taus_dev, off_dev, delta)
+
+        t_idx = 0
+
+        def checkpoint(k):
+            nonlocal t_idx
+            if buf is not None and taus[k] in ckpt and t_idx < num_checkpoints:
+                buf[:, t_idx].copy_(x_t)
+                t_idx += 1
+
+        try:
+            step()                                      # k = S-1, eager
+            checkpoint(S - 1)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                step()
+        except Exception as exc:  # noqa: BLE001  (capture is an optimisation; any failure -> eager loop)
+            torch.cuda.synchronize()
+            x_all.copy_(x_save)
+            if buf is not None:
+                buf.zero_()
+            self.hip_graph_sampling = False
+            import warnings
+            warnings.warn(f"HIP graph capture of the sampling step failed ({type(exc).__name__}: {exc}); using the eager loop")
+            return False
+        for k in range(S - 2, -1, -1):
+            graph.replay()
+            checkpoint(k)
+        if noisy:
+            self._noise_offset += delta * (S - 1)       # eager-loop bookkeeping: one draw per k >= 1
         return True
 
     # ------------------------------------------------------------------ training

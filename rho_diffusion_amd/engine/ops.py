@@ -75,6 +75,40 @@ def p_sample_step_cfg(x2: Tensor, eps2: Tensor, z: Optional[Tensor], coef_table:
     return x2
 
 
+def p_sample_step_spaced(x: Tensor, eps_hat: Tensor, z: Optional[Tensor], rows: Tensor, k_dev: Tensor, scale: Optional[float] = None,
+                         clip: bool = True) -> Tensor:
+    """One reverse update of the spaced walk (rho_p_sample_step_spaced): row ``*k_dev`` of ``rows`` [S, 8].  ``scale`` None: ``x`` and
+    ``eps_hat`` hold the sample and its prediction; a float: the guided form, both hold the doubled batch [2B, ...] and both halves
+    of ``x`` receive the update.  ``z`` [B, ...] or None."""
+    _f32c(x, "x"), _f32c(eps_hat, "eps_hat"), _f32c(rows, "rows")
+    if z is not None:
+        _f32c(z, "z")
+    if rows.dim() != 2 or rows.shape[1] != 8 or rows.shape[0] < 1:
+        raise RhoHipError(f"rows must be float32 [S, 8], got {tuple(rows.shape)}")
+    guided = scale is not None
+    n = x.numel() // 2 if guided else x.numel()
+    if n < 1 or x.numel() != (2 * n if guided else n) or eps_hat.numel() != x.numel() or (z is not None and z.numel() != n):
+        raise RhoHipError(f"x / eps_hat hold {'two rows' if guided else 'one row'} of n elements and z one: got {x.numel()}, "
+                          f"{eps_hat.numel()}, {None if z is None else z.numel()}")
+    if k_dev.dtype != torch.int32 or not k_dev.is_cuda or k_dev.numel() != 1:
+        raise RhoHipError("k_dev must be int32[1] on the GPU")
+    check(hip.lib().rho_p_sample_step_spaced(ptr(x), ptr(eps_hat), ptr(z), ptr(rows), ptr(k_dev), rows.shape[0], n, int(guided),
+                                             float(scale) if guided else 0.0, int(bool(clip)), stream()), "rho_p_sample_step_spaced")
+    return x
+
+
+def spaced_advance(k_dev: Tensor, t_dev: Tensor, taus: Tensor, offset_dev: Optional[Tensor], delta: int) -> None:
+    """k <- k - 1, t <- taus[k] while k >= 0, offset += delta (rho_spaced_advance): the loop state of the spaced walk."""
+    for name, t in (("k_dev", k_dev), ("t_dev", t_dev)):
+        if t.dtype != torch.int32 or not t.is_cuda or t.numel() != 1:
+            raise RhoHipError(f"{name} must be int32[1] on the GPU")
+    if taus.dtype != torch.int32 or not taus.is_cuda or taus.dim() != 1 or not taus.is_contiguous() or taus.numel() < 1:
+        raise RhoHipError("taus must be a contiguous int32 [S] GPU tensor")
+    if offset_dev is not None and (offset_dev.dtype != torch.int64 or not offset_dev.is_cuda or offset_dev.numel() != 1):
+        raise RhoHipError("offset_dev must be int64[1] on the GPU or None")
+    check(hip.lib().rho_spaced_advance(ptr(k_dev), ptr(t_dev), ptr(taus), ptr(offset_dev), delta, stream()), "rho_spaced_advance")
+
+
 def q_sample_coef(x0: Tensor, eps: Tensor, t: Tensor, coef_a: Tensor, coef_b: Tensor, out: Optional[Tensor] = None,
                   err_flag: Optional[Tensor] = None) -> Tensor:
     """x_t = a[t] * x0 + b[t] * eps with explicit float32 tables (GaussianDiffusionPipeline.q_sample)."""
