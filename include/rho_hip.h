@@ -969,6 +969,55 @@ int rho_bias_act_bwd(const void* x, const float* bias, const void* dy, void* dx,
 int rho_pos_add(void* x, const float* pos, int dtype, int64_t batch, int64_t m, void* stream);
 int rho_pos_add_bwd(const void* dx, float* dpos, int dtype, int64_t batch, int64_t m, void* stream);
 
+/* ---- Sample metrics (csrc/sinkhorn.hip): the Sinkhorn divergence behind WassersteinWrapper (metrics/geom.py:28-37: geomloss's
+ * SamplesLoss("sinkhorn", p=1, blur=0.01) over flatten(1)) and PeakSignalNoiseRatio (abstract_diffusion.py:79).  x float32 [n, d],
+ * y float32 [m, d], contiguous, uniform weights; 1 <= n, m <= rho_sinkhorn_max_samples() (128), d >= 1 (RHO_E_SHAPE otherwise).
+ * Inputs, outputs and the streaming passes are float32; the cost sums, the diameter and the loop run in float64 (at blur 0.01 the
+ * transport plan, hence the gradient, is decided by cost differences ~1e-7 of the costs).  No atomics: every sum runs in an order
+ * fixed by the shapes, two runs give the same bits. */
+int64_t rho_sinkhorn_max_samples(void);
+
+/* The three cost matrices of metrics/geom.py:28-37 in one pass over z = [x; y]: d2(u, v) = sum_d (u_d - v_d)^2 as a direct sum of
+ * squared differences (a self-cost is exactly 0), C = sqrt(max(d2, 1e-8)) for p = 1 and d2 / 2 for p = 2.  c_xy [n, m], c_xx [n, n],
+ * c_yy [m, m] in float32, and - c64 not NULL - the same three back to back in float64 [n m + n n + m m] for rho_sinkhorn_loop.
+ * d is cut into chunks of 512; one workgroup stages a chunk of all n + m rows in LDS once (16-byte loads when d % 4 == 0
+ * and the bases are 16-byte aligned) and writes its partial sums to `workspace`; a second launch adds the chunks in index order.
+ * d <= 65535 * 512. */
+int64_t rho_pairwise_cost_workspace_bytes(int64_t n, int64_t m, int64_t d);
+int rho_pairwise_cost(const float* x, const float* y, int64_t n, int64_t m, int64_t d, int p, float* c_xy, float* c_xx, float* c_yy,
+                      double* c64, double* workspace, int64_t workspace_bytes, void* stream);
+
+/* out[0] = || max_rows(z) - min_rows(z) ||_2, the diameter geomloss's epsilon schedule starts from (metrics/geom.py:28-37);
+ * workspace: ceil(d / 1024) doubles (rho_pairwise_cost_workspace_bytes covers it).  out: float64 [1]. */
+int rho_max_diameter(const float* x, const float* y, int64_t n, int64_t m, int64_t d, double* out, double* workspace,
+                     int64_t workspace_bytes, void* stream);
+
+/* The symmetric epsilon-scaling Sinkhorn loop of metrics/geom.py:28-37 in one launch of one workgroup (cost matrices in LDS while
+ * they fit in 160 KiB, the rest read through L2), with softmin(eps, C, h)[i] = -eps logsumexp_j(h[j] - C[i, j] / eps) (evaluated
+ * with the uniform log-weight folded in: -eps (max u + log1p(mean expm1(u - max))), u = (potential - C) / eps):
+ *   start at eps_list[0] from the log-weights; for each of the n_eps entries all four potentials from the old ones, averaged with
+ *   them; one last plain step at eps_list[n_eps - 1].
+ * c_xy, c_xx, c_yy: the float64 matrices of rho_pairwise_cost; eps_list: device float64 [n_eps].  Writes float32 f_ba, f_aa, h_a [n]; g_ab, g_bb, h_b [m] (h_b = b_log + g_ab / eps and h_a = a_log +
+ * f_aa / eps: what entered the last step); loss[0] = mean(f_ba - f_aa) + mean(g_ab - g_bb).  debias = 0 leaves f_aa = g_bb = 0.
+ * wp [n, m], wq [n, n], rp, rq [n] (all four or all NULL): the weights of the last step's gradient, P = softmax_j(h_b - C_xy / eps)
+ * and Q = softmax_k(h_a - C_xx / eps), divided by the cost for p = 1 (0 where the clamp of the cost holds), and their row sums. */
+int rho_sinkhorn_loop(const double* c_xy, const double* c_xx, const double* c_yy, int64_t n, int64_t m, const double* eps_list,
+                      int64_t n_eps, int p, int debias, float* f_ba, float* g_ab, float* f_aa, float* g_bb, float* h_b, float* h_a,
+                      float* loss, float* wp, float* wq, float* rp, float* rq, void* stream);
+
+/* The gradient of that loss w.r.t. x (metrics/geom.py:28-37 under autograd), one pass over x and y:
+ *   grad_x[i, :] = (g_out[0] / n) ((rp[i] - rq[i]) x[i, :] - sum_j wp[i, j] y[j, :] + sum_k wq[i, k] x[k, :])
+ * g_out: device float32 [1], the upstream gradient. */
+int rho_rows_combine(const float* x, const float* y, int64_t n, int64_t m, int64_t d, const float* wp, const float* wq, const float* rp,
+                     const float* rq, const float* g_out, float* grad_x, void* stream);
+
+/* PeakSignalNoiseRatio (abstract_diffusion.py:79): out = {10 log10(range^2 / mse), mse, min(target), max(target)} from one fused
+ * pass (sum of squared error, min and max as per-block partials, folded in block order).  data_range <= 0: max - min of this
+ * target.  workspace: rho_psnr_workspace_bytes(). */
+int64_t rho_psnr_workspace_bytes(void);
+int rho_psnr(const float* pred, const float* target, int64_t n, float data_range, float* out, float* workspace, int64_t workspace_bytes,
+             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,3 +99,27 @@ class HybridLossFunction(torch.autograd.Function):
 
 def hybrid_loss(model_out, x_start, x_t, target, t, tab, mean_type: int, var_type: int, vb_scale: Optional[float], err_flag=None):
     return HybridLossFunction.apply(model_out, x_start, x_t, target, t, tab, mean_type, var_type, vb_scale, err_flag)
+
+
+class SinkhornFunction(torch.autograd.Function):
+    """The debiased Sinkhorn divergence between the rows of ``x`` [N, D] and ``y`` [M, D] (metrics/geom.py:28-37) on the HIP kernels:
+    cost matrices in one streaming pass, the whole epsilon schedule in one launch, and - when ``x`` needs a gradient - the last
+    step's weights, from which the backward writes grad_x in a second streaming pass.  ``eps_list`` is the schedule on the device."""
+
+    @staticmethod
+    def forward(ctx, x, y, eps_list, p, debias):
+        need = ctx.needs_input_grad[0]
+        cost = ops.pairwise_cost(x, y, p, dtype=torch.float64)
+        out = ops.sinkhorn_loop(*cost, eps_list, p, debias, want_weights=need)
+        if need:
+            ctx.save_for_backward(x, y, out["wp"], out["wq"], out["rp"], out["rq"])
+        return out["loss"].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, wp, wq, rp, rq = ctx.saved_tensors
+        return ops.rows_combine(x, y, wp, wq, rp, rq, g.reshape(1).float().contiguous()), None, None, None, None
+
+
+def sinkhorn_loss(x: torch.Tensor, y: torch.Tensor, eps_list: torch.Tensor, p: int, debias: bool) -> torch.Tensor:
+    return SinkhornFunction.apply(x, y, eps_list, p, debias)

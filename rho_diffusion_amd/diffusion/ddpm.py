@@ -447,6 +447,10 @@ class DDPM(AbstractDiffusionPipeline):
             loss = mse_loss(pred_noise, noise)           # HIP reduction + gradient (rho_mse)
         else:
             loss = self.loss_func(pred_noise, noise)
+        # whatever the user put into self.metrics (empty by default), between the noised and the clean data (ddpm.py:283-285)
+        for key, metric in self.metrics.items():
+            with torch.no_grad():
+                self.log(f"train_{key}", metric(x_data, data))
         self.log("train_loss", loss, prog_bar=True)
         return loss
 

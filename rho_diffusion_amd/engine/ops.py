@@ -1504,3 +1504,107 @@ def pos_add_bwd(dx: Tensor, out: Optional[Tensor] = None) -> Tensor:
     out = torch.empty(tuple(dx.shape[1:]), dtype=torch.float32, device=dx.device) if out is None else _f32c(out, "out")
     check(hip.lib().rho_pos_add_bwd(ptr(dx), ptr(out), dtype_code(dx.dtype), dx.shape[0], out.numel(), stream()), "rho_pos_add_bwd")
     return out
+
+
+# ----------------------------------------------------------------------------- sample metrics (csrc/sinkhorn.hip)
+SINKHORN_MAX_SAMPLES = 128       # == rho_sinkhorn_max_samples()
+
+
+def _sinkhorn_xy(x: Tensor, y: Tensor) -> Tuple[int, int, int]:
+    """(N, M, D) of two float32 [rows, D] sample sets within the kernels' limits."""
+    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+        raise RhoHipError(f"x and y must be [N, D] and [M, D], got {tuple(x.shape)} and {tuple(y.shape)}")
+    N, M, D = int(x.shape[0]), int(y.shape[0]), int(x.shape[1])
+    if not (1 <= N <= SINKHORN_MAX_SAMPLES and 1 <= M <= SINKHORN_MAX_SAMPLES) or D < 1:
+        raise RhoHipError(f"the Sinkhorn kernels take 1 <= N, M <= {SINKHORN_MAX_SAMPLES} samples of D >= 1 values, got N = {N}, "
+                          f"M = {M}, D = {D}")
+    _f32c(x, "x"), _f32c(y, "y")
+    return N, M, D
+
+
+def sinkhorn_workspace(x: Tensor, y: Tensor) -> Tensor:
+    """Scratch of rho_pairwise_cost / rho_max_diameter for this pair (float64), allocated in stream order."""
+    N, M, D = _sinkhorn_xy(x, y)
+    nbytes = int(hip.lib().rho_pairwise_cost_workspace_bytes(N, M, D))
+    if nbytes < 0:
+        raise RhoHipError("rho_pairwise_cost_workspace_bytes refused the shape")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+
+
+def pairwise_cost(x: Tensor, y: Tensor, p: int, workspace: Optional[Tensor] = None, dtype: torch.dtype = torch.float32):
+    """(C_xy [N, M], C_xx [N, N], C_yy [M, M]) of rho_pairwise_cost: sqrt(max(d2, 1e-8)) for p = 1, d2 / 2 for p = 2.  ``dtype``
+    float32, or float64: the matrices rho_sinkhorn_loop reads (the sums run in float64 either way)."""
+    N, M, D = _sinkhorn_xy(x, y)
+    if dtype not in (torch.float32, torch.float64):
+        raise RhoHipError(f"pairwise_cost returns float32 or float64 matrices, not {dtype}")
+    ws = sinkhorn_workspace(x, y) if workspace is None else workspace
+    if ws.dtype != torch.float64 or not ws.is_cuda:
+        raise RhoHipError("workspace must be a float64 GPU tensor (sinkhorn_workspace)")
+
+    def split(buf):
+        return buf[:N * M].view(N, M), buf[N * M:N * M + N * N].view(N, N), buf[N * M + N * N:].view(M, M)
+
+    buf = torch.empty(N * M + N * N + M * M, dtype=torch.float32, device=x.device)
+    buf64 = torch.empty(N * M + N * N + M * M, dtype=torch.float64, device=x.device) if dtype == torch.float64 else None
+    c_xy, c_xx, c_yy = split(buf)
+    check(hip.lib().rho_pairwise_cost(ptr(x), ptr(y), N, M, D, int(p), ptr(c_xy), ptr(c_xx), ptr(c_yy), ptr(buf64), ptr(ws),
+                                      ws.numel() * 8, stream()), "rho_pairwise_cost")
+    return split(buf64) if buf64 is not None else (c_xy, c_xx, c_yy)
+
+
+def max_diameter(x: Tensor, y: Tensor, workspace: Optional[Tensor] = None) -> Tensor:
+    """float64 [1]: the norm of the per-coordinate extent of [x; y] (rho_max_diameter)."""
+    N, M, D = _sinkhorn_xy(x, y)
+    ws = sinkhorn_workspace(x, y) if workspace is None else workspace
+    out = torch.empty(1, dtype=torch.float64, device=x.device)
+    check(hip.lib().rho_max_diameter(ptr(x), ptr(y), N, M, D, ptr(out), ptr(ws), ws.numel() * 8, stream()), "rho_max_diameter")
+    return out
+
+
+def sinkhorn_loop(c_xy: Tensor, c_xx: Tensor, c_yy: Tensor, eps_list: Tensor, p: int, debias: bool = True, want_weights: bool = False):
+    """The whole epsilon schedule in one launch (rho_sinkhorn_loop) from float64 cost matrices (pairwise_cost(..., dtype=torch.float64))
+    and a float64 schedule on the device.  Returns a dict of float32 tensors: f_ba, f_aa, h_a [N]; g_ab,
+    g_bb, h_b [M]; loss [1]; with ``want_weights`` also wp [N, M], wq [N, N], rp, rq [N]."""
+    for name, t in (("c_xy", c_xy), ("c_xx", c_xx), ("c_yy", c_yy), ("eps_list", eps_list)):
+        hip.require_gpu(t, name)
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise RhoHipError(f"{name} must be contiguous float64, got {t.dtype} contiguous={t.is_contiguous()}")
+    N, M = int(c_xy.shape[0]), int(c_xy.shape[1])
+    if tuple(c_xx.shape) != (N, N) or tuple(c_yy.shape) != (M, M) or eps_list.numel() < 1:
+        raise RhoHipError("c_xy [N, M], c_xx [N, N], c_yy [M, M] and a non-empty eps_list are required")
+    buf = torch.empty(3 * N + 3 * M + 1, dtype=torch.float32, device=c_xy.device)
+    o = {"f_ba": buf[:N], "f_aa": buf[N:2 * N], "h_a": buf[2 * N:3 * N], "g_ab": buf[3 * N:3 * N + M],
+         "g_bb": buf[3 * N + M:3 * N + 2 * M], "h_b": buf[3 * N + 2 * M:3 * N + 3 * M], "loss": buf[3 * N + 3 * M:]}
+    if want_weights:
+        w = torch.empty(N * M + N * N + 2 * N, dtype=torch.float32, device=c_xy.device)
+        o.update(wp=w[:N * M].view(N, M), wq=w[N * M:N * M + N * N].view(N, N), rp=w[N * M + N * N:N * M + N * N + N],
+                 rq=w[N * M + N * N + N:])
+    check(hip.lib().rho_sinkhorn_loop(ptr(c_xy), ptr(c_xx), ptr(c_yy), N, M, ptr(eps_list), eps_list.numel(), int(p), 1 if debias else 0,
+                                      ptr(o["f_ba"]), ptr(o["g_ab"]), ptr(o["f_aa"]), ptr(o["g_bb"]), ptr(o["h_b"]), ptr(o["h_a"]),
+                                      ptr(o["loss"]), ptr(o.get("wp")), ptr(o.get("wq")), ptr(o.get("rp")), ptr(o.get("rq")), stream()),
+          "rho_sinkhorn_loop")
+    return o
+
+
+def rows_combine(x: Tensor, y: Tensor, wp: Tensor, wq: Tensor, rp: Tensor, rq: Tensor, g_out: Tensor) -> Tensor:
+    """grad_x [N, D] of the Sinkhorn loss from the last step's weights (rho_rows_combine); g_out: float32 [1] on the device."""
+    N, M, D = _sinkhorn_xy(x, y)
+    for name, t, numel in (("wp", wp, N * M), ("wq", wq, N * N), ("rp", rp, N), ("rq", rq, N), ("g_out", g_out, 1)):
+        if _f32c(t, name).numel() != numel:
+            raise RhoHipError(f"{name} must hold {numel} float32 values")
+    grad = torch.empty_like(x)
+    check(hip.lib().rho_rows_combine(ptr(x), ptr(y), N, M, D, ptr(wp), ptr(wq), ptr(rp), ptr(rq), ptr(g_out), ptr(grad), stream()),
+          "rho_rows_combine")
+    return grad
+
+
+def psnr(pred: Tensor, target: Tensor, data_range: Optional[float] = None) -> Tensor:
+    """float32 [4] = (10 log10(range^2 / mse), mse, min(target), max(target)) from one fused reduction (rho_psnr); ``data_range``
+    None: max - min of this target."""
+    _f32c(pred, "pred")
+    _same(pred, ("target", target))
+    ws_bytes = int(hip.lib().rho_psnr_workspace_bytes())
+    buf = torch.empty(4 + ws_bytes // 4, dtype=torch.float32, device=pred.device)
+    check(hip.lib().rho_psnr(ptr(pred), ptr(target), pred.numel(), 0.0 if data_range is None else float(data_range), ptr(buf),
+                             buf.data_ptr() + 16, ws_bytes, stream()), "rho_psnr")
+    return buf[:4]

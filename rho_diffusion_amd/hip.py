@@ -224,6 +224,16 @@ SIGNATURES = {
     "rho_bias_act_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p]),
     "rho_pos_add": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "rho_pos_add_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p]),
+    # ---- sample metrics (metrics/geom.py, metrics/psnr.py, csrc/sinkhorn.hip)
+    "rho_sinkhorn_max_samples": (c_int64, []),
+    "rho_pairwise_cost_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "rho_pairwise_cost": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_int64, c_void_p]),
+    "rho_max_diameter": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rho_sinkhorn_loop": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 12),
+    "rho_rows_combine": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 7),
+    "rho_psnr_workspace_bytes": (c_int64, []),
+    "rho_psnr": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 

@@ -1,6 +1,10 @@
-"""rho_diffusion.metrics (the reference's package; ``losses`` is built here, ``geom`` - WassersteinWrapper, which needs
-geomloss - is not)."""
-from . import losses
+"""rho_diffusion.metrics (the reference's package): ``losses`` (guided-diffusion's VLB terms) and ``geom`` (WassersteinWrapper: the
+Sinkhorn divergence of geomloss, restated here and run as HIP kernels), plus ``PeakSignalNoiseRatio``, the metric the reference's
+pipelines take from torchmetrics."""
+from . import geom, losses, psnr
+from .geom import SinkhornDivergence, WassersteinWrapper, epsilon_schedule
 from .losses import approx_standard_normal_cdf, discretized_gaussian_log_likelihood, normal_kl
+from .psnr import PeakSignalNoiseRatio
 
-__all__ = ["losses", "normal_kl", "approx_standard_normal_cdf", "discretized_gaussian_log_likelihood"]
+__all__ = ["losses", "geom", "psnr", "normal_kl", "approx_standard_normal_cdf", "discretized_gaussian_log_likelihood",
+           "SinkhornDivergence", "WassersteinWrapper", "epsilon_schedule", "PeakSignalNoiseRatio"]
