@@ -230,7 +230,8 @@ int rho_cond_keep_mask(uint8_t* keep, int64_t n, float p, uint64_t seed, uint64_
 int rho_cond_drop(float* cond, int32_t* cond_idx, const uint8_t* keep, int64_t batch, int64_t dim, int64_t nkeys, void* stream);
 
 /* out[b, o] = bias[o] + sum_k act(x[b, k]) * w[o, k] (+ add[b, o])   all float32.
- * act_in: 0 = identity, 1 = SiLU.  act_out: 0 = identity, 1 = SiLU.
+ * act_in / act_out: activation codes as in rho_timestep_embed - 0 identity, 1 SiLU, 2 ReLU, 3 GELU (erf), 4 Tanh, 5 Sigmoid,
+ * 6 ELU(1); act_out applies to the whole sum, after bias and add.  bias and add may be NULL.  in_dim <= 2048 (else RHO_E_ARG).
  * replaces the nn.Linear / SiLU chains of unet_v2.py:521-525 (time_embed), :229-235
  * (emb_layers of every ResBlock, batched by concatenating their weights) and the label
  * embedding add of :702-719. */
@@ -864,8 +865,9 @@ int rho_avgpool2x_bwd(const void* dy, void* dx, int dtype, int64_t n_times_d, in
                       int accumulate, void* stream);
 
 /* Backward of rho_linear: dw[o,k] (+)= sum_b dout[b,o] act(x[b,k]); db[o] (+)= sum_b dout[b,o];
- * dx[b,k] (+)= act'(x[b,k]) sum_o dout[b,o] w[o,k].  dw/db/dx may be NULL; dout rows are dout_stride floats apart
- * (0 = out_dim) so a slice of the batched FiLM gradient can be passed in place. */
+ * dx[b,k] (+)= act'(x[b,k]) sum_o dout[b,o] w[o,k].  dw/db/dx may each be NULL on its own (db without dw is computed too, in
+ * the same batch order); acc_params adds onto dw and db, acc_dx onto dx.  act_in: an activation code 0..6 (see rho_timestep_embed).
+ * dout rows are dout_stride floats apart (0 = out_dim) so a slice of the batched FiLM gradient can be passed in place. */
 int rho_linear_bwd(const float* dout, int64_t dout_stride, const float* x, const float* w, float* dw, float* db,
                    float* dx, int64_t batch, int64_t in_dim, int64_t out_dim, int act_in, int acc_params, int acc_dx,
                    void* stream);

@@ -1250,6 +1250,16 @@ __global__ __launch_bounds__(256) void k_linear_bwd_w(const float* __restrict__ 
     if (k == 0 && db) db[o] = accumulate ? db[o] + accb : accb;
 }
 
+// db alone (dw == NULL): the bias sum of k_linear_bwd_w in the same batch order, one thread per output feature
+__global__ __launch_bounds__(256) void k_linear_bwd_b(const float* __restrict__ dout, float* __restrict__ db, int batch, int out_dim,
+                                                      int accumulate, int64_t dstride) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= out_dim) return;
+    float accb = 0.0f;
+    for (int b = 0; b < batch; ++b) accb += dout[(int64_t)b * dstride + o];
+    db[o] = accumulate ? db[o] + accb : accb;
+}
+
 // dx[b,k] += act'(x[b,k]) * sum_o dout[b,o] W[o,k], the o range dealt to gridDim.y slices of 64 that add with fp32 atomics
 // (a thread per (b,k) walking all of out_dim was 32 workgroups x 1024 dependent iterations: 0.2-0.4 ms per FiLM linear,
 // 4.7 ms per training step for 4 MFLOP of work).  dx must hold the value to accumulate onto (zeroed by the caller side).
@@ -1301,6 +1311,9 @@ extern "C" int rho_linear_bwd(const float* dout, int64_t dout_stride, const floa
     if (dw) {
         hipLaunchKernelGGL(k_linear_bwd_w, dim3((unsigned)((out_dim * in_dim + 255) / 256)), dim3(256), 0, as_stream(stream), dout, x, dw,
                            db, (int)batch, (int)in_dim, (int)out_dim, act_in, acc_params, dstride);
+    } else if (db) {
+        hipLaunchKernelGGL(k_linear_bwd_b, dim3((unsigned)((out_dim + 255) / 256)), dim3(256), 0, as_stream(stream), dout, db, (int)batch,
+                           (int)out_dim, acc_params, dstride);
     }
     if (dx && rho_get_deterministic()) {
         hipLaunchKernelGGL(k_linear_bwd_x_det, dim3((unsigned)((batch * in_dim + 255) / 256)), dim3(256), 0, as_stream(stream), dout, w, x,

@@ -810,8 +810,9 @@ def line_profile(grid: Tensor, centers: Tensor, intensity: Tensor, offsets: Tens
     return out
 
 
-def linear(x: Tensor, w: Tensor, bias: Optional[Tensor], add: Optional[Tensor] = None, act_in: bool = False,
-           act_out: bool = False, out: Optional[Tensor] = None) -> Tensor:
+def linear(x: Tensor, w: Tensor, bias: Optional[Tensor], add: Optional[Tensor] = None, act_in: int = 0,
+           act_out: int = 0, out: Optional[Tensor] = None) -> Tensor:
+    """out = act_out(w act_in(x) + bias (+ add)): rho_linear.  ``act_in`` / ``act_out``: activation codes (see ACT_CODES; True is SiLU)."""
     _f32c(x, "x"), _f32c(w, "w")
     B, K = x.shape
     O = w.shape[0]
@@ -1334,8 +1335,9 @@ def pool2x_sum(dy: Tensor, dx: Tensor, up_hw, accumulate: bool = False) -> Tenso
 
 
 def linear_bwd(dout, x: Tensor, w: Tensor, dw: Optional[Tensor], db: Optional[Tensor], dx: Optional[Tensor],
-               act_in: bool = False, acc_params: bool = False, acc_dx: bool = False, dout_stride: int = 0) -> None:
-    """dout may be a tensor or a raw device pointer (a column slice of the batched FiLM gradient)."""
+               act_in: int = 0, acc_params: bool = False, acc_dx: bool = False, dout_stride: int = 0) -> None:
+    """dout may be a tensor or a raw device pointer (a column slice of the batched FiLM gradient).  ``act_in``: activation code
+    (see ACT_CODES; True is SiLU)."""
     B, K = x.shape
     O = w.shape[0]
     dp = dout if isinstance(dout, int) else dout.data_ptr()
