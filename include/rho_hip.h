@@ -39,7 +39,8 @@ extern "C" {
  * 10: learned variances - RHO_GD_LOG_BETA, the *_lv / strided / hybrid-loss entry points; the dataset entry points added since -
  * rho_crop_resize, rho_line_profile, rho_pil_resize_taps, rho_u8_image_batch, the guidance trio rho_p_sample_step_cfg,
  * rho_cond_keep_mask, rho_cond_drop, the query rho_attention_variant, and the spaced-walk pair rho_p_sample_step_spaced,
- * rho_spaced_advance - change no existing signature or struct, so by this
+ * rho_spaced_advance, and the prediction-type pair rho_pred_loss_ws, rho_p_sample_step_spaced_pred - change no existing signature or
+ * struct, so by this
  * rule they leave it at 10: a binding that lacks them fails on the missing symbol).  A loader must compare rho_abi_version() with the header it was written against
  * before calling anything else (hip.py does; a build with all symbols but older signatures would be called with shifted arguments). */
 #define RHO_ABI_VERSION 10
@@ -102,6 +103,28 @@ int rho_p_sample_step_spaced(float* x, const float* eps_hat, const float* z, con
  * *t_dev keeps its last value); if offset_dev != NULL, *offset_dev += delta.  k_dev, t_dev and taus must not be NULL. */
 int rho_spaced_advance(int32_t* k_dev, int32_t* t_dev, const int32_t* taus, uint64_t* offset_dev, uint64_t delta, void* stream);
 
+/* What the backbone predicts (none of this in the reference, whose DDPM predicts the noise): with x_t = sqrt(ab) x0 + sqrt(1 - ab) eps,
+ * RHO_PRED_EPSILON eps, RHO_PRED_V v = sqrt(ab) eps - sqrt(1 - ab) x0 (Salimans & Ho 2022), RHO_PRED_SAMPLE x0. */
+#define RHO_PRED_EPSILON 0
+#define RHO_PRED_V 1
+#define RHO_PRED_SAMPLE 2
+
+/* rho_p_sample_step_spaced for pred_type RHO_PRED_V or RHO_PRED_SAMPLE (RHO_PRED_EPSILON: RHO_E_ARG, that type stays on
+ * rho_p_sample_step_spaced).  rows float32 [S, 8] on the device, row k for t = tau_k:
+ *   {sqrt_ab, sqrt_1mab = sqrt(1 - ab), inv_sqrt_1mab = 1/sqrt(1 - ab) (0 where 1 - ab == 0), sqrt_abp = sqrt(ab_prev),
+ *    sigma (0 where 1 - ab == 0), coef_eps = sqrt(max(1 - ab_prev - sigma^2, 0)), 0, 0}
+ * Nothing is divided by sqrt(ab): a row with ab == 0 is legal.  k_dev, S, guided / scale, z, clip, the store to both rows under
+ * guidance and the conditions of the 16-byte form are those of rho_p_sample_step_spaced; rho_spaced_advance serves this walk
+ * unchanged.  Guidance mixes the predictions, p = fma(scale, p_c - p_u, p_u) (both conversions below are affine in p at fixed x, so
+ * this equals mixing the noise estimates); guided == 0: p = pred.  One contraction shared by every form:
+ *   RHO_PRED_V: x0 = fma(sqrt_ab, x, -(sqrt_1mab * p))        RHO_PRED_SAMPLE: x0 = p
+ *   clip != 0:  x0 = clamp(x0, -1, 1)
+ *   ep = fma(-sqrt_ab, x0, x) * inv_sqrt_1mab;   RHO_PRED_V with clip == 0:  ep = fma(sqrt_1mab, x, sqrt_ab * p)
+ *   x <- fma(sqrt_abp, x0, fma(coef_eps, ep, sigma * z))
+ * and x <- sqrt_abp * x0, ep not formed, where the row has coef_eps == 0 and sigma == 0 (always row 0). */
+int rho_p_sample_step_spaced_pred(float* x, const float* pred, const float* z, const float* rows, const int32_t* k_dev, int32_t S,
+                                  int64_t n, int guided, float scale, int clip, int pred_type, void* stream);
+
 /* Counter-based Philox4x32-10 standard normals (Box-Muller), replaces torch.randn_like at
  * ddpm.py:101-102,171,197.  out float32[n]; stream of (seed, offset) is reproducible and
  * independent of launch geometry.  offset is read from *offset_dev (uint64[1], device) when
@@ -118,6 +141,21 @@ int rho_mse(const float* a, const float* b, float* loss, float* grad_a, int64_t 
  * in index order, so the loss value is bit-reproducible run to run (rho_mse used to add its blocks with an fp32 atomic, in arrival
  * order).  loss and grad_a are identical in both.  The Python binding always uses this form. */
 int rho_mse_ws(const float* a, const float* b, float* loss, float* grad_a, int64_t n, float* partials, int64_t n_partials, void* stream);
+
+/* The training loss of a backbone that predicts pred_type (RHO_PRED_*), with an optional per-timestep weight (min-SNR-gamma, Hang et
+ * al. 2023); in place of nn.MSELoss at ddpm.py:280 and its backward, the target never materialised.  pred, x0, eps float32
+ * [batch, per_sample]; alpha_bar float32 [table_len]; w float32 [table_len] or NULL (weight 1); t int64 [batch] on the device.  Per
+ * sample b: ab = alpha_bar[t_b], sa = sqrtf(ab), sb = sqrtf(1 - ab) (as rho_q_sample forms them), wb = w[t_b].  Per element, one
+ * contraction shared by the 16-byte body (pred / x0 / eps / grad 16-byte aligned, per_sample >= 4), its tail and the scalar form:
+ *   target g = eps (EPSILON) | x0 (SAMPLE) | fma(sa, eps, -(sb * x0)) (V);   d = pred - g
+ *   sum <- fma(wb * d, d, sum);   grad = (wb * k2) * d,  k2 = 2 * (1.0f / (float)(batch * per_sample))       grad may be NULL
+ * loss[0] = sum_b wb sum_i d^2 / (batch * per_sample), reduced as rho_mse_ws reduces: block partials -> partials[n_partials]
+ * (scratch, >= 1; 1024 is plenty), added in index order, no atomics, bit-reproducible run to run.  grad has the same bits in every
+ * form and, for EPSILON with wb == 1, those of rho_mse_ws(pred, eps).  A t_b outside [0, table_len) sets *err_flag |= 4 (optional
+ * flag, int32[1]) and reads the clamped row, as rho_q_sample does. */
+int rho_pred_loss_ws(const float* pred, const float* x0, const float* eps, const float* alpha_bar, const float* w, const int64_t* t,
+                     int64_t batch, int64_t per_sample, int64_t table_len, int pred_type, float* loss, float* grad, float* partials,
+                     int64_t n_partials, int32_t* err_flag, void* stream);
 
 /* mean over all non-batch axes of a float32 [batch, per_sample] tensor -> out[batch]: mean_flat of layers.py:105-110 (ABI 7). */
 int rho_mean_flat(const float* x, float* out, int64_t batch, int64_t per_sample, void* stream);

@@ -54,6 +54,34 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return MSELossFunction.apply(pred, target)
 
 
+class PredLossFunction(torch.autograd.Function):
+    """sum_b w[t_b] sum_i (pred - target)^2 / n for a backbone that predicts the noise, v or x0 (``pred_type`` 0 / 1 / 2), the target
+    formed from (x0, noise, t) inside the kernel (rho_pred_loss_ws); ``w`` None weighs every timestep 1.  Only ``pred`` receives a
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, x0, noise, t, alpha_bar, w, pred_type, err_flag):
+        loss, grad = ops.pred_loss(pred.contiguous().float(), x0.contiguous().float(), noise.contiguous().float(), t, alpha_bar, w,
+                                   pred_type, want_grad=True, err_flag=err_flag)
+        ctx.save_for_backward(grad)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        # the scalar upstream gradient is applied on the device, as in MSELossFunction
+        from . import hip
+        gs = g.reshape(1).float().contiguous()
+        hip.check(hip.lib().rho_scale_by_device_scalar(grad.data_ptr(), gs.data_ptr(), grad.numel(), hip.stream()),
+                  "rho_scale_by_device_scalar")
+        return grad, None, None, None, None, None, None, None
+
+
+def pred_loss(pred: torch.Tensor, x0: torch.Tensor, noise: torch.Tensor, t: torch.Tensor, alpha_bar: torch.Tensor,
+              w: Optional[torch.Tensor], pred_type: int, err_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return PredLossFunction.apply(pred, x0, noise, t, alpha_bar, w, pred_type, err_flag)
+
+
 class PerSampleMSEFunction(torch.autograd.Function):
     """mean_flat((target - pred)^2) -> [N] (gaussian_diffusion.py:925, training_losses' "mse" term) with the fixed-order HIP reduction;
     the backward applies the per-sample upstream gradient on the device."""

@@ -332,6 +332,104 @@ extern "C" int rho_spaced_advance(int32_t* k_dev, int32_t* t_dev, const int32_t*
     return 0;
 }
 
+// ----------------------------------------------------------------------------- the spaced walk for v- and x0-prediction
+// rho_p_sample_step_spaced for a backbone that predicts v = sqrt(ab) eps - sqrt(1 - ab) x0 (RHO_PRED_V) or x0 itself
+// (RHO_PRED_SAMPLE).  rows = float32 [S, 8], row k for t = tau_k: {sqrt(ab), sqrt(1 - ab), 1/sqrt(1 - ab) (0 where 1 - ab == 0),
+// sqrt(ab_prev), sigma, sqrt(1 - ab_prev - sigma^2), 0, 0}.  Nothing is divided by sqrt(ab), so a row with ab == 0 is a row like any
+// other.  k, z, clip, the guided [2, n] operands and the 16-byte form follow k_p_sample_spaced; guidance mixes the predictions
+// (both conversions below are affine in p at fixed x, so this is the mix of the two noise estimates).  One written-out contraction
+// for the 16-byte body, its tail and the scalar loop:
+//   v: x0 = fma(sqrt_ab, x, -(sqrt_1mab * p))     sample: x0 = p                    clip: x0 = clamp(x0, -1, 1)
+//   ep = fma(-sqrt_ab, x0, x) * inv_sqrt_1mab;     v without clip: ep = fma(sqrt_1mab, x, sqrt_ab * p)
+//   r  = fma(sqrt_abp, x0, fma(coef_eps, ep, sigma * z))
+// and r = sqrt_abp * x0, ep not formed, where the row has coef_eps == 0 and sigma == 0 (row 0 always).
+struct PredRow {
+    float sqrt_ab, sqrt_1mab, inv_sqrt_1mab, sqrt_abp, sigma, coef_eps;
+    int clip, x0_only;
+};
+template <bool V>
+__device__ __forceinline__ float pred_update(const PredRow& c, float x, float p, float z) {
+    float x0 = V ? __fmaf_rn(c.sqrt_ab, x, -(c.sqrt_1mab * p)) : p;
+    if (c.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    if (c.x0_only) return c.sqrt_abp * x0;
+    const float ep = (V && !c.clip) ? __fmaf_rn(c.sqrt_1mab, x, c.sqrt_ab * p) : __fmaf_rn(-c.sqrt_ab, x0, x) * c.inv_sqrt_1mab;
+    return __fmaf_rn(c.sqrt_abp, x0, __fmaf_rn(c.coef_eps, ep, c.sigma * z));
+}
+template <bool GUIDED, bool V>
+__global__ __launch_bounds__(256) void k_p_sample_spaced_pred(float* __restrict__ x, const float* __restrict__ ph,
+                                                              const float* __restrict__ z, const float* __restrict__ rows,
+                                                              const int32_t* __restrict__ k_dev, int32_t S, float s, int64_t n,
+                                                              int clip, int vec) {
+    const int k = *k_dev;
+    if (k < 0 || k >= S) return;
+    const float* row = rows + 8 * (int64_t)k;
+    const float r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3], r4 = row[4], r5 = row[5];
+    PredRow c;
+    c.sqrt_ab = r0, c.sqrt_1mab = r1, c.inv_sqrt_1mab = r2, c.sqrt_abp = r3;
+    c.coef_eps = r5;
+    c.clip = clip;
+    c.x0_only = ((r5 == 0.0f) & (r4 == 0.0f)) ? 1 : 0;
+    const bool noisy = (z != nullptr) & (r4 != 0.0f);
+    c.sigma = noisy ? r4 : 0.0f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t done = 0;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        float4* xa = (float4*)x;
+        float4* xb = (float4*)(x + n);
+        const float4* pa = (const float4*)ph;
+        const float4* pb = (const float4*)(ph + n);
+        const float4* z4 = (const float4*)z;
+        for (int64_t i = tid; i < n4; i += stride) {
+            float4 a = xa[i];
+            float4 p = pa[i];
+            if (GUIDED) {
+                const float4 pu = pb[i];
+                p.x = cfg_mix(s, p.x, pu.x), p.y = cfg_mix(s, p.y, pu.y), p.z = cfg_mix(s, p.z, pu.z), p.w = cfg_mix(s, p.w, pu.w);
+            }
+            float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (noisy) zz = z4[i];
+            a.x = pred_update<V>(c, a.x, p.x, zz.x);
+            a.y = pred_update<V>(c, a.y, p.y, zz.y);
+            a.z = pred_update<V>(c, a.z, p.z, zz.z);
+            a.w = pred_update<V>(c, a.w, p.w, zz.w);
+            xa[i] = a;
+            if (GUIDED) xb[i] = a;
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + tid; i < n; i += stride) {
+        const float zz = noisy ? z[i] : 0.0f;
+        const float p = GUIDED ? cfg_mix(s, ph[i], ph[n + i]) : ph[i];
+        const float r = pred_update<V>(c, x[i], p, zz);
+        x[i] = r;
+        if (GUIDED) x[n + i] = r;
+    }
+}
+
+extern "C" int rho_p_sample_step_spaced_pred(float* x, const float* pred, const float* z, const float* rows, const int32_t* k_dev,
+                                             int32_t S, int64_t n, int guided, float scale, int clip, int pred_type, void* stream) {
+    if (!x || !pred || !rows || !k_dev || S <= 0 || n <= 0) return RHO_E_ARG;
+    if (pred_type != RHO_PRED_V && pred_type != RHO_PRED_SAMPLE) return RHO_E_ARG;     // epsilon: rho_p_sample_step_spaced
+    const bool aligned = (((uintptr_t)x | (uintptr_t)pred | (uintptr_t)z) & 15) == 0;
+    const int vec = (aligned && (!guided || n % 4 == 0)) ? 1 : 0;
+    const dim3 grid(grid_for(vec ? (n + 3) / 4 : n, 256)), block(256);
+    const int cl = clip ? 1 : 0;
+    const float s = guided ? scale : 0.0f;
+    hipStream_t st = as_stream(stream);
+    if (guided && pred_type == RHO_PRED_V)
+        hipLaunchKernelGGL((k_p_sample_spaced_pred<true, true>), grid, block, 0, st, x, pred, z, rows, k_dev, S, s, n, cl, vec);
+    else if (guided)
+        hipLaunchKernelGGL((k_p_sample_spaced_pred<true, false>), grid, block, 0, st, x, pred, z, rows, k_dev, S, s, n, cl, vec);
+    else if (pred_type == RHO_PRED_V)
+        hipLaunchKernelGGL((k_p_sample_spaced_pred<false, true>), grid, block, 0, st, x, pred, z, rows, k_dev, S, s, n, cl, vec);
+    else
+        hipLaunchKernelGGL((k_p_sample_spaced_pred<false, false>), grid, block, 0, st, x, pred, z, rows, k_dev, S, s, n, cl, vec);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
 // ----------------------------------------------------------------------------- Philox4x32-10 normals
 __device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float& a, float& b) {
     const float f0 = ((float)(u0 >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
@@ -434,6 +532,128 @@ extern "C" int rho_mse(const float* a, const float* b, float* loss, float* grad_
     const int rc = rho_mse_ws(a, b, loss, grad_a, n, partials, g, stream);
     e = hipFreeAsync(partials, as_stream(stream));
     return rc != 0 ? rc : (int)e;
+}
+
+// ----------------------------------------------------------------------------- training loss for eps / v / x0 prediction, min-SNR weights
+// pred, x0, eps float32 [batch, per_sample]; per sample b: ab = alpha_bar[t_b], sa = sqrtf(ab), sb = sqrtf(1 - ab) as k_q_sample
+// forms them, wb = w[t_b] (1 when w == NULL).  The regression target is formed on the fly and never stored:
+//   RHO_PRED_EPSILON: g = eps      RHO_PRED_SAMPLE: g = x0      RHO_PRED_V: g = fma(sa, eps, -(sb * x0))
+//   d = pred - g      acc = fma(wb * d, d, acc)      grad = (wb * (2 / n)) * d          (n = batch * per_sample; 2 / n = 2 * (1.0f / n))
+// One written-out contraction for the 16-byte body, its tail and the scalar form: grad has the same bits in all of them (and, for
+// epsilon with wb == 1, those of k_mse_part); the loss differs between the forms only by which thread adds which element.
+// Geometry and reduction are k_mse_part's: thread sums in element order of its grid-stride walk, wave_sum, the four waves of the block as
+// (r0 + r1) + (r2 + r3), times 1 / n -> partials[block]; k_mse_final adds the partials in index order.  No atomics on the sum.
+// The 16-byte body keeps (sample, offset in the sample) of its piece and advances both by the grid stride, so no division runs in
+// the loop; a piece that straddles a sample boundary (per_sample % 4 != 0) takes its coefficients element by element.
+struct LossCoef {
+    float sa, sb, w, kw;
+};
+template <int TYPE>
+__device__ __forceinline__ LossCoef loss_coef(int64_t b, const float* __restrict__ abar, const float* __restrict__ w,
+                                              const int64_t* __restrict__ t, int64_t table_len, float k2, bool& oob) {
+    int64_t tb = t[b];
+    if (tb < 0 || tb >= table_len) { oob = true; tb = tb < 0 ? 0 : table_len - 1; }
+    LossCoef c;
+    c.sa = c.sb = 0.0f;
+    if (TYPE == RHO_PRED_V) {
+        const float ab = abar[tb];
+        c.sa = sqrtf(ab), c.sb = sqrtf(1.0f - ab);
+    }
+    c.w = w != nullptr ? w[tb] : 1.0f;
+    c.kw = c.w * k2;
+    return c;
+}
+template <int TYPE>
+__device__ __forceinline__ float loss_term(const LossCoef& c, float p, float x, float e, float& acc) {
+    const float g = TYPE == RHO_PRED_EPSILON ? e : (TYPE == RHO_PRED_SAMPLE ? x : __fmaf_rn(c.sa, e, -(c.sb * x)));
+    const float d = p - g;
+    acc = __fmaf_rn(c.w * d, d, acc);
+    return c.kw * d;
+}
+template <int TYPE>
+__global__ __launch_bounds__(256) void k_pred_loss_part(const float* __restrict__ pred, const float* __restrict__ x0,
+                                                        const float* __restrict__ eps, const float* __restrict__ abar,
+                                                        const float* __restrict__ w, const int64_t* __restrict__ t,
+                                                        float* __restrict__ partials, float* __restrict__ grad, int64_t per_sample,
+                                                        int64_t n, int64_t table_len, float inv_n, int vec,
+                                                        int32_t* err_flag) {
+    __shared__ float red[4];
+    float acc = 0.0f;
+    bool oob = false;
+    const float k2 = 2.0f * inv_n;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+    int64_t done = 0;
+    if (vec) {                                   // per_sample >= 4 here: a piece touches at most two samples
+        const int64_t n4 = n >> 2;
+        const float4* p4 = reinterpret_cast<const float4*>(pred);
+        const float4* x4 = reinterpret_cast<const float4*>(x0);
+        const float4* e4 = reinterpret_cast<const float4*>(eps);
+        float4* g4 = reinterpret_cast<float4*>(grad);
+        const int64_t step = 4 * nthr, step_b = step / per_sample, step_r = step % per_sample;
+        int64_t b = (4 * tid) / per_sample, r = (4 * tid) % per_sample;           // element 4 i is element r of sample b
+        for (int64_t i = tid; i < n4; i += nthr) {
+            const float4 p = p4[i], x = x4[i], e = e4[i];
+            const LossCoef c = loss_coef<TYPE>(b, abar, w, t, table_len, k2, oob);
+            float4 g;
+            if (r + 3 < per_sample) {
+                g.x = loss_term<TYPE>(c, p.x, x.x, e.x, acc);
+                g.y = loss_term<TYPE>(c, p.y, x.y, e.y, acc);
+                g.z = loss_term<TYPE>(c, p.z, x.z, e.z, acc);
+                g.w = loss_term<TYPE>(c, p.w, x.w, e.w, acc);
+            } else {                             // elements r + j >= per_sample belong to sample b + 1 (which exists: 4 i + j < n)
+                const LossCoef c1 = loss_coef<TYPE>(b + 1, abar, w, t, table_len, k2, oob);
+                g.x = loss_term<TYPE>(c, p.x, x.x, e.x, acc);
+                g.y = loss_term<TYPE>(r + 1 < per_sample ? c : c1, p.y, x.y, e.y, acc);
+                g.z = loss_term<TYPE>(r + 2 < per_sample ? c : c1, p.z, x.z, e.z, acc);
+                g.w = loss_term<TYPE>(c1, p.w, x.w, e.w, acc);
+            }
+            if (grad) g4[i] = g;
+            b += step_b, r += step_r;
+            if (r >= per_sample) { r -= per_sample; b += 1; }
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + tid; i < n; i += nthr) {
+        const LossCoef c = loss_coef<TYPE>(i / per_sample, abar, w, t, table_len, k2, oob);
+        const float g = loss_term<TYPE>(c, pred[i], x0[i], eps[i], acc);
+        if (grad) grad[i] = g;
+    }
+    if (err_flag != nullptr && __any(oob)) {
+        if ((threadIdx.x & 63) == 0) atomicOr(err_flag, 4);
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * inv_n;
+}
+
+extern "C" int rho_pred_loss_ws(const float* pred, const float* x0, const float* eps, const float* alpha_bar, const float* w,
+                                const int64_t* t, int64_t batch, int64_t per_sample, int64_t table_len, int pred_type, float* loss,
+                                float* grad, float* partials, int64_t n_partials, int32_t* err_flag, void* stream) {
+    if (!pred || !x0 || !eps || !alpha_bar || !t || !loss || !partials || batch <= 0 || per_sample <= 0 || table_len <= 0 ||
+        n_partials < 1)
+        return RHO_E_ARG;
+    if (pred_type != RHO_PRED_EPSILON && pred_type != RHO_PRED_V && pred_type != RHO_PRED_SAMPLE) return RHO_E_ARG;
+    if (batch > INT64_MAX / per_sample) return RHO_E_ARG;
+    const int64_t n = batch * per_sample;
+    int64_t g = grid_for(n, 256 * 8);
+    if (g > n_partials) g = n_partials;
+    const int vec = (per_sample >= 4 && (((uintptr_t)pred | (uintptr_t)x0 | (uintptr_t)eps | (uintptr_t)grad) & 15) == 0) ? 1 : 0;
+    const dim3 grid((unsigned)g), block(256);
+    const float inv_n = 1.0f / (float)n;
+    hipStream_t st = as_stream(stream);
+    if (pred_type == RHO_PRED_EPSILON)
+        hipLaunchKernelGGL(k_pred_loss_part<RHO_PRED_EPSILON>, grid, block, 0, st, pred, x0, eps, alpha_bar, w, t, partials, grad,
+                           per_sample, n, table_len, inv_n, vec, err_flag);
+    else if (pred_type == RHO_PRED_V)
+        hipLaunchKernelGGL(k_pred_loss_part<RHO_PRED_V>, grid, block, 0, st, pred, x0, eps, alpha_bar, w, t, partials, grad,
+                           per_sample, n, table_len, inv_n, vec, err_flag);
+    else
+        hipLaunchKernelGGL(k_pred_loss_part<RHO_PRED_SAMPLE>, grid, block, 0, st, pred, x0, eps, alpha_bar, w, t, partials, grad,
+                           per_sample, n, table_len, inv_n, vec, err_flag);
+    hipLaunchKernelGGL(k_mse_final, dim3(1), dim3(64), 0, as_stream(stream), partials, (int)g, loss);
+    RHO_LAUNCH_CHECK();
+    return 0;
 }
 
 // mean over all non-batch axes (layers.py:105-110, mean_flat): one workgroup per sample, fp32 in a fixed order

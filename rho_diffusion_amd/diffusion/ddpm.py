@@ -13,6 +13,9 @@ The arithmetic runs in the HIP kernels of librho_hip.so:
                       engine's rho_cond_drop applies), guided sampling at batch 2B with rho_p_sample_step_cfg
   * few steps      -> DDIM with eta on a spaced timestep sequence (not in the reference): reverse_process(num_steps=, eta=) walks
                       S of the T timesteps with rho_p_sample_step_spaced / rho_spaced_advance; host side in spaced.py
+  * objective      -> prediction_type "epsilon" (the reference), "v" or "sample", and min-SNR-gamma loss weights (snr_gamma); neither in
+                      the reference: the loss is rho_pred_loss_ws (target formed in the kernel), v / sample models sample on the
+                      spaced walk with rho_p_sample_step_spaced_pred; host side in prediction.py
 Reference quirks are kept deliberately: 0.8*sqrt(beta) noise scale, z = 0 for t <= 1,
 no update at t = 0 although the backbone is evaluated, clamp to [-1, 1] after every update,
 checkpoint spacing T // 10.
@@ -30,7 +33,8 @@ from ..engine import ops
 from ..registry import registry
 from ..utils import sample_from_discrete_parameter_space, save_model_checkpoint
 from .abstract_diffusion import AbstractDiffusionPipeline
-from .spaced import resolve_timesteps, spaced_checkpoints, spaced_coefficients
+from .prediction import PREDICTION_TYPES, check_snr_gamma, min_snr_weights, resolve_prediction_type, spaced_pred_coefficients
+from .spaced import resolve_timesteps, spaced_checkpoints
 
 __all__ = ["DDPM"]
 
@@ -40,7 +44,8 @@ class DDPM(AbstractDiffusionPipeline):
                  cond_fn: str = None, cond_fn_kwargs: dict = None, optimizer=None,
                  opt_kwargs: Union[Mapping[str, Any], None] = {}, t_checkpoints=None, sampling_batch_size=10,
                  sample_every_n_epochs=5, sample_parameter_space=None, save_checkpoint_every_n_epochs=10,
-                 sampling_steps=None, sampling_eta: float = 0.0, guidance_scale=None, cond_drop_prob: float = 0.0):
+                 sampling_steps=None, sampling_eta: float = 0.0, prediction_type: str = "epsilon", snr_gamma=None,
+                 guidance_scale=None, cond_drop_prob: float = 0.0):
         super().__init__(backbone=backbone, backbone_kwargs=backbone_kwargs, schedule=schedule, timesteps=timesteps,
                          cond_fn=cond_fn, cond_fn_kwargs=cond_fn_kwargs, optimizer=optimizer, opt_kwargs=opt_kwargs)
         if isinstance(loss_func, str):
@@ -68,6 +73,16 @@ class DDPM(AbstractDiffusionPipeline):
         self.sampling_steps = sampling_steps
         self.sampling_eta = float(sampling_eta)
         self._spaced_cache = {}
+        # what the backbone predicts - "epsilon" (the reference), "v" (Salimans & Ho 2022) or "sample" (x0) - and min-SNR-gamma
+        # loss weighting (Hang et al. 2023; None: every timestep weighs 1).  With the defaults training_step and reverse_process issue
+        # the reference's launches; anything else trains through rho_pred_loss_ws, which has no torch counterpart on this path.
+        self.prediction_type = resolve_prediction_type(prediction_type)
+        self.snr_gamma = check_snr_gamma(snr_gamma)
+        if (self.prediction_type != "epsilon" or self.snr_gamma is not None) and not (
+                isinstance(self.loss_func, nn.MSELoss) and self.loss_func.reduction == "mean"):
+            raise ValueError(f"prediction_type={self.prediction_type!r} / snr_gamma={self.snr_gamma} need loss_func nn.MSELoss(reduction='mean'): "
+                             f"the weighted loss is a HIP kernel of that form and has no torch fallback; got {self.loss_func!r}")
+        self._snr_weights = {}
         # counter-based RNG state: one stream per rank (seed + rank), offset advances per draw
         self.noise_seed = int(os.environ.get("RHO_SEED", "777")) + int(os.environ.get("RANK", "0"))
         self._noise_offset = 0
@@ -138,11 +153,17 @@ class DDPM(AbstractDiffusionPipeline):
         ``num_steps`` (default: the attribute ``sampling_steps``; None = every timestep, the loop above) samples in few steps:
         a count S takes spaced_timesteps(T, S), a strictly increasing sequence is taken as given, and the walk applies the DDIM
         update with ``eta`` (default: ``sampling_eta``) on those timesteps - _reverse_process_spaced.  ``clip_denoised`` clamps its x0
-        estimate to [-1, 1]; the full loop clamps x_t itself and has no such switch."""
+        estimate to [-1, 1]; the full loop clamps x_t itself and has no such switch.
+
+        The full loop is the reference's (0.8 sqrt(beta) noise, clamp of x_t): parity code for epsilon models, and it stays
+        epsilon-only.  With ``prediction_type`` "v" or "sample" every path is the spaced walk on rho_p_sample_step_spaced_pred:
+        ``num_steps`` None then walks all T timesteps (taus = range(T)) with ``eta``, and a timestep with alpha_bar == 0 is legal."""
         scale = self.guidance_scale if guidance_scale is None else float(guidance_scale)
         if scale is not None:
             self._refuse_unguidable(conditions)
         num_steps = self.sampling_steps if num_steps is None else num_steps
+        if num_steps is None and self.prediction_type != "epsilon":
+            num_steps = range(len(self.schedule["alpha_bar_t"]))
         spaced = None
         if num_steps is not None:
             spaced = self._spaced_host(num_steps, self.sampling_eta if eta is None else eta)      # ValueError before any draw
@@ -272,31 +293,42 @@ class DDPM(AbstractDiffusionPipeline):
 
     # ------------------------------------------------------------------ few-step sampling
     def _spaced_host(self, num_steps, eta) -> dict:
-        """Timesteps and coefficient rows of a spaced walk, cached per (taus, eta): host work only, refusals included."""
+        """Timesteps and coefficient rows of a spaced walk, cached per (taus, eta, prediction type): host work only, refusals
+        included."""
         T = len(self.schedule["alpha_bar_t"])
         taus = tuple(resolve_timesteps(T, num_steps))
         eta = float(eta)
-        key = (taus, eta)
+        pred = self.prediction_type
+        key = (taus, eta, pred)
         if key not in self._spaced_cache:
             with self.schedule:                                                      # float32 tables whatever the data dtype
                 ab = self.schedule["alpha_bar_t"].clone()
-            self._spaced_cache[key] = {"taus": taus, "eta": eta, "rows": spaced_coefficients(ab, taus, eta), "T": T, "dev": {}}
+            self._spaced_cache[key] = {"taus": taus, "eta": eta, "pred": pred, "rows": spaced_pred_coefficients(ab, taus, eta, pred), "T": T,
+                                       "dev": {}}
         return self._spaced_cache[key]
 
     def _spaced_device(self, spaced: dict, dev):
-        """(rows [S, 8] float32, taus [S] int32) on ``dev``, uploaded once per (device, taus, eta)."""
+        """(rows [S, 8] float32, taus [S] int32) on ``dev``, uploaded once per (device, taus, eta, prediction type)."""
         key = str(torch.device(dev))
         if key not in spaced["dev"]:
             spaced["dev"][key] = (spaced["rows"].contiguous().to(dev), torch.tensor(spaced["taus"], dtype=torch.int32).to(dev))
         return spaced["dev"][key]
 
+    def _spaced_update(self, x_all, pred, z, rows, k_dev, scale, clip, kind) -> None:
+        """The update of one step of the spaced walk, by what the backbone predicts: the rows are of that kind (_spaced_host)."""
+        if kind == "epsilon":
+            ops.p_sample_step_spaced(x_all, pred, z, rows, k_dev, scale, clip)
+        else:
+            ops.p_sample_step_spaced_pred(x_all, pred, z, rows, k_dev, PREDICTION_TYPES[kind], scale, clip)
+
     def _reverse_process_spaced(self, x_all, x_t, cc, engine, scale, spaced, clip, t_dev, buf) -> dict:
         """The walk over ``spaced["taus"]`` from the top, k = S-1 .. 0: draw z (eta > 0 and k >= 1 only, before the backbone call as
-        in the full loop), evaluate the backbone at t = tau_k, rho_p_sample_step_spaced on row k, checkpoint, rho_spaced_advance.
+        in the full loop), evaluate the backbone at t = tau_k, rho_p_sample_step_spaced (rho_p_sample_step_spaced_pred for a v or
+        x0 model) on row k, checkpoint, rho_spaced_advance.
         ``x_all`` is what the backbone reads and the update writes: ``x_t``, or under guidance the doubled batch whose first half
         ``x_t`` is (``cc`` then carries the null rows).  k and t live on the device, so one captured graph serves every step
         (_reverse_process_spaced_graph)."""
-        taus, eta = spaced["taus"], spaced["eta"]
+        taus, eta, kind = spaced["taus"], spaced["eta"], spaced["pred"]
         S = len(taus)
         dev = x_all.device
         batch_size = x_t.size(0)
@@ -308,7 +340,8 @@ class DDPM(AbstractDiffusionPipeline):
         result = {"buffer": buf, "denoised": x_t}
         if (self.hip_graph_sampling and engine is not None and S > 2 and "noise" not in self.__dict__
                 and type(self).noise is DDPM.noise):
-            if self._reverse_process_spaced_graph(x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt):
+            if self._reverse_process_spaced_graph(x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt,
+                                                  kind):
                 self._check_backbone_errors()
                 return result
             k_dev.fill_(S - 1)
@@ -320,7 +353,7 @@ class DDPM(AbstractDiffusionPipeline):
                 pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
             else:
                 pred = self.backbone(x_t, torch.full((batch_size,), taus[k], device=dev, dtype=torch.long), cc)
-            ops.p_sample_step_spaced(x_all, pred.contiguous(), z, rows, k_dev, scale, clip)
+            self._spaced_update(x_all, pred.contiguous(), z, rows, k_dev, scale, clip, kind)
             if buf is not None and taus[k] in ckpt and t_idx < num_checkpoints:
                 buf[:, t_idx].copy_(x_t)
                 t_idx += 1
@@ -328,7 +361,8 @@ class DDPM(AbstractDiffusionPipeline):
         self._check_backbone_errors()
         return result
 
-    def _reverse_process_spaced_graph(self, x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt) -> bool:
+    def _reverse_process_spaced_graph(self, x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt,
+                                      kind="epsilon") -> bool:
         """_reverse_process_graph for the spaced walk: step S-1 runs eagerly (it builds the engine plan), one captured step is
         replayed S-1 times.  With eta > 0 the captured step draws z at every replay from the device-side offset; the draw of k = 0
         is ignored by the kernel (row 0 has sigma = 0) and not counted, so the offset ends where the eager loop leaves it.  With
@@ -345,7 +379,7 @@ class DDPM(AbstractDiffusionPipeline):
             if noisy:
                 ops.philox_normal(z, self.noise_seed, 0, offset_dev=off_dev)
             pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
-            ops.p_sample_step_spaced(x_all, pred, z, rows, k_dev, scale, clip)
+            self._spaced_update(x_all, pred, z, rows, k_dev, scale, clip, kind)
             ops.spaced_advance(k_dev, t_dev, taus_dev, off_dev, delta)
 
         t_idx = 0
@@ -395,6 +429,17 @@ class DDPM(AbstractDiffusionPipeline):
         self._noise_offset += (batch_size + 3) // 4
         return keep
 
+    def _snr_weight_table(self, dev):
+        """float32 [T] min-SNR-gamma weights of this objective on ``dev`` (None without ``snr_gamma``), built once per (device, objective, gamma)."""
+        if self.snr_gamma is None:
+            return None
+        key = (str(torch.device(dev)), self.prediction_type, self.snr_gamma)
+        if key not in self._snr_weights:
+            with self.schedule:                                                      # float32 tables whatever the data dtype
+                ab = self.schedule["alpha_bar_t"].clone()
+            self._snr_weights[key] = min_snr_weights(ab, self.prediction_type, self.snr_gamma).contiguous().to(dev)
+        return self._snr_weights[key]
+
     def _check_nan(self, force: bool = False) -> None:
         """Device-side form of the per-step host check at ddpm.py:268-272: the flag is set by the
         q_sample kernel and polled every ``nan_check_every`` steps instead of syncing each step.
@@ -414,7 +459,9 @@ class DDPM(AbstractDiffusionPipeline):
                 sys.exit(0)
 
     def training_step(self, batch: Iterable[Any], batch_idx: int = 0):
-        """ddpm.py:231-288: eps-prediction objective."""
+        """ddpm.py:231-288: eps-prediction objective; with ``prediction_type`` / ``snr_gamma`` set the backbone is regressed onto v or
+        x0 instead and timestep t weighs min_snr_weights[t] (rho_pred_loss_ws: the target is formed in the kernel from the clean data,
+        the noise and t)."""
         if isinstance(batch, list):
             data, labels = batch
         elif isinstance(batch, dict):
@@ -442,7 +489,13 @@ class DDPM(AbstractDiffusionPipeline):
             pred_noise = self.backbone(x_data, t, labels)
         else:
             pred_noise = self.backbone(x_data, t)
-        if isinstance(self.loss_func, nn.MSELoss) and self.loss_func.reduction == "mean":
+        if self.prediction_type != "epsilon" or self.snr_gamma is not None:
+            from ..autograd import pred_loss
+            dev = pred_noise.device
+            loss = pred_loss(pred_noise, data, noise, t.reshape(-1).to(device=dev, dtype=torch.int64).contiguous(),
+                             self.schedule.device_tables(dev)["alpha_bar"], self._snr_weight_table(dev),
+                             PREDICTION_TYPES[self.prediction_type], self._nan_flag)       # a bad t: bit 2, raised by _check_nan
+        elif isinstance(self.loss_func, nn.MSELoss) and self.loss_func.reduction == "mean":
             from ..autograd import mse_loss
             loss = mse_loss(pred_noise, noise)           # HIP reduction + gradient (rho_mse)
         else:

@@ -97,6 +97,31 @@ def p_sample_step_spaced(x: Tensor, eps_hat: Tensor, z: Optional[Tensor], rows: 
     return x
 
 
+def p_sample_step_spaced_pred(x: Tensor, pred: Tensor, z: Optional[Tensor], rows: Tensor, k_dev: Tensor, pred_type: int,
+                              scale: Optional[float] = None, clip: bool = True) -> Tensor:
+    """One reverse update of the spaced walk of a v- or x0-predicting backbone (rho_p_sample_step_spaced_pred): row ``*k_dev`` of
+    ``rows`` [S, 8] as spaced_pred_coefficients writes them, ``pred_type`` 1 (v) or 2 (sample).  ``scale`` / ``z`` / ``clip`` as in
+    p_sample_step_spaced."""
+    _f32c(x, "x"), _f32c(pred, "pred"), _f32c(rows, "rows")
+    if z is not None:
+        _f32c(z, "z")
+    if rows.dim() != 2 or rows.shape[1] != 8 or rows.shape[0] < 1:
+        raise RhoHipError(f"rows must be float32 [S, 8], got {tuple(rows.shape)}")
+    if pred_type not in (1, 2):
+        raise RhoHipError(f"pred_type must be 1 (v) or 2 (sample), got {pred_type}: epsilon takes p_sample_step_spaced")
+    guided = scale is not None
+    n = x.numel() // 2 if guided else x.numel()
+    if n < 1 or x.numel() != (2 * n if guided else n) or pred.numel() != x.numel() or (z is not None and z.numel() != n):
+        raise RhoHipError(f"x / pred hold {'two rows' if guided else 'one row'} of n elements and z one: got {x.numel()}, "
+                          f"{pred.numel()}, {None if z is None else z.numel()}")
+    if k_dev.dtype != torch.int32 or not k_dev.is_cuda or k_dev.numel() != 1:
+        raise RhoHipError("k_dev must be int32[1] on the GPU")
+    check(hip.lib().rho_p_sample_step_spaced_pred(ptr(x), ptr(pred), ptr(z), ptr(rows), ptr(k_dev), rows.shape[0], n, int(guided),
+                                                  float(scale) if guided else 0.0, int(bool(clip)), int(pred_type), stream()),
+          "rho_p_sample_step_spaced_pred")
+    return x
+
+
 def spaced_advance(k_dev: Tensor, t_dev: Tensor, taus: Tensor, offset_dev: Optional[Tensor], delta: int) -> None:
     """k <- k - 1, t <- taus[k] while k >= 0, offset += delta (rho_spaced_advance): the loop state of the spaced walk."""
     for name, t in (("k_dev", k_dev), ("t_dev", t_dev)):
@@ -431,6 +456,32 @@ def mse(a: Tensor, b: Tensor, want_grad: bool = False) -> Tuple[Tensor, Optional
     loss = buf[:1]
     grad = torch.empty_like(a) if want_grad else None
     check(hip.lib().rho_mse_ws(ptr(a), ptr(b), ptr(loss), ptr(grad), a.numel(), buf.data_ptr() + 4, 1024, stream()), "rho_mse_ws")
+    return loss, grad
+
+
+def pred_loss(pred: Tensor, x0: Tensor, eps: Tensor, t: Tensor, alpha_bar: Tensor, w: Optional[Tensor], pred_type: int,
+              want_grad: bool = False, err_flag: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+    """The weighted training loss of an eps- (0), v- (1) or x0-predicting (2) backbone and optionally its gradient w.r.t. ``pred``
+    (rho_pred_loss_ws).  ``pred`` / ``x0`` / ``eps`` [B, ...] float32, ``t`` int64 [B] on the device, ``alpha_bar`` [T] and ``w`` [T]
+    or None (weight 1)."""
+    _f32c(pred, "pred"), _f32c(x0, "x0"), _f32c(eps, "eps"), _f32c(alpha_bar, "alpha_bar")
+    if x0.shape != pred.shape or eps.shape != pred.shape or pred.dim() < 1 or pred.numel() < 1:
+        raise RhoHipError(f"pred, x0 and eps must have one non-empty shape: got {tuple(pred.shape)}, {tuple(x0.shape)}, {tuple(eps.shape)}")
+    B = pred.shape[0]
+    if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.numel() != B:
+        raise RhoHipError(f"t must be a contiguous int64 [{B}] GPU tensor")
+    if w is not None and (_f32c(w, "w").numel() != alpha_bar.numel()):
+        raise RhoHipError(f"w must have the {alpha_bar.numel()} entries of alpha_bar, got {w.numel()}")
+    if pred_type not in (0, 1, 2):
+        raise RhoHipError(f"pred_type must be 0 (epsilon), 1 (v) or 2 (sample), got {pred_type}")
+    if err_flag is not None and (err_flag.dtype != torch.int32 or not err_flag.is_cuda or err_flag.numel() != 1):
+        raise RhoHipError("err_flag must be int32[1] on the GPU or None")
+    buf = torch.empty(1 + 1024, dtype=torch.float32, device=pred.device)     # loss + the ordered reduction's block partials
+    loss = buf[:1]
+    grad = torch.empty_like(pred) if want_grad else None
+    check(hip.lib().rho_pred_loss_ws(ptr(pred), ptr(x0), ptr(eps), ptr(alpha_bar), ptr(w), ptr(t), B, pred.numel() // B,
+                                     alpha_bar.numel(), int(pred_type), ptr(loss), ptr(grad), buf.data_ptr() + 4, 1024, ptr(err_flag),
+                                     stream()), "rho_pred_loss_ws")
     return loss, grad
 
 

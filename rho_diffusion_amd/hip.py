@@ -78,9 +78,13 @@ SIGNATURES = {
     "rho_p_sample_step_spaced": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int, c_float, c_int,
                                          c_void_p]),
     "rho_spaced_advance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
+    "rho_p_sample_step_spaced_pred": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int, c_float, c_int,
+                                              c_int, c_void_p]),
     "rho_philox_normal": (c_int, [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p]),
     "rho_mse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "rho_mse_ws": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "rho_pred_loss_ws": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rho_mean_flat": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "rho_set_deterministic": (c_int, [c_int]),
     "rho_get_deterministic": (c_int, []),
