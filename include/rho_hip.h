@@ -39,7 +39,7 @@ extern "C" {
  * 10: learned variances - RHO_GD_LOG_BETA, the *_lv / strided / hybrid-loss entry points; the dataset entry points added since -
  * rho_crop_resize, rho_line_profile, rho_pil_resize_taps, rho_u8_image_batch, the guidance trio rho_p_sample_step_cfg,
  * rho_cond_keep_mask, rho_cond_drop, the query rho_attention_variant, and the spaced-walk pair rho_p_sample_step_spaced,
- * rho_spaced_advance, and the prediction-type pair rho_pred_loss_ws, rho_p_sample_step_spaced_pred - change no existing signature or
+ * rho_spaced_advance, and the prediction-type pair rho_pred_loss_ws, rho_p_sample_step_spaced_pred, and the multistep solver's rho_dpmpp_2m_step - change no existing signature or
  * struct, so by this
  * rule they leave it at 10: a binding that lacks them fails on the missing symbol).  A loader must compare rho_abi_version() with the header it was written against
  * before calling anything else (hip.py does; a build with all symbols but older signatures would be called with shifted arguments). */
@@ -124,6 +124,27 @@ int rho_spaced_advance(int32_t* k_dev, int32_t* t_dev, const int32_t* taus, uint
  * and x <- sqrt_abp * x0, ep not formed, where the row has coef_eps == 0 and sigma == 0 (always row 0). */
 int rho_p_sample_step_spaced_pred(float* x, const float* pred, const float* z, const float* rows, const int32_t* k_dev, int32_t S,
                                   int64_t n, int guided, float scale, int clip, int pred_type, void* stream);
+
+/* One step of DPM-Solver++(2M) (Lu et al. 2022, the data-prediction second-order multistep solver; none of this in the reference) on
+ * the spaced walk, for every pred_type (RHO_PRED_EPSILON, RHO_PRED_V, RHO_PRED_SAMPLE; anything else: RHO_E_ARG).  rows float32 [S, 8]
+ * on the device, row k for the step from t = tau_k to tau_{k-1} with alpha = sqrt(ab), sigma = sqrt(1 - ab), primes for ab_prev
+ * (1 for k = 0), lam = log(alpha / sigma), h = lam' - lam, r = h_prev / h (h_prev: the h of row k + 1):
+ *   {a_x, a_p, c_x = sigma'/sigma, c_d0 = c_0 (1 + 1/(2r)), c_d1 = -c_0 / (2r), 0, 0, 0},   c_0 = alpha' (1 - e^{-h})
+ * with a_x = sqrt(1/ab), a_p = sqrt(1/ab - 1) for EPSILON, a_x = sqrt(ab), a_p = sqrt(1 - ab) for V, both unused for SAMPLE;
+ * first-order rows (row S-1, row 0, a step whose h or h_prev is not finite) carry c_d1 = 0, c_d0 = c_0, and row 0 is
+ * {a_x, a_p, 0, 1, 0}.  hist float32 [n] - one row, also under guidance - holds the x0 estimate of the step before; it is read only
+ * where the row has c_d1 != 0 (so it may be uninitialised at the first step of a walk) and always receives this step's estimate.
+ * k_dev, S, guided / scale, clip and the store to both rows of x under guidance are those of rho_p_sample_step_spaced (k outside
+ * [0, S) writes nothing, neither x nor hist); guidance mixes the predictions, p = fma(scale, p_c - p_u, p_u), guided == 0: p = pred.
+ * The 16-byte form needs 16-byte aligned x / pred / hist and, guided, n % 4 == 0; every other case gives the same bits.  One
+ * contraction shared by every form:
+ *   x0 = fma(a_x, x, -(a_p * p))        RHO_PRED_SAMPLE: x0 = p            clip != 0:  x0 = clamp(x0, -1, 1)
+ *   c_d1 != 0:               x' = fma(c_x, x, fma(c_d0, x0, c_d1 * hist))
+ *   c_d1 == 0:               x' = fma(c_x, x, c_d0 * x0)                   c_d1 == 0 and c_x == 0:  x' = c_d0 * x0
+ *   hist <- x0 (the clamped value);   x <- x'
+ * No noise is drawn: the solver is deterministic.  rho_spaced_advance serves this walk unchanged. */
+int rho_dpmpp_2m_step(float* x, const float* pred, float* hist, const float* rows, const int32_t* k_dev, int32_t S, int64_t n,
+                      int guided, float scale, int clip, int pred_type, void* stream);
 
 /* Counter-based Philox4x32-10 standard normals (Box-Muller), replaces torch.randn_like at
  * ddpm.py:101-102,171,197.  out float32[n]; stream of (seed, offset) is reproducible and

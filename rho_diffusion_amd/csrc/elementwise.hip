@@ -430,6 +430,127 @@ extern "C" int rho_p_sample_step_spaced_pred(float* x, const float* pred, const 
     return 0;
 }
 
+// ----------------------------------------------------------------------------- DPM-Solver++(2M) on the spaced walk
+// The second-order multistep update (Lu et al. 2022; the reference has no few-step sampler) in place of the DDIM one, for all three
+// prediction types.  rows = float32 [S, 8], row k for the step from tau_k: {a_x, a_p, c_x, c_d0, c_d1, 0, 0, 0}
+// (dpmpp_2m_coefficients).  hist float32 [n], one row also under guidance: the x0 estimate the step before left behind, read only
+// where c_d1 != 0 (the first step of a walk has none: the buffer may be uninitialised) and always overwritten with this step's.
+// k, clip, the guided [2, n] operands and the 16-byte form follow k_p_sample_spaced; no noise enters.  One written-out contraction
+// for the 16-byte body, its tail and the scalar loop:
+//   x0 = fma(a_x, x, -(a_p * p))   (sample: x0 = p)        clip: x0 = clamp(x0, -1, 1)
+//   c_d1 != 0: r = fma(c_x, x, fma(c_d0, x0, c_d1 * hist))     c_d1 == 0: r = fma(c_x, x, c_d0 * x0), or c_d0 * x0 where c_x == 0
+struct Dpm2mRow {
+    float a_x, a_p, c_x, c_d0, c_d1;
+    int clip;
+};
+template <int TYPE>
+__device__ __forceinline__ float dpm2m_x0(const Dpm2mRow& c, float x, float p) {
+    float x0 = TYPE == RHO_PRED_SAMPLE ? p : __fmaf_rn(c.a_x, x, -(c.a_p * p));
+    if (c.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    return x0;
+}
+// ORDER 2: the row has c_d1 != 0; ORDER 1: c_d1 == 0, h is not used; ORDER 0: c_d1 == 0 and c_x == 0, the x0 estimate scaled
+template <int ORDER>
+__device__ __forceinline__ float dpm2m_update(const Dpm2mRow& c, float x, float x0, float h) {
+    if (ORDER == 2) return __fmaf_rn(c.c_x, x, __fmaf_rn(c.c_d0, x0, c.c_d1 * h));
+    if (ORDER == 1) return __fmaf_rn(c.c_x, x, c.c_d0 * x0);
+    return c.c_d0 * x0;
+}
+template <bool GUIDED, int TYPE, int ORDER>
+__device__ __forceinline__ void dpm2m_walk(const Dpm2mRow& c, float* __restrict__ x, const float* __restrict__ ph,
+                                           float* __restrict__ hist, float s, int64_t n, int vec) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t done = 0;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        float4* xa = (float4*)x;
+        float4* xb = (float4*)(x + n);
+        const float4* pa = (const float4*)ph;
+        const float4* pb = (const float4*)(ph + n);
+        float4* h4 = (float4*)hist;
+        for (int64_t i = tid; i < n4; i += stride) {
+            float4 a = xa[i];
+            float4 p = pa[i];
+            if (GUIDED) {
+                const float4 pu = pb[i];
+                p.x = cfg_mix(s, p.x, pu.x), p.y = cfg_mix(s, p.y, pu.y), p.z = cfg_mix(s, p.z, pu.z), p.w = cfg_mix(s, p.w, pu.w);
+            }
+            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ORDER == 2) h = h4[i];
+            float4 e;
+            e.x = dpm2m_x0<TYPE>(c, a.x, p.x), e.y = dpm2m_x0<TYPE>(c, a.y, p.y);
+            e.z = dpm2m_x0<TYPE>(c, a.z, p.z), e.w = dpm2m_x0<TYPE>(c, a.w, p.w);
+            a.x = dpm2m_update<ORDER>(c, a.x, e.x, h.x);
+            a.y = dpm2m_update<ORDER>(c, a.y, e.y, h.y);
+            a.z = dpm2m_update<ORDER>(c, a.z, e.z, h.z);
+            a.w = dpm2m_update<ORDER>(c, a.w, e.w, h.w);
+            h4[i] = e;
+            xa[i] = a;
+            if (GUIDED) xb[i] = a;
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + tid; i < n; i += stride) {
+        const float xi = x[i];
+        const float p = GUIDED ? cfg_mix(s, ph[i], ph[n + i]) : ph[i];
+        const float h = ORDER == 2 ? hist[i] : 0.0f;
+        const float e = dpm2m_x0<TYPE>(c, xi, p);
+        const float r = dpm2m_update<ORDER>(c, xi, e, h);
+        hist[i] = e;
+        x[i] = r;
+        if (GUIDED) x[n + i] = r;
+    }
+}
+template <bool GUIDED, int TYPE>
+__global__ __launch_bounds__(256) void k_dpmpp_2m_step(float* __restrict__ x, const float* __restrict__ ph, float* __restrict__ hist,
+                                                       const float* __restrict__ rows, const int32_t* __restrict__ k_dev, int32_t S,
+                                                       float s, int64_t n, int clip, int vec) {
+    const int k = *k_dev;
+    if (k < 0 || k >= S) return;
+    const float* row = rows + 8 * (int64_t)k;
+    // the whole row up front, unconditionally, as k_p_sample_spaced loads it
+    const float r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3], r4 = row[4];
+    Dpm2mRow c;
+    c.a_x = r0, c.a_p = r1, c.c_x = r2, c.c_d0 = r3, c.c_d1 = r4;
+    c.clip = clip;
+    // uniform: the row is the same for every lane of the launch
+    if (r4 != 0.0f)
+        dpm2m_walk<GUIDED, TYPE, 2>(c, x, ph, hist, s, n, vec);
+    else if (r2 != 0.0f)
+        dpm2m_walk<GUIDED, TYPE, 1>(c, x, ph, hist, s, n, vec);
+    else
+        dpm2m_walk<GUIDED, TYPE, 0>(c, x, ph, hist, s, n, vec);
+}
+
+template <bool GUIDED>
+static void dpmpp_2m_launch(int pred_type, dim3 grid, dim3 block, hipStream_t st, float* x, const float* pred, float* hist,
+                            const float* rows, const int32_t* k_dev, int32_t S, float s, int64_t n, int cl, int vec) {
+    if (pred_type == RHO_PRED_EPSILON)
+        hipLaunchKernelGGL((k_dpmpp_2m_step<GUIDED, RHO_PRED_EPSILON>), grid, block, 0, st, x, pred, hist, rows, k_dev, S, s, n, cl, vec);
+    else if (pred_type == RHO_PRED_V)
+        hipLaunchKernelGGL((k_dpmpp_2m_step<GUIDED, RHO_PRED_V>), grid, block, 0, st, x, pred, hist, rows, k_dev, S, s, n, cl, vec);
+    else
+        hipLaunchKernelGGL((k_dpmpp_2m_step<GUIDED, RHO_PRED_SAMPLE>), grid, block, 0, st, x, pred, hist, rows, k_dev, S, s, n, cl, vec);
+}
+
+extern "C" int rho_dpmpp_2m_step(float* x, const float* pred, float* hist, const float* rows, const int32_t* k_dev, int32_t S,
+                                 int64_t n, int guided, float scale, int clip, int pred_type, void* stream) {
+    if (!x || !pred || !hist || !rows || !k_dev || S <= 0 || n <= 0) return RHO_E_ARG;
+    if (pred_type != RHO_PRED_EPSILON && pred_type != RHO_PRED_V && pred_type != RHO_PRED_SAMPLE) return RHO_E_ARG;
+    const bool aligned = (((uintptr_t)x | (uintptr_t)pred | (uintptr_t)hist) & 15) == 0;
+    const int vec = (aligned && (!guided || n % 4 == 0)) ? 1 : 0;
+    const dim3 grid(grid_for(vec ? (n + 3) / 4 : n, 256)), block(256);
+    const int cl = clip ? 1 : 0;
+    hipStream_t st = as_stream(stream);
+    if (guided)
+        dpmpp_2m_launch<true>(pred_type, grid, block, st, x, pred, hist, rows, k_dev, S, scale, n, cl, vec);
+    else
+        dpmpp_2m_launch<false>(pred_type, grid, block, st, x, pred, hist, rows, k_dev, S, 0.0f, n, cl, vec);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
 // ----------------------------------------------------------------------------- Philox4x32-10 normals
 __device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float& a, float& b) {
     const float f0 = ((float)(u0 >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)

@@ -16,12 +16,15 @@ The arithmetic runs in the HIP kernels of librho_hip.so:
   * objective      -> prediction_type "epsilon" (the reference), "v" or "sample", and min-SNR-gamma loss weights (snr_gamma); neither in
                       the reference: the loss is rho_pred_loss_ws (target formed in the kernel), v / sample models sample on the
                       spaced walk with rho_p_sample_step_spaced_pred; host side in prediction.py
+  * solver         -> sampler "dpmpp_2m", DPM-Solver++(2M) on log-SNR spaced timesteps (not in the reference): the spaced walk with
+                      rho_dpmpp_2m_step and an x0 history on the device; host side in multistep.py
 Reference quirks are kept deliberately: 0.8*sqrt(beta) noise scale, z = 0 for t <= 1,
 no update at t = 0 although the backbone is evaluated, clamp to [-1, 1] after every update,
 checkpoint spacing T // 10.
 """
 from __future__ import annotations
 
+import numbers
 import os
 from typing import Any, Iterable, Mapping, Union
 
@@ -33,6 +36,7 @@ from ..engine import ops
 from ..registry import registry
 from ..utils import sample_from_discrete_parameter_space, save_model_checkpoint
 from .abstract_diffusion import AbstractDiffusionPipeline
+from .multistep import SAMPLERS, SPACINGS, dpmpp_2m_coefficients, logsnr_timesteps
 from .prediction import PREDICTION_TYPES, check_snr_gamma, min_snr_weights, resolve_prediction_type, spaced_pred_coefficients
 from .spaced import resolve_timesteps, spaced_checkpoints
 
@@ -45,7 +49,7 @@ class DDPM(AbstractDiffusionPipeline):
                  opt_kwargs: Union[Mapping[str, Any], None] = {}, t_checkpoints=None, sampling_batch_size=10,
                  sample_every_n_epochs=5, sample_parameter_space=None, save_checkpoint_every_n_epochs=10,
                  sampling_steps=None, sampling_eta: float = 0.0, prediction_type: str = "epsilon", snr_gamma=None,
-                 guidance_scale=None, cond_drop_prob: float = 0.0):
+                 sampler: str = "ddim", sampling_spacing=None, guidance_scale=None, cond_drop_prob: float = 0.0):
         super().__init__(backbone=backbone, backbone_kwargs=backbone_kwargs, schedule=schedule, timesteps=timesteps,
                          cond_fn=cond_fn, cond_fn_kwargs=cond_fn_kwargs, optimizer=optimizer, opt_kwargs=opt_kwargs)
         if isinstance(loss_func, str):
@@ -73,6 +77,13 @@ class DDPM(AbstractDiffusionPipeline):
         self.sampling_steps = sampling_steps
         self.sampling_eta = float(sampling_eta)
         self._spaced_cache = {}
+        # the update of the few-step walk and how a step count picks its timesteps: the defaults of reverse_process_with(sampler=,
+        # spacing=).  "ddim" is the first-order update above; "dpmpp_2m" is DPM-Solver++(2M) (Lu et al. 2022), second order at the
+        # same number of backbone calls, deterministic (eta must be 0).  Spacing "uniform" is spaced_timesteps, "logsnr" is
+        # logsnr_timesteps; None takes "uniform" for ddim and "logsnr" for dpmpp_2m, whose extrapolation needs steps of similar size
+        # in log-SNR.
+        self.sampler = self._check_sampler(sampler)
+        self.sampling_spacing = self._check_spacing(sampling_spacing)
         # what the backbone predicts - "epsilon" (the reference), "v" (Salimans & Ho 2022) or "sample" (x0) - and min-SNR-gamma
         # loss weighting (Hang et al. 2023; None: every timestep weighs 1).  With the defaults training_step and reverse_process issue
         # the reference's launches; anything else trains through rho_pred_loss_ws, which has no torch counterpart on this path.
@@ -141,10 +152,31 @@ class DDPM(AbstractDiffusionPipeline):
         if getattr(self.backbone, "num_classes", None) is None:
             raise ValueError("guidance_scale needs a class-conditional backbone (num_classes is None)")
 
+    @staticmethod
+    def _check_sampler(name) -> str:
+        if isinstance(name, str) and name in SAMPLERS:
+            return name
+        raise ValueError(f"sampler must be one of {', '.join(repr(s) for s in SAMPLERS)}: got {name!r}")
+
+    @staticmethod
+    def _check_spacing(name):
+        if name is None or (isinstance(name, str) and name in SPACINGS):
+            return name
+        raise ValueError(f"spacing must be None or one of {', '.join(repr(s) for s in SPACINGS)}: got {name!r}")
+
     @torch.no_grad()  # (reference: inference_mode; no_grad keeps the plan buffers usable in training too)
     def reverse_process(self, x_T: Tensor, conditions=None, t_checkpoints=None, guidance_scale=None, num_steps=None, eta=None,
                         clip_denoised: bool = True) -> dict:
-        """ddpm.py:132-229.  ``x_T`` is only a shape/device template (:171).  ``guidance_scale`` (default: the attribute of that
+        """reverse_process_with under the attributes ``sampler`` and ``sampling_spacing``: the reference's method and its keywords,
+        unchanged.  The update of the few-step walk and the timestep spacing are chosen on the pipeline (DDPM(sampler=,
+        sampling_spacing=), or by setting the attributes), or per call through reverse_process_with."""
+        return self.reverse_process_with(x_T, conditions, t_checkpoints, guidance_scale, num_steps, eta, clip_denoised)
+
+    @torch.no_grad()
+    def reverse_process_with(self, x_T: Tensor, conditions=None, t_checkpoints=None, guidance_scale=None, num_steps=None, eta=None,
+                             clip_denoised: bool = True, sampler=None, spacing=None) -> dict:
+        """reverse_process with the sampler and the spacing chosen per call (reverse_process itself keeps the keywords it had).
+        ddpm.py:132-229.  ``x_T`` is only a shape/device template (:171).  ``guidance_scale`` (default: the attribute of that
         name; None = the reference's loop) samples with classifier-free guidance: the engine runs at batch 2B on
         cat(x_t, x_t) with cat(embedded labels, zeros), rho_p_sample_step_cfg combines the two predictions, applies the update
         and writes it to both halves.  The noise draws, their Philox offsets and the returned shapes are those of the unguided
@@ -157,16 +189,31 @@ class DDPM(AbstractDiffusionPipeline):
 
         The full loop is the reference's (0.8 sqrt(beta) noise, clamp of x_t): parity code for epsilon models, and it stays
         epsilon-only.  With ``prediction_type`` "v" or "sample" every path is the spaced walk on rho_p_sample_step_spaced_pred:
-        ``num_steps`` None then walks all T timesteps (taus = range(T)) with ``eta``, and a timestep with alpha_bar == 0 is legal."""
+        ``num_steps`` None then walks all T timesteps (taus = range(T)) with ``eta``, and a timestep with alpha_bar == 0 is legal.
+
+        ``sampler`` (default: the attribute of that name) chooses the update of the spaced walk: "ddim" as above, or "dpmpp_2m",
+        DPM-Solver++(2M) on rho_dpmpp_2m_step - second order, no noise (``eta`` must be 0), for every prediction type; it needs
+        a walk, so an epsilon model must give ``num_steps``.  ``spacing`` (default: ``sampling_spacing``) says how a step COUNT picks
+        its timesteps: "uniform" (spaced_timesteps), "logsnr" (logsnr_timesteps), None = "uniform" for ddim and "logsnr" for
+        dpmpp_2m; with an explicit sequence a spacing is refused."""
         scale = self.guidance_scale if guidance_scale is None else float(guidance_scale)
         if scale is not None:
             self._refuse_unguidable(conditions)
+        sampler = self.sampler if sampler is None else self._check_sampler(sampler)
+        if spacing is None and num_steps is not None and not isinstance(num_steps, numbers.Integral):
+            spacing = None                                  # a sequence given with the call outranks the attribute's spacing
+        else:
+            spacing = self.sampling_spacing if spacing is None else self._check_spacing(spacing)
         num_steps = self.sampling_steps if num_steps is None else num_steps
         if num_steps is None and self.prediction_type != "epsilon":
             num_steps = range(len(self.schedule["alpha_bar_t"]))
+            spacing = None                                  # every timestep: nothing to choose
+        if num_steps is None and sampler != "ddim":
+            raise ValueError(f"sampler={sampler!r} walks a timestep sequence: give num_steps (the full loop of an epsilon model is the "
+                             "reference's ancestral sampler)")
         spaced = None
         if num_steps is not None:
-            spaced = self._spaced_host(num_steps, self.sampling_eta if eta is None else eta)      # ValueError before any draw
+            spaced = self._spaced_host(num_steps, self.sampling_eta if eta is None else eta, sampler, spacing)   # ValueError before any draw
         elif not clip_denoised:
             raise ValueError("clip_denoised=False needs num_steps: the full loop clamps x_t after every update as the reference does")
         hip.require_gpu(x_T, "x_T")
@@ -292,19 +339,32 @@ class DDPM(AbstractDiffusionPipeline):
         return True
 
     # ------------------------------------------------------------------ few-step sampling
-    def _spaced_host(self, num_steps, eta) -> dict:
-        """Timesteps and coefficient rows of a spaced walk, cached per (taus, eta, prediction type): host work only, refusals
-        included."""
+    def _alpha_bar32(self) -> Tensor:
+        with self.schedule:                                                          # float32 tables whatever the data dtype
+            return self.schedule["alpha_bar_t"].clone()
+
+    def _spaced_host(self, num_steps, eta, sampler: str = "ddim", spacing=None) -> dict:
+        """Timesteps and coefficient rows of a spaced walk, cached per (taus, eta, prediction type, sampler): host work only, refusals
+        included.  ``spacing`` picks the timesteps of a step count (None: "uniform" for ddim, "logsnr" for dpmpp_2m) and is refused
+        with an explicit sequence; the rows are spaced_pred_coefficients for "ddim", dpmpp_2m_coefficients for "dpmpp_2m"."""
         T = len(self.schedule["alpha_bar_t"])
-        taus = tuple(resolve_timesteps(T, num_steps))
+        sampler, spacing = self._check_sampler(sampler), self._check_spacing(spacing)
         eta = float(eta)
+        if sampler == "dpmpp_2m" and eta != 0.0:
+            raise ValueError(f"sampler='dpmpp_2m' is deterministic and takes no eta: got {eta}")
+        is_count = isinstance(num_steps, numbers.Integral) and not isinstance(num_steps, bool)
+        if not is_count and spacing is not None:
+            raise ValueError(f"spacing={spacing!r} chooses the timesteps of a step count; num_steps is an explicit timestep sequence")
+        if is_count and (spacing or ("logsnr" if sampler == "dpmpp_2m" else "uniform")) == "logsnr":
+            taus = tuple(logsnr_timesteps(self._alpha_bar32(), num_steps))
+        else:
+            taus = tuple(resolve_timesteps(T, num_steps))
         pred = self.prediction_type
-        key = (taus, eta, pred)
+        key = (taus, eta, pred, sampler)
         if key not in self._spaced_cache:
-            with self.schedule:                                                      # float32 tables whatever the data dtype
-                ab = self.schedule["alpha_bar_t"].clone()
-            self._spaced_cache[key] = {"taus": taus, "eta": eta, "pred": pred, "rows": spaced_pred_coefficients(ab, taus, eta, pred), "T": T,
-                                       "dev": {}}
+            ab = self._alpha_bar32()
+            rows = dpmpp_2m_coefficients(ab, taus, pred) if sampler == "dpmpp_2m" else spaced_pred_coefficients(ab, taus, eta, pred)
+            self._spaced_cache[key] = {"taus": taus, "eta": eta, "pred": pred, "sampler": sampler, "rows": rows, "T": T, "dev": {}}
         return self._spaced_cache[key]
 
     def _spaced_device(self, spaced: dict, dev):
@@ -314,9 +374,12 @@ class DDPM(AbstractDiffusionPipeline):
             spaced["dev"][key] = (spaced["rows"].contiguous().to(dev), torch.tensor(spaced["taus"], dtype=torch.int32).to(dev))
         return spaced["dev"][key]
 
-    def _spaced_update(self, x_all, pred, z, rows, k_dev, scale, clip, kind) -> None:
-        """The update of one step of the spaced walk, by what the backbone predicts: the rows are of that kind (_spaced_host)."""
-        if kind == "epsilon":
+    def _spaced_update(self, x_all, pred, z, rows, k_dev, scale, clip, kind, hist=None) -> None:
+        """The update of one step of the spaced walk, by the sampler and by what the backbone predicts: the rows are of that kind
+        (_spaced_host).  ``hist`` is the multistep solver's x0 history and marks its walk; the DDIM walks carry None."""
+        if hist is not None:
+            ops.dpmpp_2m_step(x_all, pred, hist, rows, k_dev, PREDICTION_TYPES[kind], scale, clip)
+        elif kind == "epsilon":
             ops.p_sample_step_spaced(x_all, pred, z, rows, k_dev, scale, clip)
         else:
             ops.p_sample_step_spaced_pred(x_all, pred, z, rows, k_dev, PREDICTION_TYPES[kind], scale, clip)
@@ -327,7 +390,11 @@ class DDPM(AbstractDiffusionPipeline):
         x0 model) on row k, checkpoint, rho_spaced_advance.
         ``x_all`` is what the backbone reads and the update writes: ``x_t``, or under guidance the doubled batch whose first half
         ``x_t`` is (``cc`` then carries the null rows).  k and t live on the device, so one captured graph serves every step
-        (_reverse_process_spaced_graph)."""
+        (_reverse_process_spaced_graph).
+
+        With sampler "dpmpp_2m" the update is rho_dpmpp_2m_step on the rows of dpmpp_2m_coefficients: no z is drawn, and ``hist``, an
+        ordinary device tensor of x_t's shape, carries the x0 estimate from one step to the next.  It is not zeroed: row S-1 is
+        first order and does not read it."""
         taus, eta, kind = spaced["taus"], spaced["eta"], spaced["pred"]
         S = len(taus)
         dev = x_all.device
@@ -337,11 +404,12 @@ class DDPM(AbstractDiffusionPipeline):
         ckpt = spaced_checkpoints(spaced["T"], taus) if buf is not None else ()
         num_checkpoints = buf.size(1) if buf is not None else 0
         noisy = eta > 0.0
+        hist = torch.empty_like(x_t) if spaced.get("sampler", "ddim") == "dpmpp_2m" else None
         result = {"buffer": buf, "denoised": x_t}
         if (self.hip_graph_sampling and engine is not None and S > 2 and "noise" not in self.__dict__
                 and type(self).noise is DDPM.noise):
             if self._reverse_process_spaced_graph(x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt,
-                                                  kind):
+                                                  kind, hist):
                 self._check_backbone_errors()
                 return result
             k_dev.fill_(S - 1)
@@ -353,7 +421,7 @@ class DDPM(AbstractDiffusionPipeline):
                 pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
             else:
                 pred = self.backbone(x_t, torch.full((batch_size,), taus[k], device=dev, dtype=torch.long), cc)
-            self._spaced_update(x_all, pred.contiguous(), z, rows, k_dev, scale, clip, kind)
+            self._spaced_update(x_all, pred.contiguous(), z, rows, k_dev, scale, clip, kind, hist)
             if buf is not None and taus[k] in ckpt and t_idx < num_checkpoints:
                 buf[:, t_idx].copy_(x_t)
                 t_idx += 1
@@ -362,11 +430,12 @@ class DDPM(AbstractDiffusionPipeline):
         return result
 
     def _reverse_process_spaced_graph(self, x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt,
-                                      kind="epsilon") -> bool:
+                                      kind="epsilon", hist=None) -> bool:
         """_reverse_process_graph for the spaced walk: step S-1 runs eagerly (it builds the engine plan), one captured step is
         replayed S-1 times.  With eta > 0 the captured step draws z at every replay from the device-side offset; the draw of k = 0
         is ignored by the kernel (row 0 has sigma = 0) and not counted, so the offset ends where the eager loop leaves it.  With
-        eta = 0 no Philox kernel is in the graph.  Returns False (nothing modified) if the capture fails."""
+        eta = 0 no Philox kernel is in the graph.  ``hist`` (the dpmpp_2m walk; None otherwise) is read and written by the captured
+        step like x_all; the eager step S-1 fills it.  Returns False (nothing modified) if the capture fails."""
         dev = x_t.device
         S = len(taus)
         delta = (x_t.numel() + 3) // 4
@@ -379,7 +448,7 @@ class DDPM(AbstractDiffusionPipeline):
             if noisy:
                 ops.philox_normal(z, self.noise_seed, 0, offset_dev=off_dev)
             pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
-            self._spaced_update(x_all, pred, z, rows, k_dev, scale, clip, kind)
+            self._spaced_update(x_all, pred, z, rows, k_dev, scale, clip, kind, hist)
             ops.spaced_advance(k_dev, t_dev, taus_dev, off_dev, delta)
 
         t_idx = 0

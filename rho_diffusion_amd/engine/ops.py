@@ -122,6 +122,30 @@ def p_sample_step_spaced_pred(x: Tensor, pred: Tensor, z: Optional[Tensor], rows
     return x
 
 
+def dpmpp_2m_step(x: Tensor, pred: Tensor, hist: Tensor, rows: Tensor, k_dev: Tensor, pred_type: int, scale: Optional[float] = None,
+                  clip: bool = True) -> Tensor:
+    """One step of DPM-Solver++(2M) on the spaced walk (rho_dpmpp_2m_step): row ``*k_dev`` of ``rows`` [S, 8] as
+    dpmpp_2m_coefficients writes them, ``pred_type`` 0 (epsilon), 1 (v) or 2 (sample).  ``hist`` [B, ...] holds the x0 estimate of the
+    step before - one row also under guidance, read only by a second-order row - and receives this step's.  ``scale`` / ``clip`` as in
+    p_sample_step_spaced."""
+    _f32c(x, "x"), _f32c(pred, "pred"), _f32c(hist, "hist"), _f32c(rows, "rows")
+    if rows.dim() != 2 or rows.shape[1] != 8 or rows.shape[0] < 1:
+        raise RhoHipError(f"rows must be float32 [S, 8], got {tuple(rows.shape)}")
+    if pred_type not in (0, 1, 2):
+        raise RhoHipError(f"pred_type must be 0 (epsilon), 1 (v) or 2 (sample), got {pred_type}")
+    guided = scale is not None
+    n = x.numel() // 2 if guided else x.numel()
+    if n < 1 or x.numel() != (2 * n if guided else n) or pred.numel() != x.numel() or hist.numel() != n:
+        raise RhoHipError(f"x / pred hold {'two rows' if guided else 'one row'} of n elements and hist one: got {x.numel()}, "
+                          f"{pred.numel()}, {hist.numel()}")
+    if k_dev.dtype != torch.int32 or not k_dev.is_cuda or k_dev.numel() != 1:
+        raise RhoHipError("k_dev must be int32[1] on the GPU")
+    check(hip.lib().rho_dpmpp_2m_step(ptr(x), ptr(pred), ptr(hist), ptr(rows), ptr(k_dev), rows.shape[0], n, int(guided),
+                                      float(scale) if guided else 0.0, int(bool(clip)), int(pred_type), stream()),
+          "rho_dpmpp_2m_step")
+    return x
+
+
 def spaced_advance(k_dev: Tensor, t_dev: Tensor, taus: Tensor, offset_dev: Optional[Tensor], delta: int) -> None:
     """k <- k - 1, t <- taus[k] while k >= 0, offset += delta (rho_spaced_advance): the loop state of the spaced walk."""
     for name, t in (("k_dev", k_dev), ("t_dev", t_dev)):

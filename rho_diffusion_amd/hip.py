@@ -80,6 +80,8 @@ SIGNATURES = {
     "rho_spaced_advance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
     "rho_p_sample_step_spaced_pred": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int, c_float, c_int,
                                               c_int, c_void_p]),
+    "rho_dpmpp_2m_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int, c_float, c_int, c_int,
+                                  c_void_p]),
     "rho_philox_normal": (c_int, [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p]),
     "rho_mse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "rho_mse_ws": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
