@@ -1079,6 +1079,40 @@ int64_t rho_psnr_workspace_bytes(void);
 int rho_psnr(const float* pred, const float* target, int64_t n, float data_range, float* out, float* workspace, int64_t workspace_bytes,
              void* stream);
 
+/* ---- Structural similarity (csrc/ssim.hip): torchmetrics' StructuralSimilarityIndexMeasure, the package the reference's pipelines
+ * take their metrics from (abstract_diffusion.py:31,79), for float32 fields [batch, channels, *sizes] with ndim = 1, 2 or 3 spatial
+ * dimensions, over the windows that lie wholly inside the field (prod(size_d - k_d + 1) per channel; torchmetrics' reflection
+ * padding is cropped again before its reduction and never enters the value).  Per spatial dimension one float32 window on the device
+ * (k_d taps, odd, 1 <= k_d <= rho_ssim_max_window() = 15); the n-D window is their outer product.  With s = target[b, c, 0, .., 0]
+ * (after the clamp), a = p - s, b = t - s and W[.] the window sum:
+ *   mu_p = s + W[a], mu_t = s + W[b], s_pp = max(W[a a] - W[a]^2, 0), s_tt likewise, s_pt = W[a b] - W[a] W[b],
+ *   S = (2 mu_p mu_t + c1)(2 s_pt + c2) / ((mu_p^2 + mu_t^2 + c1)(s_pp + s_tt + c2)),  c1 = (k1 R)^2, c2 = (k2 R)^2.
+ * All window sums run in float32 in a fixed order (taps ascending, one fma chain per pass, passes along W, H, D; the shift keeps the
+ * second moments from cancelling); the sums of S run in float64: one partial per workgroup, folded in index order by a second launch.
+ * No atomics, no read-back: two runs give the same bits and a call can be captured in a graph. */
+int64_t rho_ssim_max_window(void);
+
+/* Bytes of `workspace` for rho_ssim (abstract_diffusion.py:31,79) at this shape (it also covers rho_ssim_range); -1 where rho_ssim would refuse the shape.
+ * sizes, window_sizes: host int64 [ndim]. */
+int64_t rho_ssim_workspace_bytes(int64_t batch, int64_t channels, int ndim, const int64_t* sizes, const int64_t* window_sizes);
+
+/* out_range[0] = max(max(pred) - min(pred), max(target) - min(target)) over all n values: torchmetrics' data_range = None
+ * (abstract_diffusion.py:31,79), one pass with per-block partials folded in block order.  workspace: 16 KiB (4096 floats). */
+int rho_ssim_range(const float* pred, const float* target, int64_t n, float* out_range, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+
+/* The index above (abstract_diffusion.py:31,79).  sizes, window_sizes: host int64 [ndim]; windows: host array of ndim device pointers.
+ * R = data_range_dev[0] (device float32, e.g. of rho_ssim_range) when data_range_dev is not NULL, else data_range (> 0).  clamp != 0:
+ * both inputs are clamped to [lo, hi] as they are loaded (hi > lo).  Writes per_sample [batch] (the mean of S over the channels and
+ * windows of a sample), out [2] = {mean, sum} of per_sample over the batch and - map not NULL - S itself, float32
+ * [batch, channels, *(size_d - k_d + 1)].  workspace: rho_ssim_workspace_bytes(), 8-byte aligned.
+ * RHO_E_SHAPE: a size below its window, a window above the cap or even; RHO_E_ARG: NULL or undersized arguments, ndim outside 1..3,
+ * no positive range.  Nothing is written when a code is returned. */
+int rho_ssim(const float* pred, const float* target, int64_t batch, int64_t channels, int ndim, const int64_t* sizes,
+             const float* const* windows, const int64_t* window_sizes, float data_range, const float* data_range_dev, int clamp, float lo,
+             float hi, float k1, float k2, float* per_sample, float* out, float* map, void* workspace, int64_t workspace_bytes,
+             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

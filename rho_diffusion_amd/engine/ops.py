@@ -1685,3 +1685,63 @@ def psnr(pred: Tensor, target: Tensor, data_range: Optional[float] = None) -> Te
     check(hip.lib().rho_psnr(ptr(pred), ptr(target), pred.numel(), 0.0 if data_range is None else float(data_range), ptr(buf),
                              buf.data_ptr() + 16, ws_bytes, stream()), "rho_psnr")
     return buf[:4]
+
+
+# ----------------------------------------------------------------------------- structural similarity (csrc/ssim.hip)
+SSIM_MAX_WINDOW = 15             # == rho_ssim_max_window()
+
+
+def ssim_range(pred: Tensor, target: Tensor, workspace: Optional[Tensor] = None) -> Tensor:
+    """float32 [1] on the device: max(max(pred) - min(pred), max(target) - min(target)) (rho_ssim_range)."""
+    _f32c(pred, "pred")
+    _same(pred, ("target", target))
+    ws = torch.empty(4096, dtype=torch.float32, device=pred.device) if workspace is None else workspace
+    out = torch.empty(1, dtype=torch.float32, device=pred.device)
+    check(hip.lib().rho_ssim_range(ptr(pred), ptr(target), pred.numel(), ptr(out), ptr(ws), ws.numel() * ws.element_size(), stream()),
+          "rho_ssim_range")
+    return out
+
+
+def ssim(pred: Tensor, target: Tensor, windows: Sequence[Tensor], data_range=None, clamp: Optional[Tuple[float, float]] = None,
+         k1: float = 0.01, k2: float = 0.03, return_map: bool = False, per_sample: Optional[Tensor] = None, out: Optional[Tensor] = None,
+         map: Optional[Tensor] = None):
+    """SSIM of two float32 fields [B, C, *spatial] over the windows wholly inside the field (rho_ssim).  ``windows``: one float32
+    device tensor per spatial dimension.  ``data_range``: None (measured on the device by rho_ssim_range), a float, or a float32
+    device tensor [1]; ``clamp`` (lo, hi): both inputs are clamped as they are loaded.  Returns (per_sample [B], out [2] = {mean,
+    sum} over the batch, map or None); the map is float32 [B, C, *(size_d - k_d + 1)].  ``per_sample``, ``out``, ``map``: buffers to
+    write into.  Shapes and windows are judged by the library: a refusal raises with its code and writes nothing.  Nothing is read
+    back and nothing synchronises."""
+    _f32c(pred, "pred")
+    _same(pred, ("target", target))
+    nd = pred.dim() - 2
+    if nd < 1 or len(windows) != nd:
+        raise RhoHipError(f"pred must be [B, C, *spatial] with one window per spatial dimension, got {tuple(pred.shape)} and "
+                          f"{len(windows)} windows")
+    for i, w in enumerate(windows):
+        _f32c(w, f"windows[{i}]")
+    B, Cn = int(pred.shape[0]), int(pred.shape[1])
+    sizes = (C.c_int64 * nd)(*[int(v) for v in pred.shape[2:]])
+    ks = (C.c_int64 * nd)(*[int(w.numel()) for w in windows])
+    wptr = (C.c_void_p * nd)(*[w.data_ptr() for w in windows])
+    dev = pred.device
+    ws_bytes = int(hip.lib().rho_ssim_workspace_bytes(B, Cn, nd, sizes, ks))
+    ws = torch.empty(max(ws_bytes, 16384) // 8, dtype=torch.float64, device=dev)
+    mshape = (B, Cn) + tuple(max(int(s) - int(k) + 1, 1) for s, k in zip(sizes, ks))
+    per_sample = torch.empty(B, dtype=torch.float32, device=dev) if per_sample is None else _f32c(per_sample, "per_sample")
+    out = torch.empty(2, dtype=torch.float32, device=dev) if out is None else _f32c(out, "out")
+    if map is None and return_map:
+        map = torch.empty(mshape, dtype=torch.float32, device=dev)
+    if per_sample.numel() < B or out.numel() < 2 or (map is not None and _f32c(map, "map").numel() < math.prod(mshape)):
+        raise RhoHipError("per_sample [B], out [2] or map [B, C, *(size - k + 1)] is too small")
+    range_dev, range_val = None, 0.0
+    if data_range is None:
+        range_dev = ssim_range(pred, target, ws)
+    elif isinstance(data_range, Tensor):
+        range_dev = _f32c(data_range, "data_range")
+    else:
+        range_val = float(data_range)
+    lo, hi = (0.0, 0.0) if clamp is None else (float(clamp[0]), float(clamp[1]))
+    check(hip.lib().rho_ssim(ptr(pred), ptr(target), B, Cn, nd, sizes, wptr, ks, range_val, ptr(range_dev), 0 if clamp is None else 1,
+                             lo, hi, float(k1), float(k2), ptr(per_sample), ptr(out), ptr(map), ptr(ws), ws.numel() * 8, stream()),
+          "rho_ssim")
+    return per_sample, out, map

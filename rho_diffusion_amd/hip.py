@@ -240,6 +240,12 @@ SIGNATURES = {
     "rho_rows_combine": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64] + [c_void_p] * 7),
     "rho_psnr_workspace_bytes": (c_int64, []),
     "rho_psnr": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    # ---- structural similarity (metrics/ssim.py, csrc/ssim.hip)
+    "rho_ssim_max_window": (c_int64, []),
+    "rho_ssim_workspace_bytes": (c_int64, [c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "rho_ssim_range": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rho_ssim": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_float,
+                         c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 
