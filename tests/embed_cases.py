@@ -23,13 +23,16 @@ import numpy as np
 import torch
 
 from detdata import det_normal
-from exact_util import int_tensor
+from exact_util import f32_ulp as _f32_ulp, int_tensor
 
 U = 2.0 ** -24                 # unit roundoff of fp32
 ACTS = (0, 1, 2, 3, 4, 5, 6)   # identity, SiLU, ReLU, GELU (erf), Tanh, Sigmoid, ELU(1)
 INT_ACTS = (0, 2)
 ACT_NAMES = ("id", "silu", "relu", "gelu", "tanh", "sigmoid", "elu")
 LIP = 1.13                     # sup |act'| over the seven codes (GELU': 1.129 at u = sqrt(2); SiLU': 1.0998)
+# code -> (forward, derivative) allowance of the device libm expressions (act_other_f / dact_other_f and the embedding path's SiLU) in
+# fp32 ulps of the term magnitude; measured and derived in the docstring of test_gpu_exact_embedding.py, shared by every exact suite
+ACT_ULPS = {1: (3, 3), 3: (3, 3), 4: (2, 2), 5: (4, 4), 6: (2, 2)}
 _SQRT1_2 = 0.7071067811865476
 _INV_SQRT_2PI = 0.3989422804014327
 
@@ -105,6 +108,36 @@ def dact_mag64(u: torch.Tensor, code: int) -> torch.Tensor:
         s = _sig(u)
         return s * (1.0 + s)
     return dact64(u, code).abs()
+
+
+# ----------------------------------------------------------------------------- the kernels that use common.h's silu_f / act_other_f
+# (rho_bias_act, the GroupNorm passes, the conv loaders).  Code 1 is silu_f / dsilu_f of common.h: x * rcp(1 + exp2(t)), t = fl(c * x),
+# c = fl32(-log2 e).  With u = 2^-24, w = 1 - sigmoid(x):
+#   t: c is 0.15 u from -log2 e and the product rounds once: |dt| <= 1.15 u |t|, which is ln2 * 1.15 u |t| < 0.8 u |t| relative in 2^t;
+#   v_exp_f32: 1 ulp <= 2 u relative; so e = exp2(t) carries (2 + 0.8 |t|) u, and enters 1 + e with weight e / (1 + e) = w;
+#   the addition rounds (1 u), v_rcp_f32: 1 ulp <= 2 u: s = rcp(1 + e) carries rho u, rho = w (2 + 0.8 |t|) + 3;
+#   silu: the product with x rounds once more: (rho + 1) u |silu(x)|, i.e. SILU_F_ULPS(x) = w (2 + 0.8 |t|) + 4 ulps;
+#   dsilu = s (1 + x (1 - s)): a = 1 - s: s's error + 1 rounding; x a: 1 rounding; 1 + x a: 1 rounding; the product with s: its error
+#   on |c| <= 1 + |x| a and 1 rounding: in all rho u s (1 + |x| a + |x| s) + u s (4 |x| a + 2) <= (rho + 4) u Mag with
+#   Mag = s (1 + |x| (1 + s)) = dact_mag64: DSILU_F_ULPS(x) = w (2 + 0.8 |t|) + 7 ulps of Mag.
+# The bound grows with |x| on the negative side only (w -> 1); at x = -6 it is 12.9 / 15.9 ulps, at x = +6 it is 4.0 / 7.0.
+# Codes 2 - 6 are act_other_f / dact_other_f, the libm expressions of the embedding path: ACT_ULPS (code 2: exact).
+_LOG2E = 1.4426950408889634
+
+
+def silu_f_ulps(u64: torch.Tensor, derivative: bool) -> torch.Tensor:
+    w = 1.0 / (1.0 + torch.exp(u64))
+    return w * (2.0 + 0.8 * _LOG2E * u64.abs()) + (7.0 if derivative else 4.0)
+
+
+def hw_act_bound(u64: torch.Tensor, code: int, derivative: bool):
+    """(reference, absolute fp32 bound, term magnitude) of act(u) or act'(u), per element."""
+    want = (dact64 if derivative else act64)(u64, code)
+    mag = (dact_mag64 if derivative else act_mag64)(u64, code)
+    if code == 1:
+        return want, silu_f_ulps(u64, derivative) * _f32_ulp(mag), mag
+    ulps = 0.0 if code in INT_ACTS else float(ACT_ULPS[code][int(derivative)])
+    return want, ulps * _f32_ulp(mag), mag
 
 
 def _ulps(act_ulps, code: int, which: int) -> float:

@@ -131,10 +131,13 @@ def fwd_out_spatial(c):
     return (D, ho, wo)
 
 
-def fwd_reference(c, o, dtype=torch.float64):
-    """(activated input, full output [N, cout, Do, Ho, Wo]) evaluated in `dtype` on the CPU."""
+def fwd_reference(c, o, dtype=torch.float64, act_fn=None):
+    """(activated input, full output [N, cout, Do, Ho, Wo]) evaluated in `dtype` on the CPU.  act_fn: applied to the affine prologue's
+    result (the loader's SiLU, see silu_operand)."""
     t = {k: (v.to(dtype) if torch.is_tensor(v) else v) for k, v in o.items()}
     act = affine(t["x"], t["pa"], t["pb"]) if c["pre"] else t["x"]
+    if act_fn is not None:
+        act = act_fn(act)
     y = conv5(act, t["w"], t["b"], c["stride"], c["up"])
     if c["skip"]:
         y = y + conv5(t["sx"], t["sw"], t["sb"])
@@ -145,6 +148,75 @@ def fwd_reference(c, o, dtype=torch.float64):
     if c["res2"]:
         y = torch.cat([y[:, :c["split"]], y[:, c["split"]:] + t["res2"]], 1)
     return act, y
+
+
+# ----------------------------------------------------------------------------- SiLU in the conv loaders (pre_silu = 1)
+# The prologue cases again with the loader's SiLU switched on.  (a, b) from SILU_AB and x in [-2, 2] keep u = a x + b an integer in
+# [-2, 6] (the fma is exact; u = 6 is where a sigmoid rounded to bf16 before the product changes the operand).  silu64(u) lies
+# hundreds of fp32 ulps from every bf16 rounding tie there (test_exact_cases_host.py
+# re-proves the margin against four times the derived silu_f bound), while the loader's expression errs by a few ulps, so the bf16
+# operand handed to the MFMA is exactly s = bf16(silu64(u)), on a grid of 2^-10 (the bf16 spacing at silu(-2) = -0.238).  The host
+# twin proves sum |w s| (+ bias, residual, additive row, folded skip) stays below 2^24 steps of that grid: every fp32 partial sum is
+# exact in any order and the stored output is the reference after ONE rounding to the storage type.  The float32 kernels hand the
+# MFMA silu_f(u) itself, known to the silu_f bound: their output is bounded per element (silu_fwd_bound).
+SILU_AB = ((1, 0), (1, 1), (-1, 0), (-1, 1), (2, 2))          # (a, b) per (sample, channel); (2, 2) reaches u = 4 and 6
+SILU_U = (-2, -1, 0, 1, 2, 3, 4, 6)
+SILU_GRID = 2.0 ** -10
+SILU_FWD_CASES = [c for c in FWD_CASES if c["pre"] and not c["ksplit"]]
+SILU_FORMS = ("exact", "bf16_of_expf", "rounded_twice")
+
+
+def silu_operand(u, dtype, form="exact"):
+    """float64: what the loader hands the MFMA for an integer u: bf16(silu64(u)) in the bf16 kernels, silu64(u) (to the silu_f bound)
+    in the float32 ones.  The other forms are what a wrong loader would compute - SiLU through a bf16-rounded exponential, or
+    x * sigmoid with the sigmoid rounded to bf16 first (rounded twice) - for the host twin's mutation test."""
+    from exact_util import bf16_round
+    u = u.double()
+    if form == "exact":
+        s = u / (1.0 + torch.exp(-u))
+    elif form == "bf16_of_expf":
+        s = u / (1.0 + bf16_round(torch.exp(-u).float().double()))
+    elif form == "rounded_twice":
+        s = u * bf16_round(1.0 / (1.0 + torch.exp(-u)))
+    else:
+        raise ValueError(form)
+    return bf16_round(s) if dtype == BF16 else s
+
+
+def silu_fwd_operands(c):
+    o = fwd_operands(c)
+    N, cin = o["N"], c["c1"] + c["c2"]
+    idx = int_choice((N, cin), c["name"] + "sab", range(len(SILU_AB))).long()
+    ab = torch.tensor(SILU_AB, dtype=torch.float32)
+    o["pa"], o["pb"] = ab[idx, 0].contiguous(), ab[idx, 1].contiguous()
+    return o
+
+
+def silu_fwd_reference(c, o, dtype, form="exact"):
+    """(u, y): the integer prologue values and the fp64 output of the case with SiLU in the loader."""
+    u = affine(o["x"].double(), o["pa"].double(), o["pb"].double())
+    _, y = fwd_reference(c, o, torch.float64, lambda a: silu_operand(a, dtype, form))
+    return u, y
+
+
+def silu_fwd_magnitude(c, o, dtype):
+    """sum |w s| + |bias| + |skip terms| + |add| + |res| per output element (fp64): bounds every partial sum of the launch."""
+    oa = {k: (v.abs() if torch.is_tensor(v) and k not in ("pa", "pb", "x") else v) for k, v in o.items()}
+    _, m = fwd_reference(c, oa, torch.float64, lambda a: silu_operand(a, dtype).abs())
+    return m
+
+
+def silu_fwd_bound(c, o):
+    """float32 kernels: |dy| <= sum |w| * (silu_f bound at u) + n 2^-24 (sum |w s| + ...), n = the number of terms of an output."""
+    import embed_cases as EC
+    u = affine(o["x"].double(), o["pa"].double(), o["pb"].double())
+    _, b, _ = EC.hw_act_bound(u, 1, False)
+    z = {k: (torch.zeros_like(v) if k in ("b", "sx", "sb", "res", "res2", "add") else v.abs() if k in ("w", "sw") else v)
+         for k, v in o.items() if torch.is_tensor(v)}
+    z["N"] = o["N"]
+    _, first = fwd_reference(c, z, torch.float64, lambda a: b)
+    n = (c["c1"] + c["c2"]) * math.prod(c["kernel"]) + (sum(c["skip"]) if c["skip"] else 0) + 4
+    return first + n * 2.0 ** -24 * silu_fwd_magnitude(c, o, F32)
 
 
 # the tile of a k_conv launch (conv_common.h choose_tile: fewest tiles, then the smallest halo, then the widest W): the fused
@@ -281,10 +353,14 @@ def bwd_operands(c):
     return o
 
 
-def bwd_reference(c, o, dtype=torch.float64):
-    """dict(act, dx = gradient w.r.t. the activated input, dw, db) by autograd in `dtype` on the CPU."""
+def bwd_reference(c, o, dtype=torch.float64, act_fn=None):
+    """dict(act, dx = gradient w.r.t. the activated input, dw, db) by autograd in `dtype` on the CPU.  act_fn: applied to the affine
+    prologue's result (the loader's SiLU, see silu_operand)."""
     t = {k: (v.to(dtype) if torch.is_tensor(v) else v) for k, v in o.items()}
-    act = (affine(t["x"], t["pa"], t["pb"]) if c["pre"] else t["x"]).clone().requires_grad_(True)
+    act = affine(t["x"], t["pa"], t["pb"]) if c["pre"] else t["x"]
+    if act_fn is not None:
+        act = act_fn(act)
+    act = act.clone().requires_grad_(True)
     w = t["w"].clone().requires_grad_(True)
     b = torch.zeros(c["cout"], dtype=dtype, requires_grad=True)
     conv5(act, w, b, c["stride"], c["up"]).backward(t["dy"])
@@ -370,6 +446,29 @@ GN_BY_NAME = {c["name"]: c for c in GN_CASES}
 def gn_nblk(S):
     """rho_gn_nblk: 256-position blocks, at most 256 of them."""
     return max(1, min(256, -(-S // 256)))
+
+
+def gn_reduce_stream(S, C, pos):
+    """Which accumulation of k_gn_bwd_reduce takes position `pos`: lane pl = q % ppi of block pos / per walks q = pl, pl + ppi, ...
+    (q relative to the block) in pairs - "gq" the first, "gr" the second of a pair - and a last unpaired one in the "tail" loop."""
+    ppi = 256 // (C // 8)
+    per = -(-S // gn_nblk(S))
+    blk = pos // per
+    length = min(S, (blk + 1) * per) - blk * per
+    q = pos - blk * per
+    pl, k = q % ppi, q // ppi
+    n = -(-(length - pl) // ppi)                       # positions of this lane
+    if n % 2 == 1 and k == n - 1:
+        return "tail"
+    return "gq" if k % 2 == 0 else "gr"
+
+
+def gn_reduce_stream_positions(S, C):
+    """{stream: first position that falls into it} for the streams a shape reaches."""
+    out = {}
+    for pos in range(S):
+        out.setdefault(gn_reduce_stream(S, C, pos), pos)
+    return out
 
 
 def gn_int(shape, tag, lo, hi):
@@ -563,6 +662,32 @@ def gnb_operands(c):
     return o
 
 
+def gnb_silu_operands(c):
+    """gnb_operands with integer folded-affine rows a in {-2, -1, 1, 2}, b in -2 .. 2: u = a x0 + b is an integer in [-10, 10]."""
+    o = gnb_operands(c)
+    C = c["c1"] + c["c2"]
+    o["a"] = int_choice((c["N"], C), "gnbsa_" + c["name"], (-2.0, -1.0, 1.0, 2.0))
+    o["b"] = gn_int((c["N"], C), "gnbsb_" + c["name"], -2, 2)
+    return o
+
+
+def gnb_silu_reference(c, o, ids):
+    """gnb_silu = 1 on a data-gradient launch: the stored dX stays the integer conv result z; the per-tile rows hold sum dz and
+    sum dz x0 with dz = z * dsilu(u).  Returns (z, rows [N, tiles, 2, C], bound on the rows), fp64.  Bound: each dz = fl(z * dsilu_f(u))
+    is within |z| (dsilu_f bound at u) + 2^-24 |z| Mag(u) (embed_cases.hw_act_bound; the product rounds once); a row adds the n
+    terms of its tile in some order, every addition rounding at most once against a partial sum bounded by the magnitude sum:
+    n 2^-24 sum |z| Mag (times |x0| in the second row, whose fma adds dz * x0 unrounded)."""
+    import embed_cases as EC
+    z = bwd_reference(c, o)["dx"]
+    u = affine(o["x0"].double(), o["a"].double(), o["b"].double())
+    d, bound, mag = EC.hw_act_bound(u, 1, True)
+    n = int(torch.bincount(ids.reshape(-1)).max())
+    term = z.abs() * bound + 2.0 ** -24 * z.abs() * mag
+    rows = stats_reference(z * d, ids, o["x0"])
+    rb = stats_reference(term, ids, o["x0"].abs()) + n * 2.0 ** -24 * stats_reference(z.abs() * mag, ids, o["x0"].abs())
+    return z, rows, rb
+
+
 def to_nsc(t):
     """[N, C, D, H, W] -> [N, S, C]."""
     return t.reshape(t.shape[0], t.shape[1], -1).permute(0, 2, 1)
@@ -591,3 +716,56 @@ def gna_reference(o, dtype=torch.float64):
     conv = torch.einsum("ndhwk,kc->ndhwc", o["dy"].to(dtype), o["w"].to(dtype).reshape(-1, C))
     term = gn_bwd_apply_reference(o["g"].reshape(N, -1, C), o["x0"].reshape(N, -1, C), o["cA"], o["cP"], o["cQ"], dtype)
     return conv + term.reshape(N, D, H, W, C)
+
+
+def gna_silu_operands(case):
+    """gna_operands with gnb_silu = 1 in mind: integer folded-affine rows a in {-2, -1, 1, 2}, b in -2 .. 2 (u = a x0 + b an integer in
+    [-10, 10]), cA = 1, cP = cQ = 0 and g in {0, +-1/4, +-1/2}, so that the stored output is conv + g * dsilu(u) element for element."""
+    name, _, cy, c1, c2, _, (N, D, H, W) = case
+    C = c1 + c2
+    o = gna_operands(case)
+    o["a"] = int_choice((N, C), name + "sa", (-2.0, -1.0, 1.0, 2.0))
+    o["b"] = gn_int((N, C), name + "sb", -2, 2)
+    o["cA"], o["cP"], o["cQ"] = torch.ones(N, C), torch.zeros(N, 32), torch.zeros(N, 32)
+    o["g"] = o["g"] * 0.25            # |g dsilu(u)| < 0.56: the term never cancels a nonzero integer conv result down to near zero
+    return o
+
+
+def gna_silu_reference(o):
+    """(u, conv, want, float32 bound) channels-last, fp64.  The GNA epilogue computes gq = g * dsilu_f(u) (g a power of two or 0: an exact
+    scaling, so gq carries |g| times the derived dsilu_f bound of embed_cases.hw_act_bound), fma(1, gq, fma(0, x0, 0)) = gq, and adds
+    it to the exact integer accumulator: one rounding of the sum, 2^-24 (|conv| + |g| Mag(u))."""
+    import embed_cases as EC
+    N, D, H, W, C = o["g"].shape
+    conv = torch.einsum("ndhwk,kc->ndhwc", o["dy"].double(), o["w"].double().reshape(-1, C))
+    u = o["a"].double().reshape(N, 1, 1, 1, C) * o["x0"].double() + o["b"].double().reshape(N, 1, 1, 1, C)
+    d, bound, mag = EC.hw_act_bound(u, 1, True)
+    g = o["g"].double()
+    return u, conv, conv + g * d, g.abs() * bound + 2.0 ** -24 * (conv.abs() + g.abs() * mag)
+
+
+# ----------------------------------------------------------------------------- k_wgrad with the prologue and pre_silu = 1
+# The prologue cases of BWD_CASES with the (a, b) rows of SILU_AB: dW = sum dY s with dY in +-1 and s = bf16(silu64(u)) is exact on
+# the 2^-10 grid in the bf16 kernels (bit-equal after rho_wgrad_finalize); the float32 kernels are bounded per element by
+# sum |dY| (silu_f bound at u) + n 2^-24 sum |dY s|, n = the positions an element sums over.
+SILU_BWD_CASES = [c for c in BWD_CASES if c["pre"]]
+
+
+def silu_bwd_operands(c):
+    o = bwd_operands(c)
+    N, cin = o["N"], c["c1"] + c["c2"]
+    idx = int_choice((N, cin), "b_" + c["name"] + "sab", range(len(SILU_AB))).long()
+    ab = torch.tensor(SILU_AB, dtype=torch.float32)
+    o["pa"], o["pb"] = ab[idx, 0].contiguous(), ab[idx, 1].contiguous()
+    return o
+
+
+def silu_wgrad_reference(c, o, dtype, form="exact"):
+    """(dw, magnitude sum |dY s|, float32 bound) in fp64."""
+    import embed_cases as EC
+    dw = bwd_reference(c, o, torch.float64, lambda a: silu_operand(a, dtype, form))["dw"]
+    oa = dict(o, dy=o["dy"].abs())
+    mag = bwd_reference(c, oa, torch.float64, lambda a: silu_operand(a, dtype).abs())["dw"]
+    first = bwd_reference(c, oa, torch.float64, lambda a: EC.hw_act_bound(a, 1, False)[1])["dw"]
+    n = o["N"] * math.prod(fwd_out_spatial(c))
+    return dw, mag, first + n * 2.0 ** -24 * mag

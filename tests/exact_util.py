@@ -99,6 +99,69 @@ def assert_within_abs(got: torch.Tensor, want64: torch.Tensor, bound: torch.Tens
     raise AssertionError("\n".join(lines + _axis_lines(idx, got.shape)))
 
 
+# The tie rule for a bf16 result.  A kernel computes the value in fp32 within a derived bound and rounds it to bf16 once.  If the
+# fp64 reference r is farther than a margin from every bf16 rounding tie (the midpoint of two neighbouring bf16 numbers), every fp32
+# value inside the bound rounds to the same bf16 number, and the kernel must store bf16(r) exactly.  Closer than the margin, either
+# neighbour passes.  The margin is four times the derived fp32 bound of the value.  The share of elements allowed "either neighbour"
+# is a property of the inputs: the host twins assert it stays at or below TIE_SHARE_MAX per tensor.
+TIE_MARGIN_FACTOR = 4
+TIE_SHARE_MAX = 0.01
+
+
+def tie_margin(ulps, mag64: torch.Tensor) -> torch.Tensor:
+    """TIE_MARGIN_FACTOR times the fp32 bound `ulps` * ulp32(mag) of a value whose terms have the magnitude sum `mag`; 0 where
+    mag = 0 (every term is an exact zero)."""
+    m = mag64.detach().cpu().double()
+    return torch.where(m == 0, torch.zeros_like(m), TIE_MARGIN_FACTOR * ulps * f32_ulp(m))
+
+
+def bf16_ulp(v: torch.Tensor) -> torch.Tensor:
+    """float64: the spacing of bf16 numbers at |v| (8 significant bits; normal range)."""
+    return f32_ulp(v) * 65536.0
+
+
+def bf16_store_bound(ref64: torch.Tensor, f32_bound: torch.Tensor) -> torch.Tensor:
+    """|bf16(v) - r| for an fp32 value v with |v - r| <= f32_bound rounded once to bf16: the fp32 bound plus half a bf16 ulp at the
+    largest magnitude v can have."""
+    return f32_bound + 0.5 * bf16_ulp(ref64.double().abs() + f32_bound)
+
+
+def bf16_round(v64: torch.Tensor) -> torch.Tensor:
+    """float64 -> the nearest bf16 number (ties to even), in one rounding (through fp32 it would be two).  Normal range only."""
+    v = v64.double()
+    a = v.abs()
+    _, e = torch.frexp(a)
+    e = torch.where(a == 0, torch.full_like(e, -125), e)
+    ulp = torch.ldexp(torch.ones_like(a), e - 8)
+    return torch.sign(v) * torch.round(a / ulp) * ulp          # torch.round: halves to even
+
+
+def tie_share(ref64: torch.Tensor, margin: torch.Tensor) -> float:
+    """Fraction of elements whose reference is within `margin` (absolute, per element or a number) of a bf16 rounding tie, i.e. for
+    which bf16(r - margin) and bf16(r + margin) differ."""
+    r = ref64.detach().cpu().double()
+    m = margin.detach().cpu().double() if torch.is_tensor(margin) else float(margin)
+    return float((bf16_round(r - m) != bf16_round(r + m)).double().mean()) if r.numel() else 0.0
+
+
+def assert_bf16_tie_rule(got: torch.Tensor, ref64: torch.Tensor, margin: torch.Tensor, what: str) -> float:
+    """The tie rule above for EVERY element of a bf16 tensor: bf16(r - margin) <= got <= bf16(r + margin).  Away from a tie both ends
+    are bf16(r) and the element must equal it; within the margin of a tie they are its two neighbours (more than two bf16 numbers
+    only where the value cancels so far that the margin exceeds a bf16 ulp).  Returns the share of elements that had a choice."""
+    got, r = got.detach().cpu().double(), ref64.detach().cpu().double()
+    assert tuple(got.shape) == tuple(r.shape), f"{what}: shape {tuple(got.shape)} vs {tuple(r.shape)}"
+    m = (margin.detach().cpu().double() if torch.is_tensor(margin) else torch.tensor(float(margin), dtype=torch.float64)).expand_as(r)
+    lo, hi = bf16_round(r - m), bf16_round(r + m)
+    ok = (got >= lo) & (got <= hi)
+    if bool(ok.all()):
+        return float((lo != hi).double().mean()) if r.numel() else 0.0
+    idx = (~ok).nonzero()
+    first = tuple(int(i) for i in idx[0])
+    lines = [f"{what}: {idx.shape[0]} of {got.numel()} bf16 elements break the tie rule; first at {first}: got {got[first].item()!r}, "
+             f"reference {r[first].item()!r}, allowed [{lo[first].item()!r}, {hi[first].item()!r}]"]
+    raise AssertionError("\n".join(lines + _axis_lines(idx, got.shape)))
+
+
 def guarded(shape, dtype, device="cuda"):
     """(flat, view): a NaN-filled tensor of `shape` inside a larger allocation whose margins hold 1.5."""
     n = math.prod(shape)

@@ -312,3 +312,133 @@ def test_gna_case_reference_is_exactly_representable(case):
     assert_bit_equal(X.gna_reference(o, torch.float32), y, "fp32 vs fp64")
     check_bf16_exact(y, "conv + cA g + cQ x0 + cP")
     assert case[3] % 32 == 0 and case[4] % 32 == 0
+
+
+# ----------------------------------------------------------------------------- the streams of k_gn_bwd_reduce
+def test_reduce_stream_twin_reaches_every_accumulation():
+    """The position -> accumulation map the sparse test relies on (exact_cases.gn_reduce_stream), by hand for the three shapes:
+    nblk2_tails: ppi = 32, blocks of 129 and 128 positions: lane 0 of block 0 has 5 positions, the fifth (128) is unpaired;
+    cpg3_straddle: S = 7 < ppi = 21, every lane has one position; c2048: ppi = 1, nine positions: four pairs and the ninth alone."""
+    assert X.gn_reduce_stream_positions(257, 64) == {"gq": 0, "gr": 32, "tail": 128}
+    assert X.gn_reduce_stream_positions(7, 96) == {"tail": 0}
+    assert X.gn_reduce_stream_positions(9, 2048) == {"gq": 0, "gr": 1, "tail": 8}
+    assert X.gn_reduce_stream(257, 64, 129 + 96) == "gr" and X.gn_reduce_stream(257, 64, 129 + 64) == "gq"      # second block: four per lane
+
+
+# ----------------------------------------------------------------------------- SiLU in the conv loaders
+import embed_cases as EC  # noqa: E402
+from exact_util import TIE_MARGIN_FACTOR, bf16_round, tie_share  # noqa: E402
+from exact_cases import BF16, F32  # noqa: E402
+
+_silu_ids = lambda c: c["name"]  # noqa: E731
+
+
+def test_silu_operand_is_uniquely_determined_on_the_integer_set():
+    """For every u the SiLU cases use, silu64(u) is farther from the nearest bf16 rounding tie than TIE_MARGIN_FACTOR times the
+    derived silu_f bound (embed_cases.silu_f_ulps: at most 7.6 ulps on [-2, 6]): every fp32 value inside the bound rounds to
+    bf16(silu64(u)), so the share of loader operands with a choice is 0: the nearest tie is at least 742 fp32 ulps away."""
+    u = torch.tensor(X.SILU_U, dtype=torch.float64)
+    s = u / (1.0 + torch.exp(-u))
+    want, bound, mag = EC.hw_act_bound(u, 1, False)
+    assert float((want - s).abs().max()) < 1e-15
+    assert tie_share(s[u != 0], TIE_MARGIN_FACTOR * bound[u != 0]) == 0.0            # (u = 0: x * rcp(2) is an exact zero)
+    nz = u != 0
+    ulp16 = f32_ulp(s[nz]) * 65536
+    lo = torch.floor(s[nz].abs() / ulp16) * ulp16
+    dist = ((s[nz].abs() - lo - 0.5 * ulp16).abs() / f32_ulp(s[nz]))
+    assert float(dist.min()) >= 742, dist.tolist()
+    assert float((TIE_MARGIN_FACTOR * EC.silu_f_ulps(u, False)).max()) < 40 < float(dist.min())
+    check_f32_grid(bf16_round(s), X.SILU_GRID, "bf16(silu64(u))")
+
+
+@pytest.mark.parametrize("c", X.SILU_FWD_CASES, ids=_silu_ids)
+def test_silu_forward_cases_are_exact_after_one_rounding(c):
+    o = X.silu_fwd_operands(c)
+    u = X.affine(o["x"].double(), o["pa"].double(), o["pb"].double())
+    assert set(u.unique().tolist()) <= set(float(v) for v in X.SILU_U), "u = a x + b must stay on the proven integer set"
+    assert set(o["pa"].unique().tolist()) == {-1.0, 1.0, 2.0}, "a differs per (sample, channel), so the coefficient rows matter"
+    assert torch.equal(X.affine(o["x"], o["pa"], o["pb"]).double(), u)
+    if BF16 in c["dtypes"]:
+        _, y = X.silu_fwd_reference(c, o, BF16)
+        check_f32_grid(X.silu_fwd_magnitude(c, o, BF16), X.SILU_GRID, "sum |w s| + |bias| + |res| + |add|")
+        check_f32_grid(y, X.SILU_GRID, "y")
+        # the mutated loaders hand the MFMA another operand for some u of this case, and the output moves
+        for form in X.SILU_FORMS[1:]:
+            uu = u.unique()
+            assert not torch.equal(X.silu_operand(uu, BF16, form), X.silu_operand(uu, BF16)), f"{c['name']}: {form} gives the same operands"
+            _, ym = X.silu_fwd_reference(c, o, BF16, form)
+            assert not torch.equal(bf16_round(ym), bf16_round(y)), f"{c['name']}: a loader computing SiLU as {form} would pass"
+    if F32 in c["dtypes"]:
+        b = X.silu_fwd_bound(c, o)
+        _, y = X.silu_fwd_reference(c, o, F32)
+        assert float((b / (X.silu_fwd_magnitude(c, o, F32) + 1e-30)).max()) < 1e-3, "the float32 bound must stay a per-element one"
+
+
+def test_silu_float32_bound_notices_a_wrong_silu():
+    """The float32 bound carries n 2^-24 sum |w s| for the accumulation, which at K = 96 * 27 terms is wider than the damage of a
+    bf16-rounded exponential; the short-K cases (1x1x1, 1-D) are the ones that must notice, and are named."""
+    for form in X.SILU_FORMS[1:]:
+        bad = []
+        for c in X.SILU_FWD_CASES:
+            if F32 in c["dtypes"]:
+                o = X.silu_fwd_operands(c)
+                _, y = X.silu_fwd_reference(c, o, F32)
+                _, ym = X.silu_fwd_reference(c, o, F32, form)
+                if bool(((ym - y).abs() > X.silu_fwd_bound(c, o)).any()):
+                    bad.append(c["name"])
+        assert {"3d_1x1", "1d_1x1", "1d_basic"} <= set(bad), f"float32 SiLU as {form}: noticed by {bad}"
+
+
+@pytest.mark.parametrize("c", X.SILU_BWD_CASES, ids=_silu_ids)
+def test_silu_wgrad_cases_are_exact_on_the_grid(c):
+    o = X.silu_bwd_operands(c)
+    u = X.affine(o["x"].double(), o["pa"].double(), o["pb"].double())
+    assert set(u.unique().tolist()) <= set(float(v) for v in X.SILU_U)
+    assert float(o["dy"].abs().max()) == 1.0
+    for dt in c["dtypes"]:
+        dw, mag, bound = X.silu_wgrad_reference(c, o, dt)
+        for form in X.SILU_FORMS[1:]:
+            dwm, _, _ = X.silu_wgrad_reference(c, o, dt, form)
+            if dt == BF16:
+                assert not torch.equal(dwm, dw), f"{c['name']}: a wgrad loader computing SiLU as {form} would pass"
+            else:
+                assert bool(((dwm - dw).abs() > bound).any()), f"{c['name']}: a float32 wgrad loader computing SiLU as {form} would pass"
+        if dt == BF16:
+            check_f32_grid(mag, X.SILU_GRID, "sum |dY s|")
+            check_f32_grid(dw, X.SILU_GRID, "dW")
+
+
+@pytest.mark.parametrize("c", X.GNB_CASES, ids=_silu_ids)
+def test_gnb_silu_rows_keep_a_per_element_bound(c):
+    """The per-tile rows of a data-gradient launch with gnb_silu = 1 on integer u in [-10, 10]: the bound stays far below one term
+    (so one wrong, missing or doubled position fails), and a launch that left dsilu out of the rows is outside it."""
+    o = X.gnb_silu_operands(c)
+    u = X.affine(o["x0"].double(), o["a"].double(), o["b"].double())
+    assert float(u.abs().max()) <= 12 and torch.equal(u, u.round())
+    ids = X.tile_ids(c, "k_conv")
+    z, rows, rb = X.gnb_silu_reference(c, o, ids)
+    check_bf16_exact(z, "the integer data gradient")
+    mags = X.stats_reference(z.abs(), ids, o["x0"].abs())
+    assert float((rb / mags.clamp_min(1.0)).max()) < 1e-3, "a missing position worth a thousandth of its row's magnitude sum must fail"
+    plain = X.stats_reference(z, ids, o["x0"])
+    assert bool(((plain - rows).abs() > rb).any()), c["name"] + ": rows without dsilu would pass"
+
+
+@pytest.mark.parametrize("case", X.GNA_CASES, ids=[c[0] for c in X.GNA_CASES])
+def test_gna_silu_cases_leave_at_most_one_percent_near_a_tie(case):
+    """The skip data gradient with gna_* and gnb_silu = 1: u on the integers of [-10, 10], the conv part an exact integer, the
+    coefficients the identity, and (bf16) at most 1 % of the stored outputs within the tie margin of four times the float32 bound."""
+    from exact_util import TIE_SHARE_MAX
+    o = X.gna_silu_operands(case)
+    u, conv, want, fb = X.gna_silu_reference(o)
+    assert float(u.abs().max()) <= 12 and torch.equal(u, u.round())
+    check_bf16_exact(conv, "the integer conv part")
+    assert set(o["g"].unique().tolist()) == {-0.5, -0.25, 0.0, 0.25, 0.5} and bool((o["cA"] == 1).all())
+    d = (want - conv).abs()                                      # |g dsilu(u)| <= |g| Mag(u)
+    assert float((fb / (conv.abs() + d).clamp_min(2.0 ** -20)).max()) < 2e-5, "the bound is a few dozen fp32 ulps of the terms"
+    # leaving dsilu out (gq = g) is far outside the bound
+    nz = o["g"] != 0
+    assert float((((conv + o["g"].double()) - want).abs()[nz] / fb[nz]).max()) > 1000
+    if case[1] == BF16:
+        share = tie_share(want, TIE_MARGIN_FACTOR * fb)
+        assert share <= TIE_SHARE_MAX, f"{case[0]}: {share:.3%} of the outputs within the tie margin"

@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 import exact_cases as X
 from exact_cases import BF16, F32
-from exact_util import assert_bit_equal, check_bf16_exact, check_f32_exact, guarded, guarded_copy, guards_intact, int_tensor
+from exact_util import assert_bit_equal, assert_within_abs, check_bf16_exact, check_f32_exact, guarded, guarded_copy, guards_intact, int_tensor
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -157,8 +157,8 @@ EXPECT_W = {
 }
 
 
-def _wgrad_launch(ops, c, dtype, o, deterministic):
-    """conv_wgrad of one case into guarded, zeroed fp32 buffers; returns (dw buffer, dbias, variant)."""
+def _wgrad_launch(ops, c, dtype, o, deterministic, silu=False):
+    """conv_wgrad of one case into guarded, zeroed fp32 buffers; returns (dw buffer, dbias, variant).  silu: pre_silu = 1."""
     c1, c2, cout = c["c1"], c["c2"], c["cout"]
     act_in = o["x"]                                     # the prologue (if any) is recomputed by the kernel's loader
     x1, x2 = cl(act_in[:, :c1], dtype), (cl(act_in[:, c1:], dtype) if c2 else None)
@@ -169,7 +169,7 @@ def _wgrad_launch(ops, c, dtype, o, deterministic):
     zb = torch.zeros(wf.shape[1], device=DEV)
     pa, pb = (o["pa"].to(DEV), o["pb"].to(DEV)) if c["pre"] else (None, None)
     d = ops.make_conv_desc(x1, x2, wf, zb, kernel=c["kernel"], cout=cout, split=cout, y=dy, y2=None, stride_hw=c["stride"],
-                           pre_a=pa, pre_b=pb, pre_silu=False)
+                           pre_a=pa, pre_b=pb, pre_silu=bool(silu))
     variant = ops.conv_wgrad_variant(d, dy.shape[-1])
     assert variant == EXPECT_W[(c["name"], _dn(dtype))], variant
     _SEEN.add(variant)
@@ -206,6 +206,29 @@ def test_weight_gradient_is_bit_exact(ops, refs, c, dtype, deterministic):
     assert_bit_equal(dbias[:cout], o["dy"].double().sum((0, 2, 3, 4)), what + ": dbias vs channel sums")
     if dbias.numel() > cout:
         assert bool((dbias[cout:] == 0).all()), what + ": padded dbias tail"
+
+
+@pytest.mark.parametrize("deterministic", [False, True], ids=["atomic", "slabs"])
+@pytest.mark.parametrize("c,dtype", [pytest.param(c, dt, id=f"{c['name']}-{_dn(dt)}") for c in X.SILU_BWD_CASES for dt in c["dtypes"]])
+def test_weight_gradient_with_silu_in_the_loader(ops, c, dtype, deterministic):
+    """The prologue cases with pre_silu = 1, integer u = a x + b in [-2, 6] and dY in +-1 (exact_cases.py): the bf16 loader hands
+    the MFMA exactly bf16(silu64(u)), every sum is exact on the 2^-10 grid and dW after rho_wgrad_finalize equals fp64 bit for
+    bit, through the atomics and the ordered slabs; the float32 kernel is held per element to sum |dY| (silu_f bound at u) +
+    n 2^-24 sum |dY s|."""
+    o = X.silu_bwd_operands(c)
+    dw, mag, bound = X.silu_wgrad_reference(c, o, dtype)
+    dwbuf, dbias, variant, keep = _wgrad_launch(ops, c, dtype, o, deterministic, silu=True)
+    gflat, grad = guarded(tuple(o["w"].shape), F32)
+    ops.wgrad_finalize(dwbuf, grad)
+    torch.cuda.synchronize()
+    assert guards_intact(gflat)
+    what = f"wgrad {c['name']} {variant} pre_silu {'slabs' if deterministic else 'atomic'}: dW [cout, cin, kd, kh, kw]"
+    if dtype == BF16:
+        assert_bit_equal(grad, dw, what)
+    else:
+        worst = assert_within_abs(grad, dw, bound, what)
+        print(f"measured: {what}: worst error {worst:.3e}, bound from {float(bound.min()):.3e}")
+    assert_bit_equal(dbias[:c["cout"]], o["dy"].double().sum((0, 2, 3, 4)), what + ": dbias")
 
 
 @pytest.mark.parametrize("name,dtype", [("3d_pre", BF16), ("3d_pre", F32), ("3d_1x1", BF16), ("1x1_straddle_odd", F32)],

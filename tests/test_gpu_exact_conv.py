@@ -8,7 +8,8 @@ the failure names the index.  Every output (and statistics buffer, and k-split w
 guard bands: an unwritten element and an out-of-range store both fail without faulting.  tests/exact_cases.py holds the cases;
 tests/test_exact_cases_host.py proves on the CPU that the references stay inside the representability caps.
 
-Left out on purpose: only SiLU inside the conv loaders (pre_silu / gnb_silu = 1), which the tolerance tests keep.  The +gn_apply
+SiLU inside the conv loaders (pre_silu = 1) runs on integer u = a x + b, where the bf16 operand is uniquely bf16(silu64(u)):
+test_forward_launch_with_silu_in_the_loader (gnb_silu = 1: test_gpu_exact_groupnorm.py).  The +gn_apply
 epilogue and the fused GroupNorm-backward reduction (gnb_*) take their coefficients as inputs, so integer ones pin them bit for bit:
 test_gpu_exact_groupnorm.py, next to the GroupNorm passes themselves."""
 import pytest
@@ -16,7 +17,7 @@ import torch
 
 import exact_cases as X
 from exact_cases import BF16, F32
-from exact_util import assert_bit_equal, check_bf16_exact, check_f32_exact, guarded, guards_intact
+from exact_util import assert_bit_equal, assert_within_abs, bf16_round, check_bf16_exact, check_f32_exact, guarded, guards_intact
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -132,10 +133,10 @@ PHASE_VARIANTS = {
 }
 
 
-def build_launch(ops, c, dtype, dev=DEV, N=None, prep=True):
+def build_launch(ops, c, dtype, dev=DEV, N=None, prep=True, silu=False):
     """Operands, NaN-prefilled guarded outputs and the descriptor of one forward case.  prep=False: weights are left uninitialised
-    (for variant queries)."""
-    o = X.fwd_operands(c, N)
+    (for variant queries).  silu: the prologue coefficients of exact_cases.silu_fwd_operands and pre_silu = 1."""
+    o = X.silu_fwd_operands(c) if silu else X.fwd_operands(c, N)
     N = o["N"]
     c1, c2, cout, split = c["c1"], c["c2"], c["cout"], c["split"]
     coutp = ((cout + 31) // 32) * 32
@@ -169,7 +170,7 @@ def build_launch(ops, c, dtype, dev=DEV, N=None, prep=True):
         L["sw"], L["sb"] = prepw(o["sw"]), padded_bias(o["sb"], coutp, dev)
         skip = (L["sx1"], L["sx2"], L["sw"], L["sb"])
     L["d"] = ops.make_conv_desc(L["x1"], L["x2"], L["w"], L["b"], kernel=c["kernel"], cout=cout, split=split, y=L["y"], y2=L["y2"],
-                                stride_hw=c["stride"], up_hw=c["up"], pre_a=L["pa"], pre_b=L["pb"], pre_silu=False, res=L["res"],
+                                stride_hw=c["stride"], up_hw=c["up"], pre_a=L["pa"], pre_b=L["pb"], pre_silu=bool(silu), res=L["res"],
                                 res_add=L["add"], res_add_stride=cout if c["add"] else 0, y2_cl=c["y2"] == "cl", res2=L["res2"], skip=skip)
     return L
 
@@ -219,6 +220,63 @@ def test_forward_launch_is_bit_exact(ops, c, dtype):
         check_f32_exact(want, "statistics reference")
         assert_bit_equal(sbuf, want, f"{c['name']} {variant}: fused statistics [N, tile, (sum, sumsq), C]")
         assert guards_intact(sflat), "store outside the statistics buffer"
+
+
+# the pre_silu cases that must take the compile-time-geometry form (whole 4 x 8 x 8 tiles of a stride-1 bf16 3x3x3 layer on the
+# 16x16x32 layout, channels-last outputs, coefficients staged in LDS): apply_pre_regs<true>
+SILU_GEO = {("3d_bm128", "bf16"), ("concat_straddle_bf16", "bf16"), ("fold_bm128", "bf16")}
+# (every other k_conv case must report geo=0: ragged volumes, BM = 32, a channel-major y2, float32, the 2-D / 1-D / 1x1x1 layers)
+SILU_PARAMS = [pytest.param(c, dt, id=f"{c['name']}-{_dn(dt)}") for c in X.SILU_FWD_CASES for dt in c["dtypes"]]
+
+
+@pytest.mark.parametrize("c,dtype", SILU_PARAMS)
+def test_forward_launch_with_silu_in_the_loader(ops, c, dtype):
+    """Every prologue case again with pre_silu = 1 and u = a x + b an integer in [-2, 6] (exact_cases.py, "SiLU in the conv loaders").
+    bf16: the loader's operand is exactly bf16(silu64(u)) and every partial sum is exact, so each stored output equals the fp64
+    reference after one rounding to its storage type (bf16 y / y2; the fp32 head exactly).  float32: the operand is silu_f(u), and
+    every output element stays inside sum |w| (silu_f bound at u) + n 2^-24 sum |w s| (exact_cases.silu_fwd_bound).  The loader
+    form is asserted from the detail string of rho_conv_variant: SILU_GEO names the bf16 3x3x3 cases that run the compile-time
+    4 x 8 x 8 form, whose straight-line staging is the only caller of apply_pre_regs<true>; every other k_conv case must report
+    geo=0 - the 3-D ones read per-batch coefficient rows from LDS through apply_pre<T>, the 2-D / 1-D / 1x1x1 ones read pre_a /
+    pre_b per (sample, channel).  Virtual concat, the folded skip and k_conv32 (conv32.h) are among the cases."""
+    L = build_launch(ops, c, dtype, silu=True)
+    d = L["d"]
+    detail = ops.conv_variant_detail(d)
+    if EXPECT[(c["name"], _dn(dtype))].startswith("k_conv<"):
+        want_detail = "geo=1" if (c["name"], _dn(dtype)) in SILU_GEO else "geo=0"
+        assert detail == want_detail, f"{c['name']} {_dn(dtype)}: {detail}, the case exists for {want_detail}"
+    sflat = None
+    if c["stats"]:                                   # the launch keeps its statistics output (not integers here: only its guards count)
+        sflat, sbuf = guarded((L["N"], ops.conv_stats_tiles(d), 2, c["split"]), F32)
+        d.stats = sbuf.data_ptr()
+    variant = ops.conv_variant(d)
+    assert variant == EXPECT[(c["name"], _dn(dtype))], variant
+    _, ref = X.silu_fwd_reference(c, L["o"], dtype)
+    ops.conv_launch(d)
+    torch.cuda.synchronize()
+    what = f"{c['name']} {variant} pre_silu"
+    assert sflat is None or guards_intact(sflat), what + ": store outside the statistics buffer"
+    if dtype == BF16:
+        want = ref.clone()
+        split = c["split"]
+        want[:, :split] = bf16_round(ref[:, :split])
+        if c["y2"] != "cm_f32":
+            want[:, split:] = bf16_round(ref[:, split:])
+        check_outputs(c, L, want, what)
+    else:
+        N, split, cout = L["N"], c["split"], c["cout"]
+        bound = X.silu_fwd_bound(c, L["o"])
+        worst = 0.0
+        if L["y"] is not None:
+            assert guards_intact(L["yflat"]), what + ": store outside y"
+            worst = max(worst, float(((from_cl(L["y"]).double() - ref[:, :split]).abs() / bound[:, :split]).max()))
+            assert_within_abs(from_cl(L["y"]), ref[:, :split], bound[:, :split], what + ": y")
+        if L["y2"] is not None:
+            assert guards_intact(L["y2flat"]), what + ": store outside y2"
+            got2 = from_cl(L["y2"]) if c["y2"] == "cl" else L["y2"].float().cpu().reshape(N, cout - split, *ref.shape[2:])
+            worst = max(worst, float(((got2.double() - ref[:, split:]).abs() / bound[:, split:]).max()))
+            assert_within_abs(got2, ref[:, split:], bound[:, split:], what + ": y2")
+        print(f"measured: {what}: worst error {worst:.3f} of the derived bound")
 
 
 KSPLIT_PARAMS = [pytest.param(c, dt, id=f"{c['name']}-{_dn(dt)}") for c in X.FWD_CASES if c["ksplit"] for dt in c["dtypes"]]

@@ -32,8 +32,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 F32 = torch.float32
 
-# code -> (forward, derivative) allowance in fp32 ulps of the term magnitude: see the module docstring
-ACT_ULPS = {1: (3, 3), 3: (3, 3), 4: (2, 2), 5: (4, 4), 6: (2, 2)}
+ACT_ULPS = E.ACT_ULPS          # code -> (forward, derivative) allowance in fp32 ulps of the term magnitude: see the module docstring
 
 
 @pytest.fixture(scope="module")

@@ -11,9 +11,12 @@ rho_gn_nblk and the tails of the unrolled loops) and the plain fp64 references; 
 that the references are exactly representable.  Every output - partials, stats, a, b, cA / cP / cQ, dgamma / dbeta, dfilm, the
 scratch rows, dx - lies between guard bands and is prefilled with NaN unless the pass accumulates onto it.
 
-Left to the tolerance tests: rho_groupnorm_act (the legacy UNet), rho_layernorm_*, SiLU inside the conv loaders, and the
-activation derivatives of the backward passes (dsilu_f / dact_other_f in k_gn_bwd_reduce and k_gn_bwd_apply: the backward tests here
-run act code 0; the forward codes 1 - 6 are bounded per element below)."""
+The activation derivatives of the backward passes (dsilu_f / dact_other_f in k_gn_bwd_reduce - both unrolled streams and the tail
+loop - and in k_gn_bwd_apply, and dsilu_f in the per-tile rows of a gnb_silu data gradient) are bounded per element in section 6b
+and beside the gnb_* test; the forward codes 1 - 6 in section 3.  rho_groupnorm_act (the legacy UNet) and rho_layernorm_* have
+their own files (test_gpu_exact_v1_tail.py, test_gpu_exact_layernorm.py), SiLU inside the conv loaders is in test_gpu_exact_conv.py
+and test_gpu_exact_backward.py; dsilu_f on the stored output of the gna_* skip data gradient (gnb_silu = 1, the form the training
+plan launches behind a SiLU) is judged per element in section 8."""
 import math
 
 import pytest
@@ -21,8 +24,9 @@ import torch
 
 import exact_cases as X
 from exact_cases import BF16, F32
-from exact_util import (assert_bit_equal, assert_within_abs, assert_within_ulps, check_bf16_exact, check_f32_exact, check_f32_grid,
-                        guarded, guarded_copy, guards_intact)
+import embed_cases as EC
+from exact_util import (assert_bf16_tie_rule, assert_bit_equal, assert_within_abs, assert_within_ulps, bf16_store_bound, check_bf16_exact, check_f32_exact,
+                        check_f32_grid, f32_ulp, guarded, guarded_copy, guards_intact)
 from detdata import det_normal
 
 pytestmark = pytest.mark.gpu
@@ -563,6 +567,150 @@ def test_backward_apply_adds_the_residual_before_the_term(hip, dtype, stored):
     assert_bit_equal(dx1.float(), want, f"rho_gn_bwd_apply {_dn(dtype)}: cvt_round(dx1 + add1) + term")
 
 
+# ----------------------------------------------------------------------------- 6b. act'(u) in rho_gn_bwd_apply / rho_gn_bwd_reduce
+# a = 1, b = 0 make u = fma(1, x, 0) = x exactly; x is embed_cases.code_inputs() tiled over the case (rounded to the storage type
+# first).  Bounds per element from embed_cases.hw_act_bound: code 1 is dsilu_f (derived from its expression: w (2 + 0.8 |t|) + 7 ulps
+# of s (1 + |x| (1 + s))), codes 2 - 6 are dact_other_f with the ACT_ULPS allowances; a bf16 store adds half a bf16 ulp.
+ACT_BWD_CASES = ("nblk2_tails", "cpg3_straddle", "c2048")      # ppi = 32 with odd tails and two blocks; S < ppi and two sources; ppi = 1
+ALL_CODES = (1, 2, 3, 4, 5, 6)
+
+
+def _code_x(shape, dtype):
+    src = EC.code_inputs().reshape(-1)
+    n = math.prod(shape)
+    return src.repeat(-(-n // src.numel()))[:n].reshape(shape).to(dtype).float()
+
+
+@pytest.mark.parametrize("drop", [False, True], ids=["plain", "drop"])
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=_dn)
+@pytest.mark.parametrize("code", ALL_CODES, ids=[EC.ACT_NAMES[k] for k in ALL_CODES])
+def test_backward_apply_activation_derivative_per_element(hip, code, dtype, drop):
+    """cA = 1, cP = cQ = 0, g = 1: dx = fma(1, gq, fma(0, x, 0)) = gq = act'(x) element for element (times the mask's 0 or 2 in the
+    dropout form, both exact)."""
+    L = hip.lib()
+    for name in ACT_BWD_CASES:
+        c = X.GN_BY_NAME[name]
+        N, S, C, c1, c2 = c["N"], c["S"], c["C"], c["c1"], c["c2"]
+        x = _code_x((N, S, C), dtype)
+        x1, x2 = sources(x, c1, dtype)
+        g = torch.ones(N, S, C, device=DEV, dtype=dtype)
+        a, b, cA = torch.ones(N, C, device=DEV), torch.zeros(N, C, device=DEV), torch.ones(N, C, device=DEV)
+        cP, cQ = torch.zeros(N, 32, device=DEV), torch.zeros(N, 32, device=DEV)
+        f1, dx1 = guarded((N, S, c1), dtype)
+        f2, dx2 = guarded((N, S, c2), dtype) if c2 else (None, None)
+        args = (g.data_ptr(), x1.data_ptr(), c1, hip.ptr(x2), c2, hip.dtype_code(dtype), N, S, a.data_ptr(), b.data_ptr(), code, cA.data_ptr(),
+                cP.data_ptr(), cQ.data_ptr(), dx1.data_ptr(), hip.ptr(dx2), 0, 0, None)
+        want, bound, mag = EC.hw_act_bound(x.double(), code, True)
+        if drop:
+            mask, ctr = drop_mask(hip, (N, S, C))
+            want, bound, mag = want * mask, bound * mask, mag * mask
+            hip.check(L.rho_gn_bwd_apply_drop(*args, DROP_P, DROP_SEED, ctr.data_ptr(), hip.stream()), "rho_gn_bwd_apply_drop")
+        else:
+            hip.check(L.rho_gn_bwd_apply(*args, hip.stream()), "rho_gn_bwd_apply")
+        torch.cuda.synchronize()
+        assert guards_intact(f1) and (f2 is None or guards_intact(f2)), "store outside dx"
+        got = torch.cat([dx1, dx2], 2) if c2 else dx1
+        what = f"rho_gn_bwd_apply{'_drop' if drop else ''} act'={EC.ACT_NAMES[code]} {_dn(dtype)} {name} [N, S, C]"
+        if dtype == F32:
+            meas = float(((got.cpu().double() - want).abs() / f32_ulp(mag)).max())
+            part = float(((got.cpu().double() - want).abs() / bound.clamp_min(1e-300)).max()) if code != 2 else 0.0
+            print(f"measured: {what}: worst {meas:.3f} ulp of the term magnitude, {part:.3f} of the derived bound")
+            assert_within_abs(got, want, bound, what)
+        else:
+            assert_within_abs(got, want, bf16_store_bound(want, bound), what + " (fp32 bound + half a bf16 ulp)")
+
+
+def _reduce(hip, c, dtype, g, x, stats, code, mask_ctr):
+    """rho_gn_bwd_reduce / _drop with a = 1, b = 0 into NaN-prefilled guarded partials; returns (R1, R2) [N, C] summed over the blocks
+    in fp64."""
+    N, S, C, c1, c2 = c["N"], c["S"], c["C"], c["c1"], c["c2"]
+    L = hip.lib()
+    nblk = int(L.rho_gn_nblk(S))
+    x1, x2 = sources(x, c1, dtype)
+    gd, sd = dev(g, dtype), dev(stats)
+    a, b = torch.ones(N, C, device=DEV), torch.zeros(N, C, device=DEV)
+    pf, part = guarded((N, nblk, C // 8, 16), F32)
+    args = (gd.data_ptr(), x1.data_ptr(), c1, hip.ptr(x2), c2, hip.dtype_code(dtype), N, S, a.data_ptr(), b.data_ptr(), sd.data_ptr(), code,
+            part.data_ptr())
+    if mask_ctr is not None:
+        hip.check(L.rho_gn_bwd_reduce_drop(*args, DROP_P, DROP_SEED, mask_ctr[1].data_ptr(), hip.stream()), "rho_gn_bwd_reduce_drop")
+    else:
+        hip.check(L.rho_gn_bwd_reduce(*args, hip.stream()), "rho_gn_bwd_reduce")
+    torch.cuda.synchronize()
+    assert guards_intact(pf), "store outside the partials"
+    pc = part.cpu().double()
+    return pc[..., :8].reshape(N, nblk, C).sum(1), pc[..., 8:].reshape(N, nblk, C).sum(1)
+
+
+def _reduce_stats(c):
+    """Supplied statistics (integer mean, rstd in {0.5, 1, 2}) and the kernel's xhat = fl(fl(x - mean) * rstd), which torch's float32
+    gives bit for bit."""
+    N = c["N"]
+    mean = X.gn_int((N, 32), "gnact_mean" + c["name"], -1, 2)
+    rstd = torch.tensor([0.5, 1.0, 2.0])[X.gn_int((N, 32), "gnact_rstd" + c["name"], 0, 2).long()]
+    return mean, rstd, torch.stack([mean, rstd], 2)
+
+
+@pytest.mark.parametrize("drop", [False, True], ids=["plain", "drop"])
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=_dn)
+@pytest.mark.parametrize("code", ALL_CODES, ids=[EC.ACT_NAMES[k] for k in ALL_CODES])
+def test_backward_reduce_activation_derivative_one_term(hip, code, dtype, drop):
+    """(a) g = 2 at ONE position per (n, channel) and 0 elsewhere, that position once in each accumulation the shape reaches (the
+    unrolled gq and gr streams and the tail loop): every other term is an exact zero, so R1 summed over the blocks is the single
+    term 2 act'(x) (the activation allowance alone) and R2 = fl(2 act'(x) * xhat) with the kernel's own xhat (one rounding more)."""
+    reached = set()
+    for name in ACT_BWD_CASES:
+        c = X.GN_BY_NAME[name]
+        N, S, C = c["N"], c["S"], c["C"]
+        x = _code_x((N, S, C), dtype)
+        mean, rstd, stats = _reduce_stats(c)
+        xh = ((x - X.per_channel(mean, c["cpg"])) * X.per_channel(rstd, c["cpg"])).double()
+        for stream, pos in X.gn_reduce_stream_positions(S, C).items():
+            reached.add((name, stream))
+            g = torch.zeros(N, S, C)
+            g[:, pos, :] = 2.0
+            mc = drop_mask(hip, (N, S, C)) if drop else None
+            R1, R2 = _reduce(hip, c, dtype, g, x, stats, code, mc)
+            d, bound, mag = EC.hw_act_bound(x[:, pos, :].double(), code, True)
+            k = 2.0 * (mc[0][:, pos, :] if drop else 1.0)
+            what = f"rho_gn_bwd_reduce{'_drop' if drop else ''} act'={EC.ACT_NAMES[code]} {_dn(dtype)} {name} g at {pos} ({stream})"
+            assert_within_abs(R1, k * d, k * bound, what + ": R1 [N, C]")
+            xa = xh[:, pos, :].abs()
+            assert_within_abs(R2, k * d * xh[:, pos, :], k * bound * xa + EC.U * k * mag * xa, what + ": R2 [N, C]")
+            if dtype == F32 and not drop:
+                print(f"measured: {what}: R1 worst {float(((R1 - k * d).abs() / f32_ulp(k * mag)).max()):.3f} ulp of the term magnitude")
+    assert {s for n, s in reached if n == "nblk2_tails"} == {"gq", "gr", "tail"} and ("c2048", "gr") in reached, reached
+
+
+@pytest.mark.parametrize("drop", [False, True], ids=["plain", "drop"])
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=_dn)
+@pytest.mark.parametrize("code", ALL_CODES, ids=[EC.ACT_NAMES[k] for k in ALL_CODES])
+def test_backward_reduce_activation_derivative_dense(hip, code, dtype, drop):
+    """(b) dense g in +-2: each term g act'(x) within |g| times the activation bound (the product by +-1, +-2 and the mask's 0 / 2 is
+    exact), and S terms added in some order: every addition of a nonzero term rounds at most once, so a term passes through fewer
+    than S roundings of partial sums bounded by sum |g| Mag: |dR1| <= sum |g| bound + S 2^-24 sum |g| Mag; R2 likewise with every
+    term times |xhat| (the fma adds gq * xhat unrounded)."""
+    for name in ACT_BWD_CASES:
+        c = X.GN_BY_NAME[name]
+        N, S, C = c["N"], c["S"], c["C"]
+        x = _code_x((N, S, C), dtype)
+        mean, rstd, stats = _reduce_stats(c)
+        xh = ((x - X.per_channel(mean, c["cpg"])) * X.per_channel(rstd, c["cpg"])).double()
+        g = X.gn_int((N, S, C), "gnact_g" + name, 0, 3).double() - 2.0
+        g = torch.where(g >= 0, g + 1.0, g)                                        # -2, -1, 1, 2
+        mc = drop_mask(hip, (N, S, C)) if drop else None
+        R1, R2 = _reduce(hip, c, dtype, g.float(), x, stats, code, mc)
+        d, bound, mag = EC.hw_act_bound(x.double(), code, True)
+        k = g * (mc[0] if drop else 1.0)
+        what = f"rho_gn_bwd_reduce{'_drop' if drop else ''} act'={EC.ACT_NAMES[code]} {_dn(dtype)} {name} dense g"
+        b1 = (k.abs() * bound).sum(1) + S * EC.U * (k.abs() * mag).sum(1)
+        b2 = (k.abs() * bound * xh.abs()).sum(1) + S * EC.U * (k.abs() * mag * xh.abs()).sum(1)
+        w1 = assert_within_abs(R1, (k * d).sum(1), b1, what + ": R1 [N, C]")
+        w2 = assert_within_abs(R2, (k * d * xh).sum(1), b2, what + ": R2 [N, C]")
+        if dtype == F32 and not drop:
+            print(f"measured: {what}: R1 worst {w1:.3e} (bound up to {float(b1.max()):.3e}), R2 worst {w2:.3e} (bound up to {float(b2.max()):.3e})")
+
+
 # ----------------------------------------------------------------------------- 7. gnb_* on data-gradient launches
 def cl(t, dtype):
     return t.permute(0, 2, 3, 4, 1).contiguous().to(DEV).to(dtype)
@@ -627,6 +775,43 @@ def test_dgrad_with_fused_groupnorm_backward_reduction(hip, ops, c, dtype):
     _check_coeffs(v, q, C, True, X.is_pow2((C // 32) * S), what + " -> rho_gn_bwd_finalize(fmt=1)")
 
 
+@pytest.mark.parametrize("c,dtype", GNB_PARAMS)
+def test_dgrad_with_fused_activation_derivative_in_the_rows(hip, ops, c, dtype):
+    """The same launches with gnb_silu = 1 and integer u = gnb_a x0 + gnb_b in [-10, 10]: the stored dX is still the integer conv
+    result, bit for bit; the per-tile rows are sum dz and sum dz x0 with dz = dX * dsilu_f(u), each within the per-row bound of
+    exact_cases.gnb_silu_reference (the derived dsilu_f bound per term plus n 2^-24 of the magnitude sums for the n additions)."""
+    o = X.gnb_silu_operands(c)
+    N, c1, c2 = c["N"], c["c1"], c["c2"]
+    C = c1 + c2
+    D, H, W = c["spatial"]
+    dy = cl(o["dy"], dtype)
+    wd = ops.prep_conv_weight_dgrad(o["w"].to(DEV), dtype)
+    zb = torch.zeros(wd.shape[1], device=DEV)
+    x1, x2 = cl(o["x0"][:, :c1], dtype), cl(o["x0"][:, c1:], dtype)
+    a, b = dev(o["a"]), dev(o["b"])
+    xflat, dx = guarded((N, D, H, W, C), dtype)
+    d = ops.make_conv_desc(dy, None, wd, zb, kernel=c["kernel"], cout=C, split=C, y=dx, y2=None)
+    tiles = ops.conv_stats_tiles(d)
+    ids = X.tile_ids(c, "k_conv")
+    assert tiles == int(ids.max()) + 1, (tiles, int(ids.max()) + 1)
+    z, rows, rb = X.gnb_silu_reference(c, o, ids)
+    sflat, sbuf = guarded((N, tiles, 2, C), F32)
+    d.stats = sbuf.data_ptr()
+    d.gnb_x1, d.gnb_x2, d.gnb_c1, d.gnb_silu = x1.data_ptr(), x2.data_ptr(), c1, 1
+    d.gnb_a, d.gnb_b = a.data_ptr(), b.data_ptr()
+    variant = ops.conv_variant(d)
+    assert variant == EXPECT_GNB[(c["name"], _dn(dtype))], variant
+    ops.conv_launch(d)
+    torch.cuda.synchronize()
+    what = f"{c['name']} {variant} gnb_silu"
+    assert guards_intact(xflat), what + ": store outside dX"
+    assert guards_intact(sflat), what + ": store outside the statistics"
+    assert_bit_equal(from_cl(dx), z, what + ": dX")
+    worst = float(((sbuf.cpu().double() - rows).abs() / rb.clamp_min(1e-300)).max())
+    print(f"measured: {what}: per-tile rows worst {worst:.3f} of the derived bound")
+    assert_within_abs(sbuf, rows, rb, what + ": per-tile (sum dz, sum dz x0) [N, tile, 2, C]")
+
+
 # ----------------------------------------------------------------------------- 8. gna_* on the 1x1x1 skip data gradient
 def _gna_variant(case):
     bm = case[5]
@@ -661,3 +846,41 @@ def test_skip_dgrad_with_fused_groupnorm_backward_apply(hip, ops, case):
     assert guards_intact(ff2), name + ": store outside the second region"
     assert_bit_equal(f1.float(), want[..., :c1], f"{name} {variant}: first region [N, D, H, W, c1]")
     assert_bit_equal(f2.float(), want[..., c1:], f"{name} {variant}: second region [N, D, H, W, c2]")
+
+
+@pytest.mark.parametrize("case", X.GNA_CASES, ids=[c[0] for c in X.GNA_CASES])
+def test_skip_dgrad_with_fused_apply_and_activation_derivative(hip, ops, case):
+    """The same +gn_apply launches with gnb_silu = 1, the form the training plan runs behind a SiLU: integer u = a x0 + b in
+    [-10, 10], cA = 1, cP = cQ = 0, g in {0, +-1/4, +-1/2}, so each stored element of both output regions is the exact integer conv result plus
+    g * dsilu_f(u).  float32: within |g| (dsilu_f bound at u) + 2^-24 (|conv| + |g| Mag) per element; bf16: the tie rule with four
+    times that as the margin (the host twin holds the share near a tie to 1 %)."""
+    name, dtype, cy, c1, c2, bm, (N, D, H, W) = case
+    o = X.gna_silu_operands(case)
+    _, _, want, fb = X.gna_silu_reference(o)
+    C = c1 + c2
+    dy = dev(o["dy"], dtype)
+    wd = ops.prep_conv_weight_dgrad(o["w"].to(DEV), dtype)
+    zb = torch.zeros(wd.shape[1], device=DEV)
+    x1, x2, g = dev(o["x0"][..., :c1], dtype), dev(o["x0"][..., c1:], dtype), dev(o["g"], dtype)
+    a, b, cA, cP, cQ = (dev(o[k]) for k in ("a", "b", "cA", "cP", "cQ"))
+    ff1, f1 = guarded((N, D, H, W, c1), dtype)
+    ff2, f2 = guarded((N, D, H, W, c2), dtype)
+    d = ops.make_conv_desc(dy, None, wd, zb, kernel=(1, 1, 1), cout=C, split=c1, y=f1, y2=f2, y2_cl=True)
+    d.gnb_x1, d.gnb_x2, d.gnb_c1, d.gnb_silu = x1.data_ptr(), x2.data_ptr(), c1, 1
+    d.gnb_a, d.gnb_b = a.data_ptr(), b.data_ptr()
+    d.gna_g, d.gna_cA, d.gna_cP, d.gna_cQ = g.data_ptr(), cA.data_ptr(), cP.data_ptr(), cQ.data_ptr()
+    variant = ops.conv_variant(d)
+    assert variant == _gna_variant(case), variant
+    ops.conv_launch(d)
+    torch.cuda.synchronize()
+    assert guards_intact(ff1), name + ": store outside the first region"
+    assert guards_intact(ff2), name + ": store outside the second region"
+    for got, sl, region in ((f1, slice(0, c1), "first"), (f2, slice(c1, C), "second")):
+        what = f"{name} {variant} gnb_silu: {region} region [N, D, H, W, c]"
+        w, f = want[..., sl], fb[..., sl]
+        if dtype == F32:
+            print(f"measured: {what}: worst error {float(((got.cpu().double() - w).abs() / f.clamp_min(1e-300)).max()):.3f} of the derived bound")
+            assert_within_abs(got, w, f, what)
+        else:
+            share = assert_bf16_tie_rule(got, w, 4 * f, what)
+            print(f"measured: {what}: bf16 by the tie rule, {share:.4%} near a tie")
