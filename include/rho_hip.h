@@ -840,7 +840,7 @@ int rho_gd_ddim_step_strided(const float* x_t, const float* model_out, int64_t m
 /* Learned variances (:368-383, ABI 10).  The mean half of sample b is read at model_out + b*mean_stride, its variance values v at
  * var_values + b*var_stride (an output [B, 2C, ...] read in place: var_values = model_out + per_sample, both strides 2*per_sample).
  *   var_type RHO_GD_LEARNED: logvar = v;  RHO_GD_LEARNED_RANGE: frac = (v + 1)/2, logvar = frac*log_beta + (1 - frac)*post_logvar
- * p_mean_variance / condition_mean / p_sample, one pass: x0 as rho_gd_posterior_step,
+ * p_mean_variance / condition_mean / p_sample, one pass, the learned-variance instantiation of rho_gd_posterior_step's kernel: x0 as there,
  *   out = coef1*x0 + coef2*x_t  (+ exp(logvar)*grad)  (+ ((t != 0) * exp(0.5*logvar)) * noise)
  * variance = exp(logvar), log_variance = logvar [batch, per_sample].  Every output may be NULL (not all of them). */
 int rho_gd_posterior_step_lv(const float* x_t, const float* model_out, int64_t mean_stride, const float* var_values, int64_t var_stride,
@@ -863,8 +863,8 @@ int rho_gd_vlb_terms(const float* x_start, const float* x_t, const float* model_
                      float* xstart_mse, float* mse, int64_t out_stride, float* raw_kl, float* raw_nll, float* pred_xstart,
                      void* workspace, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);
 
-/* rho_gd_vlb_terms (prior = 0) with the per-element model log-variance of rho_gd_posterior_step_lv: the KL against post_logvar and
- * the decoder NLL with log_scales = 0.5*logvar; same outputs and reduction (ABI 10). */
+/* rho_gd_vlb_terms (prior = 0) with the per-element model log-variance of rho_gd_posterior_step_lv (the other instantiation of one
+ * kernel): the KL against post_logvar and the decoder NLL with log_scales = 0.5*logvar; same outputs and reduction (ABI 10). */
 int rho_gd_vlb_terms_lv(const float* x_start, const float* x_t, const float* model_out, int64_t mean_stride, const float* var_values,
                         int64_t var_stride, const int64_t* t, const float* tab, int64_t table_len, int mean_type, int var_type,
                         const float* quantile, const float* noise, float* vb, float* xstart_mse, float* mse, int64_t out_stride,

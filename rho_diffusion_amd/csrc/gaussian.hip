@@ -38,13 +38,6 @@ __device__ __forceinline__ int64_t gd_row_index(const int64_t* __restrict__ t, i
 
 __device__ __forceinline__ float gd_tab(const float* __restrict__ tab, int64_t len, int row, int64_t tb) { return tab[(int64_t)row * len + tb]; }
 
-// x0 from the model output: START_X as is; EPSILON _predict_xstart_from_eps (:445-450): sqrt_recip * x - sqrt_recipm1 * eps
-__device__ __forceinline__ float gd_x0(float x, float m, int eps_mode, float sr, float srm1) {
-    if (!eps_mode) return m;
-    const float p0 = sr * x, p1 = srm1 * m;
-    return p0 - p1;
-}
-
 // dynamic thresholding (:400-415): s = max(q, 1); clamp(x0, -s, s) / s
 __device__ __forceinline__ float gd_threshold(float x0, float s) { return fminf(fmaxf(x0, -s), s) / s; }
 
@@ -71,12 +64,72 @@ __device__ __forceinline__ float gd_dgll(float x, float mean, float log_scale) {
     return logf(fmaxf(cdf_plus - cdf_min, 1e-12f));
 }
 
-// normal_kl (metrics/losses.py:28-53): 0.5 * (-1 + lv2 - lv1 + exp(lv1 - lv2) + (m1 - m2)^2 * exp(-lv2)), left to right
-__device__ __forceinline__ float gd_normal_kl(float m1, float lv1, float m2, float lv2) {
-    const float a = ((-1.0f + lv2) - lv1) + expf(lv1 - lv2);
+// normal_kl (metrics/losses.py:28-53): 0.5 * (-1 + lv2 - lv1 + exp(lv1 - lv2) + (m1 - m2)^2 * exp(-lv2)), left to right, in two parts:
+// the log-variance terms (with a fixed variance uniform per sample: evaluated once per thread) and the per-element remainder
+struct GdKlTerms {
+    float e2, k0;                // exp(-lv2);  ((-1 + lv2) - lv1) + exp(lv1 - lv2)
+};
+
+__device__ __forceinline__ GdKlTerms gd_kl_terms(float lv1, float lv2) { return {expf(-lv2), ((-1.0f + lv2) - lv1) + expf(lv1 - lv2)}; }
+
+__device__ __forceinline__ float gd_kl_elem(const GdKlTerms& k, float m1, float m2) {
     const float d = m1 - m2;
-    const float q = (d * d) * expf(-lv2);
-    return 0.5f * (a + q);
+    const float q = (d * d) * k.e2;
+    return 0.5f * (k.k0 + q);
+}
+
+__device__ __forceinline__ float gd_normal_kl(float m1, float lv1, float m2, float lv2) { return gd_kl_elem(gd_kl_terms(lv1, lv2), m1, m2); }
+
+// What a thread of the step kernels knows of its sample: the launch's modes and the rows of the table at t[b], gathered once per thread.
+// LV (learned variance) reads max_log where a fixed variance reads its model_var / model_logvar rows; a kernel gathers further rows of
+// its own at tb.
+struct GdCoef {
+    int eps_mode, range;        // the model predicts epsilon (else x0);  LEARNED_RANGE (else LEARNED)
+    int64_t tb;                 // the clamped row index
+    bool t0;                    // t[b] == 0: no noise, and the VLB takes the decoder NLL
+    float sr, srm1, c1, c2;     // sqrt_recip, sqrt_recipm1, posterior mean coef1 / coef2
+    float post_logvar;          // the true posterior's log-variance; min_log of LEARNED_RANGE
+    float var, logvar;          // fixed variance
+    float max_log;              // learned variance
+};
+
+template <bool LV>
+__device__ __forceinline__ GdCoef gd_coef(const int64_t* __restrict__ t, const float* __restrict__ tab, int64_t len, int b, int eps_mode,
+                                          int range, int32_t* err_flag) {
+    GdCoef c = {};
+    c.eps_mode = eps_mode;
+    c.range = range;
+    c.tb = gd_row_index(t, b, len, err_flag);
+    c.t0 = t[b] == 0;
+    c.sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, c.tb);
+    c.srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, c.tb);
+    c.c1 = gd_tab(tab, len, RHO_GD_COEF1, c.tb);
+    c.c2 = gd_tab(tab, len, RHO_GD_COEF2, c.tb);
+    c.post_logvar = gd_tab(tab, len, RHO_GD_POST_LOGVAR, c.tb);
+    if constexpr (LV) {
+        c.max_log = gd_tab(tab, len, RHO_GD_LOG_BETA, c.tb);
+    } else {
+        c.var = gd_tab(tab, len, RHO_GD_MODEL_VAR, c.tb);
+        c.logvar = gd_tab(tab, len, RHO_GD_MODEL_LOGVAR, c.tb);
+    }
+    return c;
+}
+
+// x0 from the model output: START_X as is; EPSILON _predict_xstart_from_eps (:445-450): sqrt_recip * x - sqrt_recipm1 * eps
+__device__ __forceinline__ float gd_x0(const GdCoef& c, float x, float m) {
+    if (!c.eps_mode) return m;
+    const float p0 = c.sr * x, p1 = c.srm1 * m;
+    return p0 - p1;
+}
+
+// learned variances (:368-383), per element, float32 in the reference's order:
+//   LEARNED:        logvar = v
+//   LEARNED_RANGE:  frac = (v + 1) / 2;  logvar = frac*max_log + (1 - frac)*min_log   (max_log = log(betas), min_log = post_logvar)
+__device__ __forceinline__ float gd_learned_logvar(const GdCoef& c, float v) {
+    if (!c.range) return v;
+    const float frac = (v + 1.0f) / 2.0f;
+    const float p0 = frac * c.max_log, p1 = (1.0f - frac) * c.post_logvar;
+    return p0 + p1;
 }
 
 __device__ __forceinline__ double gd_wave_sum(double v) {
@@ -166,48 +219,84 @@ extern "C" int rho_gd_affine(const float* x, const float* y, float* out, const i
 // p_mean_variance (:338-443) + condition_mean (:473-486) + p_sample (:512-556):
 //   x0 = START_X ? m : sqrt_recip*x - sqrt_recipm1*m;  thresholded when quantile != NULL
 //   mean = coef1*x0 + coef2*x  (+ variance*grad)  (+ ((t != 0) * exp(0.5*logvar)) * noise)
-__global__ __launch_bounds__(GD_THREADS) void k_gd_posterior(const float* __restrict__ xt, const float* __restrict__ mo,
-                                                             const int64_t* __restrict__ t, const float* __restrict__ tab, int64_t len,
-                                                             int eps_mode, const float* __restrict__ quant, const float* __restrict__ grad,
+// Sample b's model output (or x0) is read at mo + b*mo_stride.  A fixed variance (LV = false) takes variance and log-variance from the
+// table, once per thread.  A learned one (:368-383) evaluates them per element from the variance values at vv + b*v_stride (for a
+// [B, 2C, ...] output read in place: the same base + C*S, both strides 2*C*S) and can write them out; every output is optional there.
+template <bool LV>
+__global__ __launch_bounds__(GD_THREADS) void k_gd_posterior(const float* __restrict__ xt, const float* __restrict__ mo, int64_t mo_stride,
+                                                             const float* __restrict__ vv, int64_t v_stride, const int64_t* __restrict__ t,
+                                                             const float* __restrict__ tab, int64_t len, int eps_mode, int range,
+                                                             const float* __restrict__ quant, const float* __restrict__ grad,
                                                              const float* __restrict__ noise, float* __restrict__ out,
-                                                             float* __restrict__ pred_x0, int64_t n, int32_t* err_flag) {
+                                                             float* __restrict__ pred_x0, float* __restrict__ var_out,
+                                                             float* __restrict__ logvar_out, int64_t n, int32_t* err_flag) {
     const int b = blockIdx.y;
-    const int64_t tb = gd_row_index(t, b, len, err_flag);
-    const float sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb), srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
-    const float c1 = gd_tab(tab, len, RHO_GD_COEF1, tb), c2 = gd_tab(tab, len, RHO_GD_COEF2, tb);
-    const float var = gd_tab(tab, len, RHO_GD_MODEL_VAR, tb);
-    const float half_lv = 0.5f * gd_tab(tab, len, RHO_GD_MODEL_LOGVAR, tb);
-    const float nstd = (t[b] != 0 ? 1.0f : 0.0f) * expf(half_lv);
+    const GdCoef c = gd_coef<LV>(t, tab, len, b, eps_mode, range, err_flag);
+    const float nmask = c.t0 ? 0.0f : 1.0f;
+    const float half_lv = 0.5f * c.logvar;
+    const float nstd = nmask * expf(half_lv);
     const float s = quant != nullptr ? fmaxf(quant[b], 1.0f) : 1.0f;
     const int64_t off = (int64_t)b * n;
+    const float* mob = mo + (int64_t)b * mo_stride - off;
+    const float* vb = LV ? vv + (int64_t)b * v_stride - off : nullptr;
     for (int64_t i = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x; i < off + n; i += (int64_t)gridDim.x * GD_THREADS) {
         const float x = xt[i];
-        float x0 = gd_x0(x, mo[i], eps_mode, sr, srm1);
+        float x0 = gd_x0(c, x, mob[i]);
         if (quant != nullptr) x0 = gd_threshold(x0, s);
-        const float p0 = c1 * x0, p1 = c2 * x;
+        float lv = c.logvar;
+        if constexpr (LV) lv = gd_learned_logvar(c, vb[i]);
+        const float p0 = c.c1 * x0, p1 = c.c2 * x;
         float v = p0 + p1;
         if (grad != nullptr) {
-            const float p2 = var * grad[i];
+            const float p2 = (LV ? expf(lv) : c.var) * grad[i];
             v = v + p2;
         }
         if (noise != nullptr) {
-            const float p3 = nstd * noise[i];
+            const float h = 0.5f * lv;
+            const float p3 = (LV ? nmask * expf(h) : nstd) * noise[i];
             v = v + p3;
         }
-        out[i] = v;
+        if (!LV || out != nullptr) out[i] = v;
         if (pred_x0 != nullptr) pred_x0[i] = x0;
+        if constexpr (LV) {
+            if (var_out != nullptr) var_out[i] = expf(lv);
+            if (logvar_out != nullptr) logvar_out[i] = lv;
+        }
     }
 }
+
+namespace {
+bool gd_mean_ok(int mean_type) { return mean_type == RHO_GD_START_X || mean_type == RHO_GD_EPSILON; }
+bool gd_lv_ok(int mean_type, int var_type) { return gd_mean_ok(mean_type) && (var_type == RHO_GD_LEARNED || var_type == RHO_GD_LEARNED_RANGE); }
+}  // namespace
 
 extern "C" int rho_gd_posterior_step(const float* x_t, const float* model_out, const int64_t* t, const float* tab, int64_t table_len,
                                      int mean_type, const float* quantile, const float* grad, const float* noise, float* out,
                                      float* pred_xstart, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream) {
     if (!x_t || !model_out || !t || !tab || !out || batch <= 0 || per_sample <= 0 || table_len <= 0) return RHO_E_ARG;
-    if (mean_type != RHO_GD_START_X && mean_type != RHO_GD_EPSILON) return RHO_E_ARG;
+    if (!gd_mean_ok(mean_type)) return RHO_E_ARG;
     if (batch > 65535) return RHO_E_SHAPE;
     dim3 grid((unsigned)gd_chunks(batch, per_sample), (unsigned)batch);
-    hipLaunchKernelGGL(k_gd_posterior, grid, dim3(GD_THREADS), 0, as_stream(stream), x_t, model_out, t, tab, table_len,
-                       mean_type == RHO_GD_EPSILON ? 1 : 0, quantile, grad, noise, out, pred_xstart, per_sample, err_flag);
+    hipLaunchKernelGGL(k_gd_posterior<false>, grid, dim3(GD_THREADS), 0, as_stream(stream), x_t, model_out, per_sample, nullptr, 0, t, tab,
+                       table_len, mean_type == RHO_GD_EPSILON ? 1 : 0, 0, quantile, grad, noise, out, pred_xstart, nullptr, nullptr, per_sample,
+                       err_flag);
+    RHO_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int rho_gd_posterior_step_lv(const float* x_t, const float* model_out, int64_t mean_stride, const float* var_values,
+                                        int64_t var_stride, const int64_t* t, const float* tab, int64_t table_len, int mean_type, int var_type,
+                                        const float* quantile, const float* grad, const float* noise, float* out, float* pred_xstart,
+                                        float* variance, float* log_variance, int64_t batch, int64_t per_sample, int32_t* err_flag,
+                                        void* stream) {
+    if (!x_t || !model_out || !var_values || !t || !tab || batch <= 0 || per_sample <= 0 || table_len <= 0) return RHO_E_ARG;
+    if (!out && !pred_xstart && !variance && !log_variance) return RHO_E_ARG;
+    if (mean_stride < per_sample || var_stride < per_sample || !gd_lv_ok(mean_type, var_type)) return RHO_E_ARG;
+    if (batch > 65535) return RHO_E_SHAPE;
+    dim3 grid((unsigned)gd_chunks(batch, per_sample), (unsigned)batch);
+    hipLaunchKernelGGL(k_gd_posterior<true>, grid, dim3(GD_THREADS), 0, as_stream(stream), x_t, model_out, mean_stride, var_values, var_stride,
+                       t, tab, table_len, mean_type == RHO_GD_EPSILON ? 1 : 0, var_type == RHO_GD_LEARNED_RANGE ? 1 : 0, quantile, grad,
+                       noise, out, pred_xstart, variance, log_variance, per_sample, err_flag);
     RHO_LAUNCH_CHECK();
     return 0;
 }
@@ -225,29 +314,29 @@ __global__ __launch_bounds__(GD_THREADS) void k_gd_ddim(const float* __restrict_
                                                         float* __restrict__ sample, float* __restrict__ pred_x0, int64_t n, int64_t mo_stride,
                                                         int32_t* err_flag) {
     const int b = blockIdx.y;
-    const int64_t tb = gd_row_index(t, b, len, err_flag);
-    const float sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb), srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
-    const float ab = gd_tab(tab, len, RHO_GD_ABAR, tb);
+    const GdCoef c = gd_coef<false>(t, tab, len, b, eps_mode, 0, err_flag);
+    const float sr = c.sr, srm1 = c.srm1;
+    const float ab = gd_tab(tab, len, RHO_GD_ABAR, c.tb);
     const float sq1mab = sqrtf(1.0f - ab);
     float c_x0, c_eps, msig = 0.0f;
     if (reverse) {
-        const float abn = gd_tab(tab, len, RHO_GD_ABAR_NEXT, tb);
+        const float abn = gd_tab(tab, len, RHO_GD_ABAR_NEXT, c.tb);
         c_x0 = sqrtf(abn);
         c_eps = sqrtf(1.0f - abn);
     } else {
-        const float abp = gd_tab(tab, len, RHO_GD_ABAR_PREV, tb);
+        const float abp = gd_tab(tab, len, RHO_GD_ABAR_PREV, c.tb);
         float sigma = eta * sqrtf((1.0f - abp) / (1.0f - ab));
         sigma = sigma * sqrtf(1.0f - ab / abp);
         c_x0 = sqrtf(abp);
         c_eps = sqrtf((1.0f - abp) - sigma * sigma);
-        msig = (t[b] != 0 ? 1.0f : 0.0f) * sigma;
+        msig = (c.t0 ? 0.0f : 1.0f) * sigma;
     }
     const float s = quant != nullptr ? fmaxf(quant[b], 1.0f) : 1.0f;
     const int64_t off = (int64_t)b * n;
     const float* mob = mo + (int64_t)b * mo_stride - off;
     for (int64_t i = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x; i < off + n; i += (int64_t)gridDim.x * GD_THREADS) {
         const float x = xt[i];
-        float x0 = gd_x0(x, mob[i], eps_mode, sr, srm1);
+        float x0 = gd_x0(c, x, mob[i]);
         if (quant != nullptr) x0 = gd_threshold(x0, s);
         const float ax = sr * x;
         if (grad != nullptr) {
@@ -274,8 +363,7 @@ int gd_ddim_step(const float* x_t, const float* model_out, int64_t model_stride,
                  int mean_type, const float* quantile, const float* grad, const float* noise, float eta, int reverse, float* sample,
                  float* pred_xstart, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream) {
     if (!x_t || !model_out || !t || !tab || !sample || batch <= 0 || per_sample <= 0 || table_len <= 0) return RHO_E_ARG;
-    if (model_stride < per_sample) return RHO_E_ARG;
-    if (mean_type != RHO_GD_START_X && mean_type != RHO_GD_EPSILON) return RHO_E_ARG;
+    if (model_stride < per_sample || !gd_mean_ok(mean_type)) return RHO_E_ARG;
     if (reverse && (eta != 0.0f || noise || grad)) return RHO_E_ARG;
     if (batch > 65535) return RHO_E_SHAPE;
     dim3 grid((unsigned)gd_chunks(batch, per_sample), (unsigned)batch);
@@ -311,61 +399,72 @@ extern "C" int rho_gd_ddim_step_strided(const float* x_t, const float* model_out
 //   nll = -discretized_gaussian_log_likelihood(x_start, model_mean, 0.5*model_logvar)
 //   (x0 - x_start)^2,  ((sr*x_t - x0)/srm1 - noise)^2
 // prior: normal_kl(sqrt_abar[T-1]*x_start, log(1-abar)[T-1], 0, 0).  Partials ws[b][chunk][4] in double.
+// The model output and, with a learned variance (LV), the variance values are read per sample as in k_gd_posterior; a fixed variance
+// evaluates the KL's log-variance terms and the NLL's log-scale once per thread, a learned one per element.
 constexpr int GD_VLB_K = 4;
 
-__global__ __launch_bounds__(GD_THREADS) void k_gd_vlb_partial(const float* __restrict__ xs, const float* __restrict__ xt, const float* __restrict__ mo,
-                                                               const int64_t* __restrict__ t, const float* __restrict__ tab, int64_t len, int eps_mode,
-                                                               const float* __restrict__ quant, const float* __restrict__ noise, int prior,
-                                                               float* __restrict__ pred_x0, double* __restrict__ ws, int64_t n, int32_t* err_flag) {
-    const int b = blockIdx.y;
-    double acc[GD_VLB_K] = {0.0, 0.0, 0.0, 0.0};
-    const int64_t off = (int64_t)b * n;
-    const int64_t i0 = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x, step = (int64_t)gridDim.x * GD_THREADS;
-    if (prior) {
-        const float sa = gd_tab(tab, len, RHO_GD_SQRT_ABAR, len - 1), lv1 = gd_tab(tab, len, RHO_GD_LOG_1M_ABAR, len - 1);
-        const float k0 = ((-1.0f + 0.0f) - lv1) + expf(lv1 - 0.0f);
-        const float e2 = expf(-0.0f);
-        for (int64_t i = i0; i < off + n; i += step) {
-            const float d = (sa * xs[i]) - 0.0f;
-            const float q = (d * d) * e2;
-            acc[0] += (double)(0.5f * (k0 + q));
-        }
-    } else {
-        const int64_t tb = gd_row_index(t, b, len, err_flag);
-        const float sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb), srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
-        const float c1 = gd_tab(tab, len, RHO_GD_COEF1, tb), c2 = gd_tab(tab, len, RHO_GD_COEF2, tb);
-        const float lv1 = gd_tab(tab, len, RHO_GD_POST_LOGVAR, tb), lv2 = gd_tab(tab, len, RHO_GD_MODEL_LOGVAR, tb);
-        const float k0 = ((-1.0f + lv2) - lv1) + expf(lv1 - lv2);
-        const float e2 = expf(-lv2);
-        const float log_scale = 0.5f * lv2;
-        const float s = quant != nullptr ? fmaxf(quant[b], 1.0f) : 1.0f;
-        for (int64_t i = i0; i < off + n; i += step) {
-            const float x = xt[i], x_start = xs[i];
-            float x0 = gd_x0(x, mo[i], eps_mode, sr, srm1);
-            if (quant != nullptr) x0 = gd_threshold(x0, s);
-            if (pred_x0 != nullptr) pred_x0[i] = x0;
-            const float cx = c2 * x;
-            const float tm = (c1 * x_start) + cx;
-            const float mm = (c1 * x0) + cx;
-            const float d = tm - mm;
-            const float q = (d * d) * e2;
-            acc[0] += (double)(0.5f * (k0 + q));
-            acc[1] -= (double)gd_dgll(x_start, mm, log_scale);
-            const float dx = x0 - x_start;
-            acc[2] += (double)(dx * dx);
-            if (noise != nullptr) {
-                const float eps = ((sr * x) - x0) / srm1;
-                const float de = eps - noise[i];
-                acc[3] += (double)(de * de);
-            }
-        }
-    }
+// workgroup sum of the partials, written to ws[b][chunk][:]
+__device__ __forceinline__ void gd_vlb_store(double (&acc)[GD_VLB_K], double* __restrict__ ws) {
     gd_block_sum<GD_VLB_K>(acc);
     if (threadIdx.x == 0) {
-        double* w = ws + ((int64_t)b * gridDim.x + blockIdx.x) * GD_VLB_K;
+        double* w = ws + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * GD_VLB_K;
 #pragma unroll
         for (int k = 0; k < GD_VLB_K; ++k) w[k] = acc[k];
     }
+}
+
+template <bool LV>
+__global__ __launch_bounds__(GD_THREADS) void k_gd_vlb_partial(const float* __restrict__ xs, const float* __restrict__ xt,
+                                                               const float* __restrict__ mo, int64_t mo_stride, const float* __restrict__ vv,
+                                                               int64_t v_stride, const int64_t* __restrict__ t, const float* __restrict__ tab,
+                                                               int64_t len, int eps_mode, int range, const float* __restrict__ quant,
+                                                               const float* __restrict__ noise, float* __restrict__ pred_x0,
+                                                               double* __restrict__ ws, int64_t n, int32_t* err_flag) {
+    const int b = blockIdx.y;
+    double acc[GD_VLB_K] = {0.0, 0.0, 0.0, 0.0};
+    const GdCoef c = gd_coef<LV>(t, tab, len, b, eps_mode, range, err_flag);
+    GdKlTerms kl = gd_kl_terms(c.post_logvar, c.logvar);
+    float log_scale = 0.5f * c.logvar;
+    const float s = quant != nullptr ? fmaxf(quant[b], 1.0f) : 1.0f;
+    const int64_t off = (int64_t)b * n;
+    const float* mob = mo + (int64_t)b * mo_stride - off;
+    const float* vb = LV ? vv + (int64_t)b * v_stride - off : nullptr;
+    for (int64_t i = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x; i < off + n; i += (int64_t)gridDim.x * GD_THREADS) {
+        const float x = xt[i], x_start = xs[i];
+        float x0 = gd_x0(c, x, mob[i]);
+        if (quant != nullptr) x0 = gd_threshold(x0, s);
+        if (pred_x0 != nullptr) pred_x0[i] = x0;
+        if constexpr (LV) {
+            const float lv2 = gd_learned_logvar(c, vb[i]);
+            kl = gd_kl_terms(c.post_logvar, lv2);
+            log_scale = 0.5f * lv2;
+        }
+        const float cx = c.c2 * x;
+        const float tm = (c.c1 * x_start) + cx;
+        const float mm = (c.c1 * x0) + cx;
+        acc[0] += (double)gd_kl_elem(kl, tm, mm);
+        acc[1] -= (double)gd_dgll(x_start, mm, log_scale);
+        const float dx = x0 - x_start;
+        acc[2] += (double)(dx * dx);
+        if (noise != nullptr) {
+            const float eps = ((c.sr * x) - x0) / c.srm1;
+            const float de = eps - noise[i];
+            acc[3] += (double)(de * de);
+        }
+    }
+    gd_vlb_store(acc, ws);
+}
+
+// _prior_bpd: the KL of q(x_{T-1} | x_0) against N(0, 1); it reads the last table column and none of a step's inputs
+__global__ __launch_bounds__(GD_THREADS) void k_gd_prior_partial(const float* __restrict__ xs, const float* __restrict__ tab, int64_t len,
+                                                                 double* __restrict__ ws, int64_t n) {
+    double acc[GD_VLB_K] = {0.0, 0.0, 0.0, 0.0};
+    const float sa = gd_tab(tab, len, RHO_GD_SQRT_ABAR, len - 1);
+    const GdKlTerms kl = gd_kl_terms(gd_tab(tab, len, RHO_GD_LOG_1M_ABAR, len - 1), 0.0f);
+    const int64_t off = (int64_t)blockIdx.y * n;
+    for (int64_t i = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x; i < off + n; i += (int64_t)gridDim.x * GD_THREADS)
+        acc[0] += (double)gd_kl_elem(kl, sa * xs[i], 0.0f);
+    gd_vlb_store(acc, ws);
 }
 
 // stage 2: per sample means (float32, as mean_flat returns them) / ln 2; vb = where(t == 0, nll, kl)
@@ -402,148 +501,21 @@ extern "C" int rho_gd_vlb_terms(const float* x_start, const float* x_t, const fl
                                 void* workspace, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream) {
     if (!x_start || !tab || !vb || !workspace || batch <= 0 || per_sample <= 0 || table_len <= 0 || out_stride < 1) return RHO_E_ARG;
     if (!prior && (!x_t || !model_out || !t || (mse && !noise))) return RHO_E_ARG;
-    if (mean_type != RHO_GD_START_X && mean_type != RHO_GD_EPSILON) return RHO_E_ARG;
+    if (!gd_mean_ok(mean_type)) return RHO_E_ARG;
     if (batch > 65535) return RHO_E_SHAPE;
     const int64_t chunks = gd_chunks(batch, per_sample);
+    const dim3 grid((unsigned)chunks, (unsigned)batch);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(k_gd_vlb_partial, dim3((unsigned)chunks, (unsigned)batch), dim3(GD_THREADS), 0, st, x_start, x_t, model_out, t, tab,
-                       table_len, mean_type == RHO_GD_EPSILON ? 1 : 0, quantile, noise, prior, pred_xstart, (double*)workspace,
-                       per_sample, err_flag);
+    if (prior)
+        hipLaunchKernelGGL(k_gd_prior_partial, grid, dim3(GD_THREADS), 0, st, x_start, tab, table_len, (double*)workspace, per_sample);
+    else
+        hipLaunchKernelGGL(k_gd_vlb_partial<false>, grid, dim3(GD_THREADS), 0, st, x_start, x_t, model_out, per_sample, nullptr, 0, t, tab,
+                           table_len, mean_type == RHO_GD_EPSILON ? 1 : 0, 0, quantile, noise, pred_xstart, (double*)workspace, per_sample,
+                           err_flag);
     hipLaunchKernelGGL(k_gd_vlb_final, dim3((unsigned)batch), dim3(GD_THREADS), 0, st, (const double*)workspace, chunks, t, prior,
                        per_sample, vb, xstart_mse, mse, out_stride, raw_kl, raw_nll);
     RHO_LAUNCH_CHECK();
     return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- learned variances
-// p_mean_variance with model_var_type LEARNED / LEARNED_RANGE (:368-383).  The model output is [B, 2C, ...]: the mean half of sample b
-// at model_out + b*mean_stride, the variance values v at var_values + b*var_stride (for an output read in place: the same base + C*S,
-// both strides 2*C*S).  Per element, float32 in the reference's order:
-//   LEARNED:        logvar = v
-//   LEARNED_RANGE:  frac = (v + 1) / 2;  logvar = frac*max_log + (1 - frac)*min_log   (max_log = log(betas), min_log = post_logvar)
-//   var = exp(logvar)
-namespace {
-__device__ __forceinline__ float gd_learned_logvar(float v, int range, float min_log, float max_log) {
-    if (!range) return v;
-    const float frac = (v + 1.0f) / 2.0f;
-    const float p0 = frac * max_log, p1 = (1.0f - frac) * min_log;
-    return p0 + p1;
-}
-
-// d logvar / d v (autograd's order: d frac = g*max_log + -(g*min_log), d v = d frac / 2)
-__device__ __forceinline__ float gd_learned_dlogvar(float g, int range, float min_log, float max_log) {
-    if (!range) return g;
-    const float p0 = g * max_log, p1 = g * min_log;
-    return (p0 + -p1) / 2.0f;
-}
-
-int gd_lv_args(int mean_type, int var_type) {
-    if (mean_type != RHO_GD_START_X && mean_type != RHO_GD_EPSILON) return RHO_E_ARG;
-    if (var_type != RHO_GD_LEARNED && var_type != RHO_GD_LEARNED_RANGE) return RHO_E_ARG;
-    return 0;
-}
-}  // namespace
-
-// mean = coef1*x0 + coef2*x (+ var*grad) (+ ((t != 0) * exp(0.5*logvar)) * noise), var / logvar per element
-__global__ __launch_bounds__(GD_THREADS) void k_gd_posterior_lv(const float* __restrict__ xt, const float* __restrict__ mo, int64_t mo_stride,
-                                                                const float* __restrict__ vv, int64_t v_stride, const int64_t* __restrict__ t,
-                                                                const float* __restrict__ tab, int64_t len, int eps_mode, int range,
-                                                                const float* __restrict__ quant, const float* __restrict__ grad,
-                                                                const float* __restrict__ noise, float* __restrict__ out,
-                                                                float* __restrict__ pred_x0, float* __restrict__ var_out,
-                                                                float* __restrict__ logvar_out, int64_t n, int32_t* err_flag) {
-    const int b = blockIdx.y;
-    const int64_t tb = gd_row_index(t, b, len, err_flag);
-    const float sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb), srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
-    const float c1 = gd_tab(tab, len, RHO_GD_COEF1, tb), c2 = gd_tab(tab, len, RHO_GD_COEF2, tb);
-    const float min_log = gd_tab(tab, len, RHO_GD_POST_LOGVAR, tb), max_log = gd_tab(tab, len, RHO_GD_LOG_BETA, tb);
-    const float nmask = t[b] != 0 ? 1.0f : 0.0f;
-    const float s = quant != nullptr ? fmaxf(quant[b], 1.0f) : 1.0f;
-    const int64_t off = (int64_t)b * n;
-    const float* mob = mo + (int64_t)b * mo_stride - off;
-    const float* vb = vv + (int64_t)b * v_stride - off;
-    for (int64_t i = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x; i < off + n; i += (int64_t)gridDim.x * GD_THREADS) {
-        const float x = xt[i];
-        float x0 = gd_x0(x, mob[i], eps_mode, sr, srm1);
-        if (quant != nullptr) x0 = gd_threshold(x0, s);
-        const float lv = gd_learned_logvar(vb[i], range, min_log, max_log);
-        const float p0 = c1 * x0, p1 = c2 * x;
-        float v = p0 + p1;
-        if (grad != nullptr) {
-            const float p2 = expf(lv) * grad[i];
-            v = v + p2;
-        }
-        if (noise != nullptr) {
-            const float h = 0.5f * lv;
-            const float p3 = (nmask * expf(h)) * noise[i];
-            v = v + p3;
-        }
-        if (out != nullptr) out[i] = v;
-        if (pred_x0 != nullptr) pred_x0[i] = x0;
-        if (var_out != nullptr) var_out[i] = expf(lv);
-        if (logvar_out != nullptr) logvar_out[i] = lv;
-    }
-}
-
-extern "C" int rho_gd_posterior_step_lv(const float* x_t, const float* model_out, int64_t mean_stride, const float* var_values,
-                                        int64_t var_stride, const int64_t* t, const float* tab, int64_t table_len, int mean_type, int var_type,
-                                        const float* quantile, const float* grad, const float* noise, float* out, float* pred_xstart,
-                                        float* variance, float* log_variance, int64_t batch, int64_t per_sample, int32_t* err_flag,
-                                        void* stream) {
-    if (!x_t || !model_out || !var_values || !t || !tab || batch <= 0 || per_sample <= 0 || table_len <= 0) return RHO_E_ARG;
-    if (!out && !pred_xstart && !variance && !log_variance) return RHO_E_ARG;
-    if (mean_stride < per_sample || var_stride < per_sample || gd_lv_args(mean_type, var_type)) return RHO_E_ARG;
-    if (batch > 65535) return RHO_E_SHAPE;
-    dim3 grid((unsigned)gd_chunks(batch, per_sample), (unsigned)batch);
-    hipLaunchKernelGGL(k_gd_posterior_lv, grid, dim3(GD_THREADS), 0, as_stream(stream), x_t, model_out, mean_stride, var_values, var_stride, t,
-                       tab, table_len, mean_type == RHO_GD_EPSILON ? 1 : 0, var_type == RHO_GD_LEARNED_RANGE ? 1 : 0, quantile, grad, noise,
-                       out, pred_xstart, variance, log_variance, per_sample, err_flag);
-    RHO_LAUNCH_CHECK();
-    return 0;
-}
-
-// _vb_terms_bpd / calc_bpd_loop statistics with a learned variance: as k_gd_vlb_partial with the model log-variance per element
-__global__ __launch_bounds__(GD_THREADS) void k_gd_vlb_lv_partial(const float* __restrict__ xs, const float* __restrict__ xt,
-                                                                  const float* __restrict__ mo, int64_t mo_stride, const float* __restrict__ vv,
-                                                                  int64_t v_stride, const int64_t* __restrict__ t, const float* __restrict__ tab,
-                                                                  int64_t len, int eps_mode, int range, const float* __restrict__ quant,
-                                                                  const float* __restrict__ noise, float* __restrict__ pred_x0,
-                                                                  double* __restrict__ ws, int64_t n, int32_t* err_flag) {
-    const int b = blockIdx.y;
-    double acc[GD_VLB_K] = {0.0, 0.0, 0.0, 0.0};
-    const int64_t off = (int64_t)b * n;
-    const int64_t tb = gd_row_index(t, b, len, err_flag);
-    const float sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb), srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
-    const float c1 = gd_tab(tab, len, RHO_GD_COEF1, tb), c2 = gd_tab(tab, len, RHO_GD_COEF2, tb);
-    const float lv1 = gd_tab(tab, len, RHO_GD_POST_LOGVAR, tb), max_log = gd_tab(tab, len, RHO_GD_LOG_BETA, tb);
-    const float s = quant != nullptr ? fmaxf(quant[b], 1.0f) : 1.0f;
-    const float* mob = mo + (int64_t)b * mo_stride - off;
-    const float* vb = vv + (int64_t)b * v_stride - off;
-    for (int64_t i = off + (int64_t)blockIdx.x * GD_THREADS + threadIdx.x; i < off + n; i += (int64_t)gridDim.x * GD_THREADS) {
-        const float x = xt[i], x_start = xs[i];
-        float x0 = gd_x0(x, mob[i], eps_mode, sr, srm1);
-        if (quant != nullptr) x0 = gd_threshold(x0, s);
-        if (pred_x0 != nullptr) pred_x0[i] = x0;
-        const float lv2 = gd_learned_logvar(vb[i], range, lv1, max_log);
-        const float cx = c2 * x;
-        const float tm = (c1 * x_start) + cx;
-        const float mm = (c1 * x0) + cx;
-        acc[0] += (double)gd_normal_kl(tm, lv1, mm, lv2);
-        acc[1] -= (double)gd_dgll(x_start, mm, 0.5f * lv2);
-        const float dx = x0 - x_start;
-        acc[2] += (double)(dx * dx);
-        if (noise != nullptr) {
-            const float eps = ((sr * x) - x0) / srm1;
-            const float de = eps - noise[i];
-            acc[3] += (double)(de * de);
-        }
-    }
-    gd_block_sum<GD_VLB_K>(acc);
-    if (threadIdx.x == 0) {
-        double* w = ws + ((int64_t)b * gridDim.x + blockIdx.x) * GD_VLB_K;
-#pragma unroll
-        for (int k = 0; k < GD_VLB_K; ++k) w[k] = acc[k];
-    }
 }
 
 extern "C" int rho_gd_vlb_terms_lv(const float* x_start, const float* x_t, const float* model_out, int64_t mean_stride, const float* var_values,
@@ -553,11 +525,11 @@ extern "C" int rho_gd_vlb_terms_lv(const float* x_start, const float* x_t, const
                                    int32_t* err_flag, void* stream) {
     if (!x_start || !x_t || !model_out || !var_values || !t || !tab || !vb || !workspace || (mse && !noise)) return RHO_E_ARG;
     if (batch <= 0 || per_sample <= 0 || table_len <= 0 || out_stride < 1) return RHO_E_ARG;
-    if (mean_stride < per_sample || var_stride < per_sample || gd_lv_args(mean_type, var_type)) return RHO_E_ARG;
+    if (mean_stride < per_sample || var_stride < per_sample || !gd_lv_ok(mean_type, var_type)) return RHO_E_ARG;
     if (batch > 65535) return RHO_E_SHAPE;
     const int64_t chunks = gd_chunks(batch, per_sample);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(k_gd_vlb_lv_partial, dim3((unsigned)chunks, (unsigned)batch), dim3(GD_THREADS), 0, st, x_start, x_t, model_out,
+    hipLaunchKernelGGL(k_gd_vlb_partial<true>, dim3((unsigned)chunks, (unsigned)batch), dim3(GD_THREADS), 0, st, x_start, x_t, model_out,
                        mean_stride, var_values, var_stride, t, tab, table_len, mean_type == RHO_GD_EPSILON ? 1 : 0,
                        var_type == RHO_GD_LEARNED_RANGE ? 1 : 0, quantile, noise, pred_xstart, (double*)workspace, per_sample, err_flag);
     hipLaunchKernelGGL(k_gd_vlb_final, dim3((unsigned)batch), dim3(GD_THREADS), 0, st, (const double*)workspace, chunks, t, 0, per_sample, vb,
@@ -576,30 +548,16 @@ extern "C" int rho_gd_vlb_terms_lv(const float* x_start, const float* x_t, const
 namespace {
 constexpr int GD_HYB_K = 2;
 
-struct GdHybCoef {
-    float sr, srm1, c1, c2, lv1, max_log;
-    int eps_mode, range, t0;
-};
-
-__device__ __forceinline__ GdHybCoef gd_hyb_coef(const int64_t* __restrict__ t, const float* __restrict__ tab, int64_t len, int b, int eps_mode,
-                                                 int range, int32_t* err_flag) {
-    const int64_t tb = gd_row_index(t, b, len, err_flag);
-    GdHybCoef c;
-    c.sr = gd_tab(tab, len, RHO_GD_SQRT_RECIP, tb);
-    c.srm1 = gd_tab(tab, len, RHO_GD_SQRT_RECIPM1, tb);
-    c.c1 = gd_tab(tab, len, RHO_GD_COEF1, tb);
-    c.c2 = gd_tab(tab, len, RHO_GD_COEF2, tb);
-    c.lv1 = gd_tab(tab, len, RHO_GD_POST_LOGVAR, tb);
-    c.max_log = gd_tab(tab, len, RHO_GD_LOG_BETA, tb);
-    c.eps_mode = eps_mode;
-    c.range = range;
-    c.t0 = t[b] == 0;
-    return c;
+// d logvar / d v (autograd's order: d frac = g*max_log + -(g*min_log), d v = d frac / 2)
+__device__ __forceinline__ float gd_learned_dlogvar(const GdCoef& c, float g) {
+    if (!c.range) return g;
+    const float p0 = g * c.max_log, p1 = g * c.post_logvar;
+    return (p0 + -p1) / 2.0f;
 }
 
 // the means of one element: (true mean, frozen model mean)
-__device__ __forceinline__ void gd_hyb_means(const GdHybCoef& c, float x, float xs, float m, float& tm, float& mm) {
-    const float x0 = gd_x0(x, m, c.eps_mode, c.sr, c.srm1);
+__device__ __forceinline__ void gd_hyb_means(const GdCoef& c, float x, float xs, float m, float& tm, float& mm) {
+    const float x0 = gd_x0(c, x, m);
     const float cx = c.c2 * x;
     tm = (c.c1 * xs) + cx;
     mm = (c.c1 * x0) + cx;
@@ -659,27 +617,27 @@ __device__ __forceinline__ float gd_kl_bwd(float g, float m1, float lv1, float m
 }
 
 // mean((target - m)^2) and the selected VLB term of one element pair
-__device__ __forceinline__ void gd_hyb_fwd_elem(const GdHybCoef& c, float x, float xs, float tg, float m, float v, double (&acc)[GD_HYB_K]) {
+__device__ __forceinline__ void gd_hyb_fwd_elem(const GdCoef& c, float x, float xs, float tg, float m, float v, double (&acc)[GD_HYB_K]) {
     const float d = tg - m;
     acc[0] += (double)(d * d);
     float tm, mm;
     gd_hyb_means(c, x, xs, m, tm, mm);
-    const float lv2 = gd_learned_logvar(v, c.range, c.lv1, c.max_log);
+    const float lv2 = gd_learned_logvar(c, v);
     if (c.t0) acc[1] -= (double)gd_dgll(xs, mm, 0.5f * lv2);
-    else acc[1] += (double)gd_normal_kl(tm, c.lv1, mm, lv2);
+    else acc[1] += (double)gd_normal_kl(tm, c.post_logvar, mm, lv2);
 }
 
 // (d mean-half, d variance-half) of one element pair; gm = d loss / d mse[b] / n, gv = d loss / d vb[b] * scale / ln2 / n
-__device__ __forceinline__ void gd_hyb_bwd_elem(const GdHybCoef& c, float x, float xs, float tg, float m, float v, float gm, float gv, float& dm,
+__device__ __forceinline__ void gd_hyb_bwd_elem(const GdCoef& c, float x, float xs, float tg, float m, float v, float gm, float gv, float& dm,
                                                 float& dv) {
     const float d = tg - m;
     const float p = gm * (2.0f * d);
     dm = -p;
     float tm, mm;
     gd_hyb_means(c, x, xs, m, tm, mm);
-    const float lv2 = gd_learned_logvar(v, c.range, c.lv1, c.max_log);
-    const float dlv = c.t0 ? gd_nll_bwd(gv, xs, mm, lv2) : gd_kl_bwd(gv, tm, c.lv1, mm, lv2);
-    dv = gd_learned_dlogvar(dlv, c.range, c.lv1, c.max_log);
+    const float lv2 = gd_learned_logvar(c, v);
+    const float dlv = c.t0 ? gd_nll_bwd(gv, xs, mm, lv2) : gd_kl_bwd(gv, tm, c.post_logvar, mm, lv2);
+    dv = gd_learned_dlogvar(c, dlv);
 }
 }  // namespace
 
@@ -689,7 +647,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_gd_hybrid_partial(const float* _
                                                                   const int64_t* __restrict__ t, const float* __restrict__ tab, int64_t len,
                                                                   int eps_mode, int range, double* __restrict__ ws, int64_t n, int32_t* err_flag) {
     const int b = blockIdx.y;
-    const GdHybCoef c = gd_hyb_coef(t, tab, len, b, eps_mode, range, err_flag);
+    const GdCoef c = gd_coef<true>(t, tab, len, b, eps_mode, range, err_flag);
     double acc[GD_HYB_K] = {0.0, 0.0};
     const int64_t off = (int64_t)b * n;
     const float* mb = mo + 2 * off;
@@ -744,7 +702,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_gd_hybrid_bwd(const float* __res
                                                               const float* __restrict__ g_vb, float* __restrict__ grad, int64_t n,
                                                               int32_t* err_flag) {
     const int b = blockIdx.y;
-    const GdHybCoef c = gd_hyb_coef(t, tab, len, b, eps_mode, range, err_flag);
+    const GdCoef c = gd_coef<true>(t, tab, len, b, eps_mode, range, err_flag);
     // autograd: loss = mse + vb hands g_loss to both; the reference's ops in order: (vb * scale), / ln2, mean over n
     const float gl = g_loss != nullptr ? g_loss[b] : 0.0f;
     const float gms = g_mse != nullptr ? gl + g_mse[b] : gl;
@@ -786,7 +744,7 @@ extern "C" int rho_gd_hybrid_loss(const float* x_start, const float* x_t, const 
                                   const float* tab, int64_t table_len, int mean_type, int var_type, int rescaled, float vb_scale, float* loss,
                                   float* mse, float* vb, void* workspace, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream) {
     if (!x_start || !x_t || !target || !model_out || !t || !tab || !loss || !workspace) return RHO_E_ARG;
-    if (batch <= 0 || per_sample <= 0 || table_len <= 0 || gd_lv_args(mean_type, var_type)) return RHO_E_ARG;
+    if (batch <= 0 || per_sample <= 0 || table_len <= 0 || !gd_lv_ok(mean_type, var_type)) return RHO_E_ARG;
     if (batch > 65535) return RHO_E_SHAPE;
     const int v = (per_sample & 3) == 0 ? 4 : 1;
     const int64_t chunks = gd_hyb_chunks(batch, per_sample, v);      // <= gd_chunks(batch, per_sample): the workspace of the VLB pass fits
@@ -810,7 +768,7 @@ extern "C" int rho_gd_hybrid_loss_bwd(const float* x_start, const float* x_t, co
                                       const float* g_loss, const float* g_mse, const float* g_vb, float* grad, int64_t batch, int64_t per_sample,
                                       int32_t* err_flag, void* stream) {
     if (!x_start || !x_t || !target || !model_out || !t || !tab || !grad) return RHO_E_ARG;
-    if (batch <= 0 || per_sample <= 0 || table_len <= 0 || gd_lv_args(mean_type, var_type)) return RHO_E_ARG;
+    if (batch <= 0 || per_sample <= 0 || table_len <= 0 || !gd_lv_ok(mean_type, var_type)) return RHO_E_ARG;
     if (batch > 65535) return RHO_E_SHAPE;
     const int v = (per_sample & 3) == 0 ? 4 : 1;
     dim3 grid((unsigned)gd_hyb_chunks(batch, per_sample, v), (unsigned)batch);

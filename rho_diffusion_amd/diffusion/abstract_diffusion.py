@@ -8,6 +8,7 @@ attributes the pipelines use (``log``, ``device``, ``global_rank``, ``current_ep
 from __future__ import annotations
 
 import math
+import os
 import types
 from logging import getLogger
 from typing import Any, Mapping, Union
@@ -16,6 +17,8 @@ import torch
 from torch import Tensor, nn
 from torch.optim import AdamW
 
+from .. import hip
+from ..engine import ops
 from ..registry import registry
 
 try:  # pragma: no cover - lightning is not installed in the build container
@@ -70,6 +73,40 @@ class AbstractDiffusionPipeline(_Base):
         self.save_hyperparameters({"model_kwargs": backbone_kwargs, "opt_kwargs": dict(opt_kwargs or {})})
         self.timesteps = timesteps
         self._python_logger = getLogger(self.__class__.__name__)
+
+    def _init_loss_and_noise(self, loss_func) -> None:
+        """What the constructors of the concrete pipelines share: ``loss_func`` resolved by registry name / class, and the
+        counter-based RNG state of ``noise``: one Philox stream per rank (seed + rank), the offset advances per draw."""
+        if isinstance(loss_func, str):
+            loss_func = registry.get("nn", loss_func)
+        if isinstance(loss_func, type):
+            loss_func = loss_func()
+        self.loss_func = loss_func
+        self.noise_seed = int(os.environ.get("RHO_SEED", "777")) + int(os.environ.get("RANK", "0"))
+        self._noise_offset = 0
+
+    def noise(self, data: Tensor) -> Tensor:
+        """Standard normal with the shape of ``data`` (the reference's randn_like), Philox4x32-10 on the device."""
+        hip.require_gpu(data, "data")
+        out = torch.empty(data.shape, dtype=torch.float32, device=data.device)
+        ops.philox_normal(out, self.noise_seed, self._noise_offset)
+        self._noise_offset += (out.numel() + 3) // 4
+        return out
+
+    @staticmethod
+    def _resolve_conditions(conditions, batch_size: int, device):
+        """The ``conditions`` forms reverse_process accepts (ddpm.py:173-184): one label for the batch, "auto" (random labels of
+        ten classes, drawn on the device), a tensor (taken as it is), a list; None is unconditional."""
+        if conditions is None or isinstance(conditions, torch.Tensor):
+            return conditions
+        if isinstance(conditions, int):
+            return torch.full((batch_size,), fill_value=conditions, device=device, dtype=torch.long)
+        if isinstance(conditions, str) and conditions == "auto":
+            return torch.randint(0, 10, (batch_size,), device=device).long()
+        if isinstance(conditions, list):
+            return torch.tensor(conditions).to(device)
+        what = repr(conditions) if isinstance(conditions, str) else type(conditions).__name__
+        raise TypeError(f'conditions must be None, an int, "auto", a tensor or a list: got {what}')
 
     def configure_optimizers(self, mpi_world_size: int = 1):
         """AdamW defaults merged with the configured kwargs; lr *= sqrt(world) (abstract_diffusion.py:86-148).

@@ -33,7 +33,6 @@ from torch import Tensor, nn
 
 from .. import hip
 from ..engine import ops
-from ..registry import registry
 from ..utils import sample_from_discrete_parameter_space, save_model_checkpoint
 from .abstract_diffusion import AbstractDiffusionPipeline
 from .multistep import SAMPLERS, SPACINGS, dpmpp_2m_coefficients, logsnr_timesteps
@@ -52,11 +51,7 @@ class DDPM(AbstractDiffusionPipeline):
                  sampler: str = "ddim", sampling_spacing=None, guidance_scale=None, cond_drop_prob: float = 0.0):
         super().__init__(backbone=backbone, backbone_kwargs=backbone_kwargs, schedule=schedule, timesteps=timesteps,
                          cond_fn=cond_fn, cond_fn_kwargs=cond_fn_kwargs, optimizer=optimizer, opt_kwargs=opt_kwargs)
-        if isinstance(loss_func, str):
-            loss_func = registry.get("nn", loss_func)
-        if isinstance(loss_func, type):
-            loss_func = loss_func()
-        self.loss_func = loss_func
+        self._init_loss_and_noise(loss_func)
         self.t_checkpoints = t_checkpoints
         self.sampling_batch_size = sampling_batch_size
         self.sample_every_n_epochs = sample_every_n_epochs
@@ -94,9 +89,6 @@ class DDPM(AbstractDiffusionPipeline):
             raise ValueError(f"prediction_type={self.prediction_type!r} / snr_gamma={self.snr_gamma} need loss_func nn.MSELoss(reduction='mean'): "
                              f"the weighted loss is a HIP kernel of that form and has no torch fallback; got {self.loss_func!r}")
         self._snr_weights = {}
-        # counter-based RNG state: one stream per rank (seed + rank), offset advances per draw
-        self.noise_seed = int(os.environ.get("RHO_SEED", "777")) + int(os.environ.get("RANK", "0"))
-        self._noise_offset = 0
         self._nan_flag = None
         self.nan_check_every = 50
         self._steps_seen = 0
@@ -110,16 +102,7 @@ class DDPM(AbstractDiffusionPipeline):
         # torch.manual_seed like the reference; DPTrainer / bench.py switch it on.
         self.device_timesteps = os.environ.get("RHO_DEVICE_TIMESTEPS", "0") == "1"
 
-    # ------------------------------------------------------------------ noise
-    def noise(self, data: Tensor) -> Tensor:
-        """Standard normal with the shape of ``data`` (ddpm.py:101-102), Philox4x32-10 on the device."""
-        hip.require_gpu(data, "data")
-        out = torch.empty(data.shape, dtype=torch.float32, device=data.device)
-        ops.philox_normal(out, self.noise_seed, self._noise_offset)
-        self._noise_offset += (out.numel() + 3) // 4
-        return out
-
-    # ------------------------------------------------------------------ q_sample
+    # ------------------------------------------------------------------ q_sample (noise, ddpm.py:101-102, is the base class's Philox draw)
     def forward_process(self, data: Tensor, t: Union[Tensor, None] = None) -> list:
         """ddpm.py:104-130: returns [x_t, noise]."""
         hip.require_gpu(data, "data")
@@ -231,18 +214,7 @@ class DDPM(AbstractDiffusionPipeline):
 
         x_t = self.noise(x_T).contiguous()
 
-        if conditions is not None:
-            if isinstance(conditions, int):
-                cc = torch.full((batch_size,), fill_value=conditions, device=dev, dtype=torch.long)
-            elif isinstance(conditions, str) and conditions == "auto":
-                cc = torch.randint(0, 10, (batch_size,), device=dev).long()
-            elif isinstance(conditions, torch.Tensor):
-                cc = conditions
-            elif isinstance(conditions, list):
-                cc = torch.tensor(conditions).to(dev)
-        else:
-            cc = None
-        cc = self._preembed_conditions(cc)
+        cc = self._preembed_conditions(self._resolve_conditions(conditions, batch_size, dev))
 
         engine = self.backbone.engine() if hasattr(self.backbone, "engine") else None
         t_dev = torch.full((1,), denoise_steps - 1 if spaced is None else spaced["taus"][-1], dtype=torch.int32, device=dev)
@@ -269,7 +241,7 @@ class DDPM(AbstractDiffusionPipeline):
             return self._reverse_process_spaced(x_all, x_t, cc, engine, scale, spaced, bool(clip_denoised), t_dev, buf)
         t_idx = 0
         if (self.hip_graph_sampling and engine is not None and denoise_steps > 2 and "noise" not in self.__dict__
-                and type(self).noise is DDPM.noise):
+                and type(self).noise is AbstractDiffusionPipeline.noise):
             done = self._reverse_process_graph(x_all, x_t, cc, engine, update, t_dev, denoise_steps, buf, steps_per_ckpt, num_checkpoints)
             if done:
                 self._check_backbone_errors()
@@ -407,7 +379,7 @@ class DDPM(AbstractDiffusionPipeline):
         hist = torch.empty_like(x_t) if spaced.get("sampler", "ddim") == "dpmpp_2m" else None
         result = {"buffer": buf, "denoised": x_t}
         if (self.hip_graph_sampling and engine is not None and S > 2 and "noise" not in self.__dict__
-                and type(self).noise is DDPM.noise):
+                and type(self).noise is AbstractDiffusionPipeline.noise):
             if self._reverse_process_spaced_graph(x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt,
                                                   kind, hist):
                 self._check_backbone_errors()

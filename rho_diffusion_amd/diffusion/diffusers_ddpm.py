@@ -23,7 +23,6 @@ from torch import Tensor
 
 from .. import hip
 from ..engine import ops
-from ..registry import registry
 from .abstract_diffusion import AbstractDiffusionPipeline
 
 __all__ = ["DDPMScheduler", "DiffusersDDPMPipeline"]
@@ -132,25 +131,12 @@ class DiffusersDDPMPipeline(AbstractDiffusionPipeline):
                  sample_every_n_epochs=5, sample_parameter_space=None, save_checkpoint_every_n_epochs=10):
         super().__init__(backbone=backbone, backbone_kwargs=backbone_kwargs, schedule=schedule, timesteps=timesteps,
                          cond_fn=cond_fn, cond_fn_kwargs=cond_fn_kwargs, optimizer=optimizer, opt_kwargs=opt_kwargs)
-        if isinstance(loss_func, str):
-            loss_func = registry.get("nn", loss_func)
-        if isinstance(loss_func, type):
-            loss_func = loss_func()
-        self.loss_func = loss_func
+        self._init_loss_and_noise(loss_func)
         self.t_checkpoints = t_checkpoints
         self.sampling_batch_size = sampling_batch_size
         self.sample_every_n_epochs = sample_every_n_epochs
         self.sample_parameter_space = sample_parameter_space
         self.save_weights_every_n_epochs = save_checkpoint_every_n_epochs
-        self.noise_seed = int(os.environ.get("RHO_SEED", "777")) + int(os.environ.get("RANK", "0"))
-        self._noise_offset = 0
-
-    def noise(self, data: Tensor) -> Tensor:
-        hip.require_gpu(data, "data")
-        out = torch.empty(data.shape, dtype=torch.float32, device=data.device)
-        ops.philox_normal(out, self.noise_seed, self._noise_offset)
-        self._noise_offset += (out.numel() + 3) // 4
-        return out
 
     def forward_process(self, clean_images: Tensor, t: Union[Tensor, None] = None):
         """diffusers.py:146-149: returns (noisy_images, noise)."""
@@ -173,18 +159,7 @@ class DiffusersDDPMPipeline(AbstractDiffusionPipeline):
             steps_per_ckpt = denoise_steps // num_checkpoints
         else:
             num_checkpoints, buf, steps_per_ckpt = 0, None, denoise_steps
-        if conditions is not None:
-            if isinstance(conditions, int):
-                cc = torch.full((batch_size,), fill_value=conditions, device=dev, dtype=torch.long)
-            elif isinstance(conditions, str) and conditions == "auto":
-                cc = torch.randint(0, 10, (batch_size,), device=dev).long()
-            elif isinstance(conditions, torch.Tensor):
-                cc = conditions
-            elif isinstance(conditions, list):
-                cc = torch.tensor(conditions).to(dev)
-        else:
-            cc = None
-        cc = self._preembed_conditions(cc)
+        cc = self._preembed_conditions(self._resolve_conditions(conditions, batch_size, dev))
         engine = self.backbone.engine() if hasattr(self.backbone, "engine") else None
         t_dev = torch.full((1,), denoise_steps - 1, dtype=torch.int32, device=dev)
         t_idx = 0

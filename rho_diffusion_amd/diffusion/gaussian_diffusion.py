@@ -17,17 +17,20 @@ The per-step scalars (four table entries) are kernel arguments computed on the h
 noise (:1186 then :877) and the backbone output is regressed on the once-noised data.
 
 The rest of the reference class's public API (guided-diffusion's) is built on csrc/gaussian.hip, for the mean types START_X /
-EPSILON, the fixed variances and the learned ones (LEARNED / LEARNED_RANGE with a 2C-channel backbone, :368-383, whose output
-halves the kernels read in place; training_losses then returns the hybrid loss mse + vb, :893-930): the distribution helpers (:277-510), ancestral sampling (:512-652), the DDIM loop with eta and
+EPSILON and every variance type: the distribution helpers (:277-510), ancestral sampling (:512-652), the DDIM loop with eta and
 ``cond_fn`` (:654-702, :742-824), DDIM inversion (:704-740), the variational bound in bits per dimension (:826-859, :936-1009)
-and ``training_losses`` (:861-934).  Every kernel gathers per-sample rows of one packed float32 table (``_gd_table``) at a
-device ``t[B]``; the loops never synchronise with the host and poll the error flag once at the end.
+and ``training_losses`` (:861-934).  Every kernel gathers per-sample rows of one packed float32 table (``_tab``) at a device
+``t[B]``; the loops never synchronise with the host and poll the error flag once at the end.
+
+Fixed and learned variances take one path.  ``_x0_source`` hands a step its x0 source and, for LEARNED / LEARNED_RANGE (2C-channel
+backbone, :368-383), the variance half of the model output; both halves are views that the kernels read in place.  The ops.gd_*
+wrappers launch the learned-variance instantiation of a kernel when they are given variance values and the fixed one (variance from
+the table) otherwise.  With a learned variance training_losses returns the hybrid loss mse + vb (:893-930).
 """
 from __future__ import annotations
 
 import enum
 import math
-import os
 from typing import Any, Mapping, Union
 
 import numpy as np
@@ -37,7 +40,6 @@ from torch import Tensor
 from .. import hip
 from .. import metrics  # noqa: F401  (rho_diffusion.metrics.losses resolves under install_alias, as the reference imports it here)
 from ..engine import ops
-from ..registry import registry
 from ..utils import sample_from_discrete_parameter_space, save_model_checkpoint
 from .abstract_diffusion import AbstractDiffusionPipeline
 
@@ -78,8 +80,8 @@ def model_variance_tables(tables: Mapping[str, np.ndarray], var_type: ModelVarTy
         return v, np.log(v)
     if var_type == ModelVarType.FIXED_SMALL:
         return tables["posterior_variance"], tables["posterior_log_variance_clipped"]
-    raise NotImplementedError(f"model_var_type {var_type}: learned variances (gaussian_diffusion.py:368-383) need a 2C-channel "
-                              "backbone and are not built; use FIXED_LARGE or FIXED_SMALL")
+    raise NotImplementedError(f"model_var_type {var_type}: learned variances (gaussian_diffusion.py:368-383) take their value from the "
+                              "2C-channel model output and have no per-t table; this is a table of FIXED_LARGE or FIXED_SMALL")
 
 
 def gd_table_rows(tables: Mapping[str, np.ndarray], var_type: ModelVarType) -> np.ndarray:
@@ -163,11 +165,7 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
                  sample_every_n_epochs=5, sample_parameter_space=None, save_checkpoint_every_n_epochs=10):
         super().__init__(backbone=backbone, backbone_kwargs=backbone_kwargs, schedule=schedule, timesteps=timesteps,
                          cond_fn=cond_fn, cond_fn_kwargs=cond_fn_kwargs, optimizer=optimizer, opt_kwargs=opt_kwargs)
-        if isinstance(loss_func, str):
-            loss_func = registry.get("nn", loss_func)
-        if isinstance(loss_func, type):
-            loss_func = loss_func()
-        self.loss_func = loss_func
+        self._init_loss_and_noise(loss_func)
         self.t_checkpoints = t_checkpoints
         self.sampling_batch_size = sampling_batch_size
         self.sample_every_n_epochs = sample_every_n_epochs
@@ -186,23 +184,13 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         self.timesteps = int(self.betas.shape[0])
         self.dynamic_thresholding_percentile = 0.9
 
-        self.noise_seed = int(os.environ.get("RHO_SEED", "777")) + int(os.environ.get("RANK", "0"))
-        self._noise_offset = 0
         self._dev_tables = {}
         self._quant_ws = None
         self._gd_tables = {}
         self._gd_err = None
         self._gd_ws = None
 
-    # ------------------------------------------------------------------ noise / q_sample
-    def noise(self, data: Tensor) -> Tensor:
-        """:1011-1012, Philox4x32-10 on the device (seed + rank; offset advances per draw)."""
-        hip.require_gpu(data, "data")
-        out = torch.empty(data.shape, dtype=torch.float32, device=data.device)
-        ops.philox_normal(out, self.noise_seed, self._noise_offset)
-        self._noise_offset += (out.numel() + 3) // 4
-        return out
-
+    # ------------------------------------------------------------------ q_sample (noise, :1011-1012, is the base class's Philox draw)
     def _table(self, name: str, device) -> Tensor:
         key = (name, str(device))
         if key not in self._dev_tables:
@@ -248,26 +236,12 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
             steps_per_ckpt = denoise_steps // num_checkpoints
         else:
             num_checkpoints, buf, steps_per_ckpt = 0, None, denoise_steps
-        if conditions is not None:
-            if isinstance(conditions, int):
-                cc = torch.full((batch_size,), fill_value=conditions, device=dev, dtype=torch.long)
-            elif isinstance(conditions, str) and conditions == "auto":
-                cc = torch.randint(0, 10, (batch_size,), device=dev).long()
-            elif isinstance(conditions, torch.Tensor):
-                cc = conditions
-            elif isinstance(conditions, list):
-                cc = torch.tensor(conditions).to(dev)
-        else:
-            cc = None
-        cc = self._preembed_conditions(cc)
+        cc = self._preembed_conditions(self._resolve_conditions(conditions, batch_size, dev))
 
         engine = self.backbone.engine() if hasattr(self.backbone, "engine") else None
         learned, C = self._learned(), x_T.shape[1]
         t_dev = torch.full((1,), denoise_steps - 1, dtype=torch.int32, device=dev)
         quant = torch.empty(batch_size, dtype=torch.float32, device=dev)
-        need = hip.lib().rho_abs_quantile_workspace_bytes(batch_size)
-        if self._quant_ws is None or self._quant_ws.device != dev or self._quant_ws.numel() * 4 < need:
-            self._quant_ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=dev)
         t_idx = 0
         for t in range(denoise_steps - 1, -1, -1):
             if engine is not None:
@@ -279,7 +253,7 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
             x0_hat = x0_hat.contiguous()
             c_recip, c_recipm1, sqrt_abp, coef_eps, sig = self.ddim_coefficients(t, eta)
             z = self.noise(x_t) if sig != 0.0 else None          # the reference draws it always; with eta = 0 it is multiplied by 0
-            ops.abs_quantile(x0_hat, self.dynamic_thresholding_percentile, out=quant, workspace=self._quant_ws)
+            self._quantile(x0_hat, out=quant)
             ops.ddim_step(x_t, x0_hat, quant, z, x_t, None, c_recip, c_recipm1, sqrt_abp, coef_eps, sig)
             if buf is not None and t % steps_per_ckpt == 0 and t_idx < num_checkpoints:
                 buf[:, t_idx].copy_(x_t)
@@ -299,29 +273,26 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
                                       "is not built; use START_X or EPSILON")
         raise NotImplementedError(self.model_mean_type)
 
-    def _gd_table(self, device) -> Tensor:
-        """Packed float32 [RHO_GD_ROWS, T] table for the current ``model_var_type`` on ``device``."""
-        key = (str(device), self.model_var_type)
-        if key not in self._gd_tables:
-            self._gd_tables[key] = torch.from_numpy(gd_table_rows(self.tables, self.model_var_type)).to(device).contiguous()
-        return self._gd_tables[key]
+    def _var_code(self):
+        """var_type of the ops.gd_* calls: None for a fixed variance (that one is in the table)."""
+        return {ModelVarType.LEARNED: ops.GD_LEARNED, ModelVarType.LEARNED_RANGE: ops.GD_LEARNED_RANGE}.get(self.model_var_type)
 
     def _learned(self) -> bool:
-        return self.model_var_type in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE)
-
-    def _var_code(self) -> int:
-        return ops.GD_LEARNED_RANGE if self.model_var_type == ModelVarType.LEARNED_RANGE else ops.GD_LEARNED
-
-    def _gd_table_learned(self, device) -> Tensor:
-        """Packed float32 table of the learned variances (min_log = post_logvar, max_log = log_beta rows)."""
-        key = (str(device), "learned")
-        if key not in self._gd_tables:
-            self._gd_tables[key] = torch.from_numpy(gd_table_rows_learned(self.tables)).to(device).contiguous()
-        return self._gd_tables[key]
+        return self._var_code() is not None
 
     def _tab(self, device) -> Tensor:
-        """The table every gd kernel of the current configuration reads."""
-        return self._gd_table_learned(device) if self._learned() else self._gd_table(device)
+        """The packed float32 [RHO_GD_ROWS, T] table every gd kernel of the current ``model_var_type`` reads, on ``device``.  A learned
+        variance reads its post_logvar (min_log) and log_beta (max_log) rows."""
+        key = (str(device), self.model_var_type)
+        if key not in self._gd_tables:
+            rows = gd_table_rows_learned(self.tables) if self._learned() else gd_table_rows(self.tables, self.model_var_type)
+            self._gd_tables[key] = torch.from_numpy(rows).to(device).contiguous()
+        return self._gd_tables[key]
+
+    def _gd_table(self, device) -> Tensor:
+        """``_tab`` for a fixed ``model_var_type``, whose model_var / model_logvar rows are the model's; a learned type is refused."""
+        model_variance_tables(self.tables, self.model_var_type)
+        return self._tab(device)
 
     def _gd_flag(self, device) -> Tensor:
         if self._gd_err is None or self._gd_err.device != torch.device(device):
@@ -390,52 +361,31 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
             return t.float() * (1000.0 / self.timesteps)
         return t
 
-    def _quantile(self, x: Tensor) -> Tensor:
-        B = x.shape[0]
-        need = hip.lib().rho_abs_quantile_workspace_bytes(B)
-        if self._quant_ws is None or self._quant_ws.device != x.device or self._quant_ws.numel() * 4 < need:
-            self._quant_ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=x.device)
-        return ops.abs_quantile(x, self.dynamic_thresholding_percentile, workspace=self._quant_ws)
+    def _quantile(self, x: Tensor, out: Tensor = None) -> Tensor:
+        """The per-sample dynamic-thresholding quantile of |x| (x any per-sample view), on the pipeline's workspace."""
+        self._quant_ws = ops.quantile_workspace(x.shape[0], x.device, self._quant_ws)
+        return ops.abs_quantile(x, self.dynamic_thresholding_percentile, out=out, workspace=self._quant_ws)
 
     def _x0_source(self, x: Tensor, mo: Tensor, t: Tensor, tab: Tensor, clip_denoised: bool, denoised_fn):
-        """(source, mean code, quantile) for the step kernels: ``process_xstart`` (:400-415).  The model output goes to the kernel
-        as it is unless x0 must exist before the quantile or ``denoised_fn`` (EPSILON with thresholding, any denoised_fn): then x0
-        is materialised first and handed over as a START_X output."""
-        code = self._mean_code()
-        if denoised_fn is None:
-            if clip_denoised and code == ops.GD_EPSILON:
-                mo = ops.gd_affine(x, mo, t, tab, "sqrt_recip", "sqrt_recipm1", "ax-by", err_flag=self._gd_flag(x.device))
-                code = ops.GD_START_X
-            return mo, code, (self._quantile(mo) if clip_denoised else None)
-        if code == ops.GD_EPSILON:
-            mo = ops.gd_affine(x, mo, t, tab, "sqrt_recip", "sqrt_recipm1", "ax-by", err_flag=self._gd_flag(x.device))
-        x0 = self._gd_x(denoised_fn(mo), "denoised_fn output")
-        return x0, ops.GD_START_X, (self._quantile(x0) if clip_denoised else None)
-
-    def _x0_source_lv(self, x: Tensor, mo: Tensor, t: Tensor, tab: Tensor, clip_denoised: bool, denoised_fn):
-        """``_x0_source`` for a learned variance: (x0 source, variance values, mean code, quantile).  The two halves of the [B, 2C, ...]
-        output are read in place (views); x0 is materialised only where the reference needs it first (EPSILON with thresholding,
-        denoised_fn)."""
+        """(source, variance values or None, mean code, quantile) for the step kernels: ``process_xstart`` (:400-415).  With a learned
+        variance the two halves of the [B, 2C, ...] output are views read in place.  The model output goes to the kernel as it is
+        unless x0 must exist before the quantile or ``denoised_fn`` (EPSILON with thresholding, any denoised_fn): then x0 is
+        materialised first and handed over as a START_X output."""
         C = x.shape[1]
-        mean, var = mo[:, :C], mo[:, C:]
+        src, var = (mo[:, :C], mo[:, C:]) if self._learned() else (mo, None)
         code = self._mean_code()
-        n = x.numel() // x.shape[0]
-        if denoised_fn is None and not (clip_denoised and code == ops.GD_EPSILON):
-            return mean, var, code, (self._quantile_rows(mean, n) if clip_denoised else None)
-        if code == ops.GD_EPSILON:
-            x0 = torch.empty_like(x)
-            ops.gd_posterior_step_lv(x, mean, var, t, tab, code, self._var_code(), None, None, None, None, x0, err_flag=self._gd_flag(x.device))
-            mean = x0
-        if denoised_fn is not None:
-            mean = self._gd_x(denoised_fn(mean), "denoised_fn output")
-        return mean, var, ops.GD_START_X, (self._quantile_rows(mean, n) if clip_denoised else None)
-
-    def _quantile_rows(self, x: Tensor, n: int) -> Tensor:
-        B = x.shape[0]
-        need = hip.lib().rho_abs_quantile_workspace_bytes(B)
-        if self._quant_ws is None or self._quant_ws.device != x.device or self._quant_ws.numel() * 4 < need:
-            self._quant_ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=x.device)
-        return ops.abs_quantile_rows(x, self.dynamic_thresholding_percentile, n, workspace=self._quant_ws)
+        if denoised_fn is not None or (clip_denoised and code == ops.GD_EPSILON):
+            if code == ops.GD_EPSILON and var is None:
+                src = ops.gd_affine(x, src, t, tab, "sqrt_recip", "sqrt_recipm1", "ax-by", err_flag=self._gd_flag(x.device))
+            elif code == ops.GD_EPSILON:     # gd_affine takes contiguous operands: the posterior kernel reads the half in place, same x0
+                x0 = torch.empty_like(x)
+                ops.gd_posterior_step(x, src, t, tab, code, None, None, None, None, x0, err_flag=self._gd_flag(x.device), var_values=var,
+                                      var_type=self._var_code())
+                src = x0
+            if denoised_fn is not None:
+                src = self._gd_x(denoised_fn(src), "denoised_fn output")
+            code = ops.GD_START_X
+        return src, var, code, (self._quantile(src) if clip_denoised else None)
 
     def _cond_grad(self, cond_fn, x: Tensor, t: Tensor, model_kwargs) -> Tensor:
         g = cond_fn(x, self._scale_timesteps(t), **(model_kwargs or {}))
@@ -482,17 +432,14 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         t = self._gd_t(t, B, x.device)
         tab = self._tab(x.device)
         mo = self._gd_model(model, x, t, self._gd_model_kwargs(model_kwargs))
-        if self._learned():
-            src, var, code, q = self._x0_source_lv(x, mo, t, tab, clip_denoised, denoised_fn)
-            mean, px, v, lv = (torch.empty_like(x) for _ in range(4))
-            ops.gd_posterior_step_lv(x, src, var, t, tab, code, self._var_code(), q, None, None, mean, px, v, lv,
-                                     err_flag=self._gd_flag(x.device))
-            return {"mean": mean, "variance": v, "log_variance": lv, "pred_xstart": px}
-        src, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
+        src, var, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
         mean, px = torch.empty_like(x), torch.empty_like(x)
-        ops.gd_posterior_step(x, src, t, tab, code, q, None, None, mean, px, err_flag=self._gd_flag(x.device))
-        return {"mean": mean, "variance": self._gd_view(tab, "model_var", t, x.shape),
-                "log_variance": self._gd_view(tab, "model_logvar", t, x.shape), "pred_xstart": px}
+        v, lv = (None, None) if var is None else (torch.empty_like(x), torch.empty_like(x))      # learned: per element, from the kernel
+        ops.gd_posterior_step(x, src, t, tab, code, q, None, None, mean, px, err_flag=self._gd_flag(x.device), var_values=var,
+                              var_type=self._var_code(), variance=v, log_variance=lv)
+        if var is None:                                                                           # fixed: expanded views of the table rows
+            v, lv = self._gd_view(tab, "model_var", t, x.shape), self._gd_view(tab, "model_logvar", t, x.shape)
+        return {"mean": mean, "variance": v, "log_variance": lv, "pred_xstart": px}
 
     def condition_mean(self, cond_fn, p_mean_var: dict, x: Tensor, t: Tensor, model_kwargs=None) -> Tensor:
         """:473-486: mean + variance * cond_fn(x, t).  The mean is re-derived from ``p_mean_var["pred_xstart"]`` in the same pass
@@ -502,13 +449,10 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         tab = self._tab(x.device)
         g = self._cond_grad(cond_fn, x, t, model_kwargs)
         out = torch.empty_like(x)
-        if self._learned():                  # variance per element: exp of p_mean_var's log_variance (bit-equal to its "variance")
-            ops.gd_posterior_step_lv(x, self._gd_x(p_mean_var["pred_xstart"], "pred_xstart"), self._gd_x(p_mean_var["log_variance"],
-                                     "log_variance"), t, tab, ops.GD_START_X, ops.GD_LEARNED, None, g, None, out, None,
-                                     err_flag=self._gd_flag(x.device))
-            return out
+        # a learned variance per element: exp of p_mean_var's log_variance (bit-equal to its "variance"), handed over as LEARNED values
+        var = self._gd_x(p_mean_var["log_variance"], "log_variance") if self._learned() else None
         ops.gd_posterior_step(x, self._gd_x(p_mean_var["pred_xstart"], "pred_xstart"), t, tab, ops.GD_START_X, None, g, None, out, None,
-                              err_flag=self._gd_flag(x.device))
+                              err_flag=self._gd_flag(x.device), var_values=var, var_type=None if var is None else ops.GD_LEARNED)
         return out
 
     def condition_score(self, cond_fn, p_mean_var: dict, x: Tensor, t: Tensor, model_kwargs=None) -> dict:
@@ -530,16 +474,11 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
     def _p_step(self, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, kw, sample, px, t_dev=None) -> dict:
         tab = self._tab(x.device)
         mo = self._gd_model(model, x, t, kw, t_dev)
-        if self._learned():
-            src, var, code, q = self._x0_source_lv(x, mo, t, tab, clip_denoised, denoised_fn)
-            noise = self.noise(x)
-            g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
-            ops.gd_posterior_step_lv(x, src, var, t, tab, code, self._var_code(), q, g, noise, sample, px, err_flag=self._gd_flag(x.device))
-            return {"sample": sample, "pred_xstart": px}
-        src, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
+        src, var, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
         noise = self.noise(x)                                                  # :545, drawn before cond_fn runs
         g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
-        ops.gd_posterior_step(x, src, t, tab, code, q, g, noise, sample, px, err_flag=self._gd_flag(x.device))
+        ops.gd_posterior_step(x, src, t, tab, code, q, g, noise, sample, px, err_flag=self._gd_flag(x.device), var_values=var,
+                              var_type=self._var_code())
         return {"sample": sample, "pred_xstart": px}
 
     @torch.no_grad()
@@ -610,13 +549,7 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
     def _ddim_step(self, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, kw, eta, reverse, sample, px, t_dev=None) -> dict:
         tab = self._tab(x.device)
         mo = self._gd_model(model, x, t, kw, t_dev)
-        if self._learned():                  # the variance half is ignored, as the reference's ddim_sample does
-            src, _, code, q = self._x0_source_lv(x, mo, t, tab, clip_denoised, denoised_fn)
-            g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
-            noise = self.noise(x) if (not reverse and eta != 0.0) else None
-            ops.gd_ddim_step_strided(x, src, t, tab, code, q, g, noise, eta, reverse, sample, px, err_flag=self._gd_flag(x.device))
-            return {"sample": sample, "pred_xstart": px}
-        src, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)
+        src, _, code, q = self._x0_source(x, mo, t, tab, clip_denoised, denoised_fn)     # a learned variance is ignored, as in the reference
         g = self._cond_grad(cond_fn, x, t, model_kwargs) if cond_fn is not None else None
         # :685: the reference draws the noise at every step; with eta = 0 it is multiplied by 0 and no used draw follows it
         noise = self.noise(x) if (not reverse and eta != 0.0) else None
@@ -670,14 +603,9 @@ class GaussianDiffusionPipeline(AbstractDiffusionPipeline):
         tab = self._tab(x_start.device)
         mo = self._gd_model(model, x_t, t, kw, t_dev)
         self._gd_ws = ops.gd_workspace(x_start.shape[0], x_start.numel() // x_start.shape[0], x_start.device, self._gd_ws)
-        if self._learned():
-            src, var, code, q = self._x0_source_lv(x_t, mo, t, tab, clip_denoised, None)
-            ops.gd_vlb_terms_lv(x_start, x_t, src, var, t, tab, code, self._var_code(), q, noise, vb, xstart_mse, mse, raw_kl, raw_nll, px,
-                                workspace=self._gd_ws, err_flag=self._gd_flag(x_start.device))
-            return
-        src, code, q = self._x0_source(x_t, mo, t, tab, clip_denoised, None)
+        src, var, code, q = self._x0_source(x_t, mo, t, tab, clip_denoised, None)
         ops.gd_vlb_terms(x_start, x_t, src, t, tab, code, q, noise, vb, xstart_mse, mse, raw_kl, raw_nll, px, workspace=self._gd_ws,
-                         err_flag=self._gd_flag(x_start.device))
+                         err_flag=self._gd_flag(x_start.device), var_values=var, var_type=self._var_code())
 
     @torch.no_grad()
     def _vb_terms_bpd(self, model, x_start: Tensor, x_t: Tensor, t: Tensor, clip_denoised=True, model_kwargs=None) -> dict:

@@ -171,15 +171,35 @@ def q_sample_coef(x0: Tensor, eps: Tensor, t: Tensor, coef_a: Tensor, coef_b: Te
     return out
 
 
+def quantile_workspace(batch: int, device, ws: Optional[Tensor] = None) -> Tensor:
+    need = hip.lib().rho_abs_quantile_workspace_bytes(batch)
+    if ws is None or ws.device != torch.device(device) or ws.numel() * ws.element_size() < need:
+        ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=device)
+    return ws
+
+
+def _sample_rows(v: Tensor, name: str, batch: int, n: int) -> int:
+    """Per-sample stride of ``v``: a float32 GPU tensor whose sample b is the contiguous block of n elements at v[b] (a contiguous
+    tensor, or one half of a contiguous [B, 2C, ...] learned-variance output sliced along dim 1).  n for a contiguous tensor."""
+    hip.require_gpu(v, name)
+    if v.dtype != torch.float32 or v.dim() < 1 or v.shape[0] != batch or v.numel() != batch * n or not (v.is_contiguous() or v[0].is_contiguous()):
+        raise RhoHipError(f"{name} must be float32 [{batch}, ...] with {n} contiguous elements per sample, got {v.dtype} {tuple(v.shape)} "
+                          f"strides {v.stride()}")
+    return n if batch == 1 or v.is_contiguous() else v.stride(0)
+
+
 def abs_quantile(x: Tensor, q: float, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
-    """Per-sample torch.quantile(|x|.flatten(1), q) (float32, linear interpolation), exact radix select on the device."""
-    x = _f32c(x, "x")
+    """Per-sample torch.quantile(|x|.flatten(1), q) (float32, linear interpolation), exact radix select on the device.  ``x`` is any
+    per-sample view (``_sample_rows``), read in place: e.g. the mean half of a learned-variance output."""
     B = x.shape[0]
-    need = hip.lib().rho_abs_quantile_workspace_bytes(B)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty((need + 3) // 4, dtype=torch.int32, device=x.device)
+    n = x.numel() // B
+    stride = _sample_rows(x, "x", B, n)
+    workspace = quantile_workspace(B, x.device, workspace)
     out = torch.empty(B, dtype=torch.float32, device=x.device) if out is None else out
-    check(hip.lib().rho_abs_quantile(ptr(x), B, x.numel() // B, float(q), ptr(workspace), ptr(out), stream()), "rho_abs_quantile")
+    if stride == n:
+        check(hip.lib().rho_abs_quantile(ptr(x), B, n, float(q), ptr(workspace), ptr(out), stream()), "rho_abs_quantile")
+    else:
+        check(hip.lib().rho_abs_quantile_strided(ptr(x), B, n, stride, float(q), ptr(workspace), ptr(out), stream()), "rho_abs_quantile_strided")
     return out
 
 
@@ -237,33 +257,61 @@ def gd_affine(x: Tensor, y: Optional[Tensor], t: Tensor, tab: Tensor, row_a: str
     return out
 
 
-def gd_posterior_step(x_t: Tensor, model_out: Tensor, t: Tensor, tab: Tensor, mean_type: int, quantile: Optional[Tensor],
-                      grad: Optional[Tensor], noise: Optional[Tensor], out: Tensor, pred_xstart: Optional[Tensor],
-                      err_flag: Optional[Tensor] = None) -> Tensor:
-    """p_mean_variance / condition_mean / p_sample in one pass (rho_gd_posterior_step)."""
-    _f32c(x_t, "x_t")
-    _same(x_t, ("model_out", model_out), ("grad", grad), ("noise", noise), ("out", out), ("pred_xstart", pred_xstart))
-    B = x_t.shape[0]
-    if quantile is not None and (_f32c(quantile, "quantile").numel() != B):
+def _gd_quantile(quantile: Optional[Tensor], batch: int) -> None:
+    if quantile is not None and _f32c(quantile, "quantile").numel() != batch:
         raise RhoHipError("quantile must be float32 [B]")
-    check(hip.lib().rho_gd_posterior_step(ptr(x_t), ptr(model_out), ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab), mean_type, ptr(quantile),
-                                          ptr(grad), ptr(noise), ptr(out), ptr(pred_xstart), B, x_t.numel() // B, ptr(err_flag), stream()),
-          "rho_gd_posterior_step")
+
+
+def _gd_variance(var_values: Optional[Tensor], var_type: Optional[int], *lv_only) -> bool:
+    """Whether the call has a learned variance: ``var_values`` and ``var_type`` come together, and what only a learned variance has
+    (``lv_only``) comes with them."""
+    if (var_values is None) != (var_type is None) or (var_values is None and any(o is not None for o in lv_only)):
+        raise RhoHipError("a learned variance takes var_values and var_type together; variance / log_variance outputs need them")
+    return var_values is not None
+
+
+def gd_posterior_step(x_t: Tensor, model_out: Tensor, t: Tensor, tab: Tensor, mean_type: int, quantile: Optional[Tensor],
+                      grad: Optional[Tensor], noise: Optional[Tensor], out: Optional[Tensor], pred_xstart: Optional[Tensor],
+                      err_flag: Optional[Tensor] = None, var_values: Optional[Tensor] = None, var_type: Optional[int] = None,
+                      variance: Optional[Tensor] = None, log_variance: Optional[Tensor] = None) -> Optional[Tensor]:
+    """p_mean_variance / condition_mean / p_sample in one pass.  With a fixed variance (rho_gd_posterior_step) it comes from ``tab``
+    and ``out`` is required.  With a learned one (rho_gd_posterior_step_lv: ``var_values`` and ``var_type`` GD_LEARNED /
+    GD_LEARNED_RANGE) ``model_out`` (the mean half or an x0) and ``var_values`` are per-sample views read in place, every output is
+    optional and the per-element ``variance`` / ``log_variance`` can be written too."""
+    _f32c(x_t, "x_t")
+    _same(x_t, ("grad", grad), ("noise", noise), ("out", out), ("pred_xstart", pred_xstart), ("variance", variance),
+          ("log_variance", log_variance))
+    B, n = x_t.shape[0], x_t.numel() // x_t.shape[0]
+    _gd_quantile(quantile, B)
+    if _gd_variance(var_values, var_type, variance, log_variance):
+        ms, vs = _sample_rows(model_out, "model_out", B, n), _sample_rows(var_values, "var_values", B, n)
+        check(hip.lib().rho_gd_posterior_step_lv(ptr(x_t), ptr(model_out), ms, ptr(var_values), vs, ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab),
+                                                 mean_type, var_type, ptr(quantile), ptr(grad), ptr(noise), ptr(out), ptr(pred_xstart),
+                                                 ptr(variance), ptr(log_variance), B, n, ptr(err_flag), stream()), "rho_gd_posterior_step_lv")
+    else:
+        _same(x_t, ("model_out", model_out))
+        check(hip.lib().rho_gd_posterior_step(ptr(x_t), ptr(model_out), ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab), mean_type, ptr(quantile),
+                                              ptr(grad), ptr(noise), ptr(out), ptr(pred_xstart), B, n, ptr(err_flag), stream()),
+              "rho_gd_posterior_step")
     return out
 
 
 def gd_ddim_step(x_t: Tensor, model_out: Tensor, t: Tensor, tab: Tensor, mean_type: int, quantile: Optional[Tensor],
                  grad: Optional[Tensor], noise: Optional[Tensor], eta: float, reverse: bool, sample: Tensor, pred_xstart: Optional[Tensor],
                  err_flag: Optional[Tensor] = None) -> Tensor:
-    """ddim_sample (eta, condition_score) or ddim_reverse_sample with per-sample t (rho_gd_ddim_step)."""
+    """ddim_sample (eta, condition_score) or ddim_reverse_sample with per-sample t (rho_gd_ddim_step; rho_gd_ddim_step_strided where
+    ``model_out`` is a non-contiguous per-sample view of x_t's per-sample size, read in place)."""
     _f32c(x_t, "x_t")
-    _same(x_t, ("model_out", model_out), ("grad", grad), ("noise", noise), ("sample", sample), ("pred_xstart", pred_xstart))
-    B = x_t.shape[0]
-    if quantile is not None and (_f32c(quantile, "quantile").numel() != B):
-        raise RhoHipError("quantile must be float32 [B]")
-    check(hip.lib().rho_gd_ddim_step(ptr(x_t), ptr(model_out), ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab), mean_type, ptr(quantile), ptr(grad),
-                                     ptr(noise), float(eta), 1 if reverse else 0, ptr(sample), ptr(pred_xstart), B, x_t.numel() // B,
-                                     ptr(err_flag), stream()), "rho_gd_ddim_step")
+    _same(x_t, ("grad", grad), ("noise", noise), ("sample", sample), ("pred_xstart", pred_xstart))
+    B, n = x_t.shape[0], x_t.numel() // x_t.shape[0]
+    stride = _sample_rows(model_out, "model_out", B, n)
+    _gd_quantile(quantile, B)
+    tail = (ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab), mean_type, ptr(quantile), ptr(grad), ptr(noise), float(eta), 1 if reverse else 0,
+            ptr(sample), ptr(pred_xstart), B, n, ptr(err_flag), stream())
+    if stride == n:
+        check(hip.lib().rho_gd_ddim_step(ptr(x_t), ptr(model_out), *tail), "rho_gd_ddim_step")
+    else:
+        check(hip.lib().rho_gd_ddim_step_strided(ptr(x_t), ptr(model_out), stride, *tail), "rho_gd_ddim_step_strided")
     return sample
 
 
@@ -278,24 +326,33 @@ def gd_vlb_terms(x_start: Tensor, x_t: Optional[Tensor], model_out: Optional[Ten
                  quantile: Optional[Tensor], noise: Optional[Tensor], vb: Tensor, xstart_mse: Optional[Tensor] = None,
                  mse: Optional[Tensor] = None, raw_kl: Optional[Tensor] = None, raw_nll: Optional[Tensor] = None,
                  pred_xstart: Optional[Tensor] = None, prior: bool = False, workspace: Optional[Tensor] = None,
-                 err_flag: Optional[Tensor] = None) -> Tensor:
+                 err_flag: Optional[Tensor] = None, var_values: Optional[Tensor] = None, var_type: Optional[int] = None) -> Tensor:
     """_vb_terms_bpd + calc_bpd_loop statistics (or _prior_bpd) per sample (rho_gd_vlb_terms).  vb / xstart_mse / mse: float32 with
-    B elements at a common stride (e.g. column j of an [N, T] tensor)."""
+    B elements at a common stride (e.g. column j of an [N, T] tensor).  With a learned variance (rho_gd_vlb_terms_lv: ``var_values``
+    and ``var_type``) ``model_out`` and ``var_values`` are per-sample views read in place."""
     _f32c(x_start, "x_start")
-    _same(x_start, ("x_t", x_t), ("model_out", model_out), ("noise", noise), ("pred_xstart", pred_xstart))
+    _same(x_start, ("x_t", x_t), ("noise", noise), ("pred_xstart", pred_xstart))
     B, n = x_start.shape[0], x_start.numel() // x_start.shape[0]
     stride = vb.stride(0) if vb.dim() == 1 else 1
     for name, o in (("vb", vb), ("xstart_mse", xstart_mse), ("mse", mse)):
         if o is not None and (o.dtype != torch.float32 or not o.is_cuda or o.dim() != 1 or o.numel() != B or (B > 1 and o.stride(0) != stride)):
             raise RhoHipError(f"{name} must be float32 [B] on the GPU with vb's stride")
-    for name, o in (("raw_kl", raw_kl), ("raw_nll", raw_nll), ("quantile", quantile)):
+    for name, o in (("raw_kl", raw_kl), ("raw_nll", raw_nll)):
         if o is not None and (_f32c(o, name).numel() != B):
             raise RhoHipError(f"{name} must be float32 [B]")
+    _gd_quantile(quantile, B)
     ws = gd_workspace(B, n, x_start.device, workspace)
-    check(hip.lib().rho_gd_vlb_terms(ptr(x_start), ptr(x_t), ptr(model_out), ptr(_gd_t(t, B)) if t is not None else None, ptr(tab),
-                                     _gd_tab(tab), mean_type, ptr(quantile), ptr(noise), 1 if prior else 0, ptr(vb), ptr(xstart_mse),
-                                     ptr(mse), max(stride, 1), ptr(raw_kl), ptr(raw_nll), ptr(pred_xstart), ptr(ws), B, n, ptr(err_flag),
-                                     stream()), "rho_gd_vlb_terms")
+    outs = (ptr(vb), ptr(xstart_mse), ptr(mse), max(stride, 1), ptr(raw_kl), ptr(raw_nll), ptr(pred_xstart), ptr(ws), B, n, ptr(err_flag), stream())
+    if _gd_variance(var_values, var_type):
+        if prior:
+            raise RhoHipError("the prior term has no model variance: var_values does not go with prior=True")
+        ms, vs = _sample_rows(model_out, "model_out", B, n), _sample_rows(var_values, "var_values", B, n)
+        check(hip.lib().rho_gd_vlb_terms_lv(ptr(x_start), ptr(x_t), ptr(model_out), ms, ptr(var_values), vs, ptr(_gd_t(t, B)), ptr(tab),
+                                            _gd_tab(tab), mean_type, var_type, ptr(quantile), ptr(noise), *outs), "rho_gd_vlb_terms_lv")
+    else:
+        _same(x_start, ("model_out", model_out))
+        check(hip.lib().rho_gd_vlb_terms(ptr(x_start), ptr(x_t), ptr(model_out), ptr(_gd_t(t, B)) if t is not None else None, ptr(tab),
+                                         _gd_tab(tab), mean_type, ptr(quantile), ptr(noise), 1 if prior else 0, *outs), "rho_gd_vlb_terms")
     return vb
 
 
@@ -319,87 +376,6 @@ def gd_mse_per_sample_bwd(target: Tensor, out: Tensor, g: Tensor) -> Tensor:
     grad = torch.empty_like(out)
     check(hip.lib().rho_gd_mse_per_sample_bwd(ptr(target), ptr(out), ptr(g), ptr(grad), B, n, stream()), "rho_gd_mse_per_sample_bwd")
     return grad
-
-
-def _gd_rows(v: Tensor, name: str, batch: int, n: int) -> int:
-    """Per-sample stride of ``v``: a float32 GPU tensor whose sample b is the contiguous block of n elements at v[b] (a contiguous
-    tensor, or one half of a contiguous [B, 2C, ...] learned-variance output sliced along dim 1)."""
-    hip.require_gpu(v, name)
-    if v.dtype != torch.float32 or v.dim() < 1 or v.shape[0] != batch or v[0].numel() != n or not v[0].is_contiguous():
-        raise RhoHipError(f"{name} must be float32 [{batch}, ...] with {n} contiguous elements per sample, got {v.dtype} {tuple(v.shape)} "
-                          f"strides {v.stride()}")
-    return v.stride(0) if batch > 1 else n
-
-
-def abs_quantile_rows(x: Tensor, q: float, n: int, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
-    """abs_quantile over the n-element rows of a strided per-sample view (the mean half of a learned-variance output), in place."""
-    B = x.shape[0]
-    stride = _gd_rows(x, "x", B, n)
-    need = hip.lib().rho_abs_quantile_workspace_bytes(B)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty((need + 3) // 4, dtype=torch.int32, device=x.device)
-    out = torch.empty(B, dtype=torch.float32, device=x.device) if out is None else out
-    check(hip.lib().rho_abs_quantile_strided(ptr(x), B, n, stride, float(q), ptr(workspace), ptr(out), stream()), "rho_abs_quantile_strided")
-    return out
-
-
-def gd_ddim_step_strided(x_t: Tensor, model_out: Tensor, t: Tensor, tab: Tensor, mean_type: int, quantile: Optional[Tensor],
-                         grad: Optional[Tensor], noise: Optional[Tensor], eta: float, reverse: bool, sample: Tensor,
-                         pred_xstart: Optional[Tensor], err_flag: Optional[Tensor] = None) -> Tensor:
-    """gd_ddim_step with ``model_out`` any per-sample view of x_t's per-sample size (rho_gd_ddim_step_strided)."""
-    _f32c(x_t, "x_t")
-    _same(x_t, ("grad", grad), ("noise", noise), ("sample", sample), ("pred_xstart", pred_xstart))
-    B, n = x_t.shape[0], x_t.numel() // x_t.shape[0]
-    stride = _gd_rows(model_out, "model_out", B, n)
-    if quantile is not None and (_f32c(quantile, "quantile").numel() != B):
-        raise RhoHipError("quantile must be float32 [B]")
-    check(hip.lib().rho_gd_ddim_step_strided(ptr(x_t), ptr(model_out), stride, ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab), mean_type,
-                                             ptr(quantile), ptr(grad), ptr(noise), float(eta), 1 if reverse else 0, ptr(sample),
-                                             ptr(pred_xstart), B, n, ptr(err_flag), stream()), "rho_gd_ddim_step_strided")
-    return sample
-
-
-def gd_posterior_step_lv(x_t: Tensor, model_out: Tensor, var_values: Tensor, t: Tensor, tab: Tensor, mean_type: int, var_type: int,
-                         quantile: Optional[Tensor], grad: Optional[Tensor], noise: Optional[Tensor], out: Optional[Tensor],
-                         pred_xstart: Optional[Tensor], variance: Optional[Tensor] = None, log_variance: Optional[Tensor] = None,
-                         err_flag: Optional[Tensor] = None) -> Optional[Tensor]:
-    """p_mean_variance / condition_mean / p_sample with a learned variance, one pass (rho_gd_posterior_step_lv).  ``model_out`` (the
-    mean half or an x0) and ``var_values`` are per-sample views read in place."""
-    _f32c(x_t, "x_t")
-    _same(x_t, ("grad", grad), ("noise", noise), ("out", out), ("pred_xstart", pred_xstart), ("variance", variance),
-          ("log_variance", log_variance))
-    B, n = x_t.shape[0], x_t.numel() // x_t.shape[0]
-    ms, vs = _gd_rows(model_out, "model_out", B, n), _gd_rows(var_values, "var_values", B, n)
-    if quantile is not None and (_f32c(quantile, "quantile").numel() != B):
-        raise RhoHipError("quantile must be float32 [B]")
-    check(hip.lib().rho_gd_posterior_step_lv(ptr(x_t), ptr(model_out), ms, ptr(var_values), vs, ptr(_gd_t(t, B)), ptr(tab), _gd_tab(tab),
-                                             mean_type, var_type, ptr(quantile), ptr(grad), ptr(noise), ptr(out), ptr(pred_xstart),
-                                             ptr(variance), ptr(log_variance), B, n, ptr(err_flag), stream()), "rho_gd_posterior_step_lv")
-    return out
-
-
-def gd_vlb_terms_lv(x_start: Tensor, x_t: Tensor, model_out: Tensor, var_values: Tensor, t: Tensor, tab: Tensor, mean_type: int,
-                    var_type: int, quantile: Optional[Tensor], noise: Optional[Tensor], vb: Tensor, xstart_mse: Optional[Tensor] = None,
-                    mse: Optional[Tensor] = None, raw_kl: Optional[Tensor] = None, raw_nll: Optional[Tensor] = None,
-                    pred_xstart: Optional[Tensor] = None, workspace: Optional[Tensor] = None, err_flag: Optional[Tensor] = None) -> Tensor:
-    """gd_vlb_terms with a learned variance (rho_gd_vlb_terms_lv); ``model_out`` / ``var_values`` per-sample views read in place."""
-    _f32c(x_start, "x_start")
-    _same(x_start, ("x_t", x_t), ("noise", noise), ("pred_xstart", pred_xstart))
-    B, n = x_start.shape[0], x_start.numel() // x_start.shape[0]
-    ms, vs = _gd_rows(model_out, "model_out", B, n), _gd_rows(var_values, "var_values", B, n)
-    stride = vb.stride(0) if vb.dim() == 1 else 1
-    for name, o in (("vb", vb), ("xstart_mse", xstart_mse), ("mse", mse)):
-        if o is not None and (o.dtype != torch.float32 or not o.is_cuda or o.dim() != 1 or o.numel() != B or (B > 1 and o.stride(0) != stride)):
-            raise RhoHipError(f"{name} must be float32 [B] on the GPU with vb's stride")
-    for name, o in (("raw_kl", raw_kl), ("raw_nll", raw_nll), ("quantile", quantile)):
-        if o is not None and (_f32c(o, name).numel() != B):
-            raise RhoHipError(f"{name} must be float32 [B]")
-    ws = gd_workspace(B, n, x_start.device, workspace)
-    check(hip.lib().rho_gd_vlb_terms_lv(ptr(x_start), ptr(x_t), ptr(model_out), ms, ptr(var_values), vs, ptr(_gd_t(t, B)), ptr(tab),
-                                        _gd_tab(tab), mean_type, var_type, ptr(quantile), ptr(noise), ptr(vb), ptr(xstart_mse), ptr(mse),
-                                        max(stride, 1), ptr(raw_kl), ptr(raw_nll), ptr(pred_xstart), ptr(ws), B, n, ptr(err_flag),
-                                        stream()), "rho_gd_vlb_terms_lv")
-    return vb
 
 
 def _gd_hybrid_args(x_start: Tensor, x_t: Tensor, target: Tensor, model_out: Tensor):

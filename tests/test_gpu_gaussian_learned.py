@@ -179,7 +179,7 @@ def test_hybrid_loss_and_bpd_bit_reproducible_and_split_across_workgroups():
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     # the fused pass against the separate VLB entry point on the same halves (KL and NLL of the same elements)
     vbx = torch.empty(2, device=DEV)
-    ops.gd_vlb_terms_lv(x0, x_t, mo[:, :1], mo[:, 1:], t, tab, ops.GD_EPSILON, ops.GD_LEARNED_RANGE, None, None, vbx)
+    ops.gd_vlb_terms(x0, x_t, mo[:, :1], t, tab, ops.GD_EPSILON, None, None, vbx, var_values=mo[:, 1:], var_type=ops.GD_LEARNED_RANGE)
     assert torch.allclose(outs[0][0][2], vbx.cpu() * 0.02, rtol=1e-6)
     assert torch.isfinite(outs[0][1]).all()
     x = det_normal((2, 1, 4, 8, 8), "g19_bpd_x0").clamp(-1, 1).to(DEV)

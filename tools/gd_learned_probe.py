@@ -103,8 +103,8 @@ def probe(name, cfg, steps, reps, dev, train):
         "hybrid_loss_fwd": (lambda: ops.gd_hybrid_loss(x0, xt, nz, mo, t, tab, ops.GD_START_X, ops.GD_LEARNED_RANGE, 0.008, ws), 20 * n),
         "hybrid_loss_bwd": (lambda: ops.gd_hybrid_loss_bwd(x0, xt, nz, mo, t, tab, ops.GD_START_X, ops.GD_LEARNED_RANGE, 0.008, gl, None,
                                                            None), 28 * n),
-        "gd_vlb_terms_lv": (lambda: ops.gd_vlb_terms_lv(x0, xt, mo[:, :1], mo[:, 1:], t, tab, ops.GD_START_X, ops.GD_LEARNED_RANGE, None,
-                                                        None, torch.empty(B, device=dev), workspace=ws), 16 * n),
+        "gd_vlb_terms_lv": (lambda: ops.gd_vlb_terms(x0, xt, mo[:, :1], t, tab, ops.GD_START_X, None, None, torch.empty(B, device=dev),
+                                                     workspace=ws, var_values=mo[:, 1:], var_type=ops.GD_LEARNED_RANGE), 16 * n),
     }
     res["kernel_us"], res["kernel_TBps"], res["kernel_GB"] = {}, {}, {}
     for k, (fn, nbytes) in kern.items():
