@@ -100,112 +100,123 @@ extern "C" int rho_q_sample(const float* x0, const float* eps, float* x_t, const
     return 0;
 }
 
-// ----------------------------------------------------------------------------- p_sample_step
+// ----------------------------------------------------------------------------- the element walk of the reverse-process updates
+// rho_p_sample_step[_cfg], rho_p_sample_step_spaced[_pred] and rho_dpmpp_2m_step stream the same operands and differ in the
+// per-element expression (an update functor Op) and in how the kernel loads its coefficient row.  step_walk owns the rest:
+//   * the grid-stride 16-byte body (vec, granted by step_launch) and the scalar loop behind it - the tail of the body, or every
+//     element where vec == 0.  Both call op(), a written-out contraction, so all forms give the same bits;
+//   * GUIDED: x and ph hold [2, n] - row 0 is x_t / the conditional prediction, row 1 its copy (the 2B batch the engine reads) / the
+//     null-condition prediction.  p = p_u + s * (p_c - p_u) (cfg_mix: the difference, one fma) enters op, the result is stored to
+//     BOTH rows of x: no guided prediction and no duplicate of x_t in between;
+//   * the side operand, one row of n also under guidance: read only under read_side (z where noise enters, hist where the row is
+//     second order; else op sees 0 and the buffer may be NULL or uninitialised) and written where Op::WRITES_SIDE (hist).  One
+//     pointer serves the read and the write of an element, so it alone carries __restrict__.
+// Every launch has STEP_BLOCK threads per block (step_launch), and the walk counts with the constant: blockDim.x read inside a
+// __device__ function compiles to a vector load from the dispatch packet in front of the first element.
+constexpr int STEP_BLOCK = 256;
+__device__ __forceinline__ float cfg_mix(float s, float ec, float eu) { return __fmaf_rn(s, ec - eu, eu); }
+template <bool GUIDED, class Op, class Side>
+__device__ __forceinline__ void step_walk(const Op& op, float* __restrict__ x, const float* __restrict__ ph, Side* __restrict__ side,
+                                          bool read_side, float s, int64_t n, int vec) {
+    const int64_t stride = (int64_t)gridDim.x * STEP_BLOCK;
+    const int64_t tid = (int64_t)blockIdx.x * STEP_BLOCK + threadIdx.x;
+    int64_t done = 0;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        float4* xa = (float4*)x;
+        float4* xb = (float4*)(x + n);
+        const float4* pa = (const float4*)ph;
+        const float4* pb = (const float4*)(ph + n);
+        for (int64_t i = tid; i < n4; i += stride) {
+            float4 a = xa[i];
+            float4 p = pa[i];
+            if (GUIDED) {
+                const float4 pu = pb[i];
+                p.x = cfg_mix(s, p.x, pu.x), p.y = cfg_mix(s, p.y, pu.y), p.z = cfg_mix(s, p.z, pu.z), p.w = cfg_mix(s, p.w, pu.w);
+            }
+            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (read_side) h = ((const float4*)side)[i];
+            float4 o;
+            a.x = op(a.x, p.x, h.x, o.x);
+            a.y = op(a.y, p.y, h.y, o.y);
+            a.z = op(a.z, p.z, h.z, o.z);
+            a.w = op(a.w, p.w, h.w, o.w);
+            if constexpr (Op::WRITES_SIDE) ((float4*)side)[i] = o;
+            xa[i] = a;
+            if (GUIDED) xb[i] = a;
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + tid; i < n; i += stride) {
+        const float xi = x[i];
+        const float p = GUIDED ? cfg_mix(s, ph[i], ph[n + i]) : ph[i];
+        const float h = read_side ? side[i] : 0.0f;
+        float o;
+        const float r = op(xi, p, h, o);
+        if constexpr (Op::WRITES_SIDE) side[i] = o;
+        x[i] = r;
+        if (GUIDED) x[n + i] = r;
+    }
+}
+
+// The 16-byte form needs 16-byte aligned bases and, under guidance, n % 4 == 0 (row 1 starts n elements behind row 0); the plain form
+// takes any n and finishes with the scalar tail.  Any other n or pointer takes the scalar loop alone, one thread per element.
+struct StepLaunch {
+    int vec;
+    dim3 grid, block;
+};
+static StepLaunch step_launch(const void* x, const void* pred, const void* side, int64_t n, int guided) {
+    const bool aligned = (((uintptr_t)x | (uintptr_t)pred | (uintptr_t)side) & 15) == 0;
+    const int vec = (aligned && (!guided || n % 4 == 0)) ? 1 : 0;
+    return {vec, dim3(grid_for(vec ? (n + 3) / 4 : n, STEP_BLOCK)), dim3(STEP_BLOCK)};
+}
+
+// ----------------------------------------------------------------------------- p_sample_step, plain and with classifier-free guidance
 // ddpm.py:210-218.  coef row = {1/sqrt(alpha), beta/sqrt(1-abar), 0.8*sqrt(beta)}; t read on device so
 // that one captured graph serves every step; t == 0 => no update (q3), t <= 1 => z ignored.
-// One written-out contraction for the 16-byte body, its tail and the 4-byte-aligned fallback: all three round alike.
-__device__ __forceinline__ float p_update(float c0, float c1, float c2, float x, float e, float z) {
-    return fminf(fmaxf(__fmaf_rn(c0, __fmaf_rn(-c1, e, x), c2 * z), -1.0f), 1.0f);
-}
-__global__ __launch_bounds__(256) void k_p_sample(float* __restrict__ x, const float* __restrict__ eh,
-                                                  const float* __restrict__ z, const float* __restrict__ coef,
-                                                  const int32_t* __restrict__ t_dev, int64_t n) {
+// rho_p_sample_step_cfg: x2 / eps2 = [2, n] as step_walk's GUIDED form takes them; 4n floats read (3n when z is ignored), 2n written.
+struct PSampleOp {
+    static constexpr bool WRITES_SIDE = false;
+    float c0, c1, c2;
+    __device__ __forceinline__ float operator()(float x, float e, float z, float&) const {
+        return fminf(fmaxf(__fmaf_rn(c0, __fmaf_rn(-c1, e, x), c2 * z), -1.0f), 1.0f);
+    }
+};
+template <bool GUIDED>
+__device__ __forceinline__ void p_sample_rows(float* __restrict__ x, const float* __restrict__ eh, const float* __restrict__ z,
+                                              const float* __restrict__ coef, const int32_t* __restrict__ t_dev, float s, int64_t n,
+                                              int vec) {
     const int t = *t_dev;
     if (t <= 0) return;
-    const float c0 = coef[3 * t + 0], c1 = coef[3 * t + 1], c2 = (t > 1 && z != nullptr) ? coef[3 * t + 2] : 0.0f;
-    const int64_t n4 = n >> 2;
-    const bool vec = ((((uintptr_t)x | (uintptr_t)eh | (uintptr_t)z) & 15) == 0);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (vec) {
-        float4* x4 = (float4*)x;
-        const float4* e4 = (const float4*)eh;
-        const float4* z4 = (const float4*)z;
-        for (int64_t i = tid; i < n4; i += stride) {
-            float4 a = x4[i];
-            const float4 e = e4[i];
-            float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c2 != 0.0f) zz = z4[i];
-            a.x = p_update(c0, c1, c2, a.x, e.x, zz.x);
-            a.y = p_update(c0, c1, c2, a.y, e.y, zz.y);
-            a.z = p_update(c0, c1, c2, a.z, e.z, zz.z);
-            a.w = p_update(c0, c1, c2, a.w, e.w, zz.w);
-            x4[i] = a;
-        }
-        for (int64_t i = (n4 << 2) + tid; i < n; i += stride) {
-            const float zz = (c2 != 0.0f) ? z[i] : 0.0f;
-            x[i] = p_update(c0, c1, c2, x[i], eh[i], zz);
-        }
-    } else {
-        for (int64_t i = tid; i < n; i += stride) {
-            const float zz = (c2 != 0.0f) ? z[i] : 0.0f;
-            x[i] = p_update(c0, c1, c2, x[i], eh[i], zz);
-        }
-    }
+    PSampleOp c;
+    c.c0 = coef[3 * t + 0], c.c1 = coef[3 * t + 1], c.c2 = (t > 1 && z != nullptr) ? coef[3 * t + 2] : 0.0f;
+    step_walk<GUIDED>(c, x, eh, z, c.c2 != 0.0f, s, n, vec);
+}
+__global__ __launch_bounds__(STEP_BLOCK) void k_p_sample(float* __restrict__ x, const float* __restrict__ eh,
+                                                  const float* __restrict__ z, const float* __restrict__ coef,
+                                                  const int32_t* __restrict__ t_dev, int64_t n, int vec) {
+    p_sample_rows<false>(x, eh, z, coef, t_dev, 0.0f, n, vec);
+}
+__global__ __launch_bounds__(STEP_BLOCK) void k_p_sample_cfg(float* __restrict__ x2, const float* __restrict__ e2,
+                                                      const float* __restrict__ z, const float* __restrict__ coef,
+                                                      const int32_t* __restrict__ t_dev, float s, int64_t n, int vec) {
+    p_sample_rows<true>(x2, e2, z, coef, t_dev, s, n, vec);
 }
 
 extern "C" int rho_p_sample_step(float* x, const float* eps_hat, const float* z, const float* coef_table,
                                  const int32_t* t_dev, int64_t n, void* stream) {
     if (!x || !eps_hat || !coef_table || !t_dev || n <= 0) return RHO_E_ARG;
-    hipLaunchKernelGGL(k_p_sample, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, as_stream(stream), x, eps_hat, z, coef_table,
-                       t_dev, n);
+    const StepLaunch l = step_launch(x, eps_hat, z, n, 0);
+    hipLaunchKernelGGL(k_p_sample, l.grid, l.block, 0, as_stream(stream), x, eps_hat, z, coef_table, t_dev, n, l.vec);
     RHO_LAUNCH_CHECK();
     return 0;
-}
-
-// ----------------------------------------------------------------------------- p_sample_step, classifier-free guidance
-// x2 = [2, n]: row 0 is x_t, row 1 its copy (the 2B batch the engine reads); eps2 = [2, n]: the conditional and the null-condition
-// prediction of that batch.  g = e_u + scale * (e_c - e_u), then p_update on (x, g, z) as above, stored to BOTH rows: 4n floats
-// read (3n when z is ignored), 2n written, no guided prediction and no duplicate of x_t in between.
-// One written-out contraction again: the difference, one fma, then p_update - the 16-byte body and the scalar form round alike.
-__device__ __forceinline__ float p_update_cfg(float c0, float c1, float c2, float s, float x, float ec, float eu, float z) {
-    return p_update(c0, c1, c2, x, __fmaf_rn(s, ec - eu, eu), z);
-}
-// Row 1 starts n elements behind row 0, so the 16-byte form needs n % 4 == 0 besides the aligned bases (the caller decides: vec);
-// it then covers every element and has no tail of its own.  Any other n or pointer takes the scalar loop.
-__global__ __launch_bounds__(256) void k_p_sample_cfg(float* __restrict__ x2, const float* __restrict__ e2,
-                                                      const float* __restrict__ z, const float* __restrict__ coef,
-                                                      const int32_t* __restrict__ t_dev, float s, int64_t n, int vec) {
-    const int t = *t_dev;
-    if (t <= 0) return;
-    const float c0 = coef[3 * t + 0], c1 = coef[3 * t + 1], c2 = (t > 1 && z != nullptr) ? coef[3 * t + 2] : 0.0f;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (vec) {
-        const int64_t n4 = n >> 2;
-        float4* xa = (float4*)x2;
-        float4* xb = (float4*)(x2 + n);
-        const float4* ec4 = (const float4*)e2;
-        const float4* eu4 = (const float4*)(e2 + n);
-        const float4* z4 = (const float4*)z;
-        for (int64_t i = tid; i < n4; i += stride) {
-            float4 a = xa[i];
-            const float4 ec = ec4[i], eu = eu4[i];
-            float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c2 != 0.0f) zz = z4[i];
-            a.x = p_update_cfg(c0, c1, c2, s, a.x, ec.x, eu.x, zz.x);
-            a.y = p_update_cfg(c0, c1, c2, s, a.y, ec.y, eu.y, zz.y);
-            a.z = p_update_cfg(c0, c1, c2, s, a.z, ec.z, eu.z, zz.z);
-            a.w = p_update_cfg(c0, c1, c2, s, a.w, ec.w, eu.w, zz.w);
-            xa[i] = a;
-            xb[i] = a;
-        }
-    } else {
-        for (int64_t i = tid; i < n; i += stride) {
-            const float zz = (c2 != 0.0f) ? z[i] : 0.0f;
-            const float r = p_update_cfg(c0, c1, c2, s, x2[i], e2[i], e2[n + i], zz);
-            x2[i] = r;
-            x2[n + i] = r;
-        }
-    }
 }
 
 extern "C" int rho_p_sample_step_cfg(float* x2, const float* eps2, const float* z, const float* coef_table, const int32_t* t_dev,
                                      float scale, int64_t n, void* stream) {
     if (!x2 || !eps2 || !coef_table || !t_dev || n <= 0) return RHO_E_ARG;
-    const int vec = (n % 4 == 0 && (((uintptr_t)x2 | (uintptr_t)eps2 | (uintptr_t)z) & 15) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(k_p_sample_cfg, dim3(grid_for(vec ? n / 4 : n, 256)), dim3(256), 0, as_stream(stream), x2, eps2, z,
-                       coef_table, t_dev, scale, n, vec);
+    const StepLaunch l = step_launch(x2, eps2, z, n, 1);
+    hipLaunchKernelGGL(k_p_sample_cfg, l.grid, l.block, 0, as_stream(stream), x2, eps2, z, coef_table, t_dev, scale, n, l.vec);
     RHO_LAUNCH_CHECK();
     return 0;
 }
@@ -227,26 +238,24 @@ extern "C" int rho_step_advance(int32_t* t_dev, uint64_t* offset_dev, uint64_t d
 // Few-step sampling (DDIM with eta; the reference's DDPM has no such sampler).  rows = float32 [S, 8], row k for t = tau_k:
 // {sqrt(1/ab), sqrt(1/ab - 1), sqrt(ab), 1/sqrt(1 - ab), sqrt(ab_prev), sigma, sqrt(1 - ab_prev - sigma^2), 0}; k read on the device
 // so that one captured graph serves every step, k outside [0, S) => nothing is written.  Noise enters iff z != NULL and the row's
-// sigma != 0, else z is not read.  One written-out contraction for the 16-byte body, its tail and the scalar loop:
+// sigma != 0, else z is not read.  The guided [2, n] operands and the 16-byte form are step_walk's.
 //   x0 = fma(c_recip, x, -(c_recipm1 * e));   clip: x0 = clamp(x0, -1, 1), ep = fma(-sqrt_ab, x0, x) * inv_sqrt_1mab;   else ep = e
 //   r  = fma(sqrt_abp, x0, fma(coef_eps, ep, sigma * z))
 // and r = sqrt_abp * x0 where the row has coef_eps == 0 and sigma == 0 (row 0 always; ep is not formed: at alpha_bar == 1 it is 0/0).
-struct SpacedRow {
+struct SpacedOp {
+    static constexpr bool WRITES_SIDE = false;
     float c_recip, c_recipm1, sqrt_ab, inv_sqrt_1mab, sqrt_abp, sigma, coef_eps;
     int clip, x0_only;
+    __device__ __forceinline__ float operator()(float x, float e, float z, float&) const {
+        float x0 = __fmaf_rn(c_recip, x, -(c_recipm1 * e));
+        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        if (x0_only) return sqrt_abp * x0;
+        const float ep = clip ? __fmaf_rn(-sqrt_ab, x0, x) * inv_sqrt_1mab : e;
+        return __fmaf_rn(sqrt_abp, x0, __fmaf_rn(coef_eps, ep, sigma * z));
+    }
 };
-__device__ __forceinline__ float spaced_update(const SpacedRow& c, float x, float e, float z) {
-    float x0 = __fmaf_rn(c.c_recip, x, -(c.c_recipm1 * e));
-    if (c.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    if (c.x0_only) return c.sqrt_abp * x0;
-    const float ep = c.clip ? __fmaf_rn(-c.sqrt_ab, x0, x) * c.inv_sqrt_1mab : e;
-    return __fmaf_rn(c.sqrt_abp, x0, __fmaf_rn(c.coef_eps, ep, c.sigma * z));
-}
-__device__ __forceinline__ float cfg_mix(float s, float ec, float eu) { return __fmaf_rn(s, ec - eu, eu); }
-// GUIDED: x and eh hold [2, n] as in k_p_sample_cfg - row 1 starts n elements behind row 0, so the caller grants the 16-byte form
-// (vec) only for n % 4 == 0 there; the plain form takes any n with aligned bases and finishes with a scalar tail.
 template <bool GUIDED>
-__global__ __launch_bounds__(256) void k_p_sample_spaced(float* __restrict__ x, const float* __restrict__ eh,
+__global__ __launch_bounds__(STEP_BLOCK) void k_p_sample_spaced(float* __restrict__ x, const float* __restrict__ eh,
                                                          const float* __restrict__ z, const float* __restrict__ rows,
                                                          const int32_t* __restrict__ k_dev, int32_t S, float s, int64_t n, int clip,
                                                          int vec) {
@@ -255,62 +264,27 @@ __global__ __launch_bounds__(256) void k_p_sample_spaced(float* __restrict__ x, 
     const float* row = rows + 8 * (int64_t)k;
     // the whole row up front, unconditionally: one scalar load behind k instead of a chain of dependent ones behind each test
     const float r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3], r4 = row[4], r5 = row[5], r6 = row[6];
-    SpacedRow c;
+    SpacedOp c;
     c.c_recip = r0, c.c_recipm1 = r1, c.sqrt_ab = r2, c.inv_sqrt_1mab = r3, c.sqrt_abp = r4;
     c.coef_eps = r6;
     c.clip = clip;
     c.x0_only = ((r6 == 0.0f) & (r5 == 0.0f)) ? 1 : 0;
     const bool noisy = (z != nullptr) & (r5 != 0.0f);
     c.sigma = noisy ? r5 : 0.0f;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t done = 0;
-    if (vec) {
-        const int64_t n4 = n >> 2;
-        float4* xa = (float4*)x;
-        float4* xb = (float4*)(x + n);
-        const float4* ea = (const float4*)eh;
-        const float4* eb = (const float4*)(eh + n);
-        const float4* z4 = (const float4*)z;
-        for (int64_t i = tid; i < n4; i += stride) {
-            float4 a = xa[i];
-            float4 e = ea[i];
-            if (GUIDED) {
-                const float4 eu = eb[i];
-                e.x = cfg_mix(s, e.x, eu.x), e.y = cfg_mix(s, e.y, eu.y), e.z = cfg_mix(s, e.z, eu.z), e.w = cfg_mix(s, e.w, eu.w);
-            }
-            float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (noisy) zz = z4[i];
-            a.x = spaced_update(c, a.x, e.x, zz.x);
-            a.y = spaced_update(c, a.y, e.y, zz.y);
-            a.z = spaced_update(c, a.z, e.z, zz.z);
-            a.w = spaced_update(c, a.w, e.w, zz.w);
-            xa[i] = a;
-            if (GUIDED) xb[i] = a;
-        }
-        done = n4 << 2;
-    }
-    for (int64_t i = done + tid; i < n; i += stride) {
-        const float zz = noisy ? z[i] : 0.0f;
-        const float e = GUIDED ? cfg_mix(s, eh[i], eh[n + i]) : eh[i];
-        const float r = spaced_update(c, x[i], e, zz);
-        x[i] = r;
-        if (GUIDED) x[n + i] = r;
-    }
+    step_walk<GUIDED>(c, x, eh, z, noisy, s, n, vec);
 }
 
 extern "C" int rho_p_sample_step_spaced(float* x, const float* eps_hat, const float* z, const float* rows, const int32_t* k_dev,
                                         int32_t S, int64_t n, int guided, float scale, int clip, void* stream) {
     if (!x || !eps_hat || !rows || !k_dev || S <= 0 || n <= 0) return RHO_E_ARG;
-    const bool aligned = (((uintptr_t)x | (uintptr_t)eps_hat | (uintptr_t)z) & 15) == 0;
-    const int vec = (aligned && (!guided || n % 4 == 0)) ? 1 : 0;
-    const dim3 grid(grid_for(vec ? (n + 3) / 4 : n, 256)), block(256);
+    const StepLaunch l = step_launch(x, eps_hat, z, n, guided);
+    const dim3 grid = l.grid, block = l.block;
     if (guided)
         hipLaunchKernelGGL(k_p_sample_spaced<true>, grid, block, 0, as_stream(stream), x, eps_hat, z, rows, k_dev, S, scale, n,
-                           clip ? 1 : 0, vec);
+                           clip ? 1 : 0, l.vec);
     else
         hipLaunchKernelGGL(k_p_sample_spaced<false>, grid, block, 0, as_stream(stream), x, eps_hat, z, rows, k_dev, S, 0.0f, n,
-                           clip ? 1 : 0, vec);
+                           clip ? 1 : 0, l.vec);
     RHO_LAUNCH_CHECK();
     return 0;
 }
@@ -336,27 +310,27 @@ extern "C" int rho_spaced_advance(int32_t* k_dev, int32_t* t_dev, const int32_t*
 // rho_p_sample_step_spaced for a backbone that predicts v = sqrt(ab) eps - sqrt(1 - ab) x0 (RHO_PRED_V) or x0 itself
 // (RHO_PRED_SAMPLE).  rows = float32 [S, 8], row k for t = tau_k: {sqrt(ab), sqrt(1 - ab), 1/sqrt(1 - ab) (0 where 1 - ab == 0),
 // sqrt(ab_prev), sigma, sqrt(1 - ab_prev - sigma^2), 0, 0}.  Nothing is divided by sqrt(ab), so a row with ab == 0 is a row like any
-// other.  k, z, clip, the guided [2, n] operands and the 16-byte form follow k_p_sample_spaced; guidance mixes the predictions
-// (both conversions below are affine in p at fixed x, so this is the mix of the two noise estimates).  One written-out contraction
-// for the 16-byte body, its tail and the scalar loop:
+// other.  k, z and clip follow k_p_sample_spaced; guidance mixes the predictions (both conversions below are affine in p at fixed x,
+// so this is the mix of the two noise estimates).
 //   v: x0 = fma(sqrt_ab, x, -(sqrt_1mab * p))     sample: x0 = p                    clip: x0 = clamp(x0, -1, 1)
 //   ep = fma(-sqrt_ab, x0, x) * inv_sqrt_1mab;     v without clip: ep = fma(sqrt_1mab, x, sqrt_ab * p)
 //   r  = fma(sqrt_abp, x0, fma(coef_eps, ep, sigma * z))
 // and r = sqrt_abp * x0, ep not formed, where the row has coef_eps == 0 and sigma == 0 (row 0 always).
-struct PredRow {
+template <bool V>
+struct PredOp {
+    static constexpr bool WRITES_SIDE = false;
     float sqrt_ab, sqrt_1mab, inv_sqrt_1mab, sqrt_abp, sigma, coef_eps;
     int clip, x0_only;
+    __device__ __forceinline__ float operator()(float x, float p, float z, float&) const {
+        float x0 = V ? __fmaf_rn(sqrt_ab, x, -(sqrt_1mab * p)) : p;
+        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        if (x0_only) return sqrt_abp * x0;
+        const float ep = (V && !clip) ? __fmaf_rn(sqrt_1mab, x, sqrt_ab * p) : __fmaf_rn(-sqrt_ab, x0, x) * inv_sqrt_1mab;
+        return __fmaf_rn(sqrt_abp, x0, __fmaf_rn(coef_eps, ep, sigma * z));
+    }
 };
-template <bool V>
-__device__ __forceinline__ float pred_update(const PredRow& c, float x, float p, float z) {
-    float x0 = V ? __fmaf_rn(c.sqrt_ab, x, -(c.sqrt_1mab * p)) : p;
-    if (c.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    if (c.x0_only) return c.sqrt_abp * x0;
-    const float ep = (V && !c.clip) ? __fmaf_rn(c.sqrt_1mab, x, c.sqrt_ab * p) : __fmaf_rn(-c.sqrt_ab, x0, x) * c.inv_sqrt_1mab;
-    return __fmaf_rn(c.sqrt_abp, x0, __fmaf_rn(c.coef_eps, ep, c.sigma * z));
-}
 template <bool GUIDED, bool V>
-__global__ __launch_bounds__(256) void k_p_sample_spaced_pred(float* __restrict__ x, const float* __restrict__ ph,
+__global__ __launch_bounds__(STEP_BLOCK) void k_p_sample_spaced_pred(float* __restrict__ x, const float* __restrict__ ph,
                                                               const float* __restrict__ z, const float* __restrict__ rows,
                                                               const int32_t* __restrict__ k_dev, int32_t S, float s, int64_t n,
                                                               int clip, int vec) {
@@ -364,58 +338,23 @@ __global__ __launch_bounds__(256) void k_p_sample_spaced_pred(float* __restrict_
     if (k < 0 || k >= S) return;
     const float* row = rows + 8 * (int64_t)k;
     const float r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3], r4 = row[4], r5 = row[5];
-    PredRow c;
+    PredOp<V> c;
     c.sqrt_ab = r0, c.sqrt_1mab = r1, c.inv_sqrt_1mab = r2, c.sqrt_abp = r3;
     c.coef_eps = r5;
     c.clip = clip;
     c.x0_only = ((r5 == 0.0f) & (r4 == 0.0f)) ? 1 : 0;
     const bool noisy = (z != nullptr) & (r4 != 0.0f);
     c.sigma = noisy ? r4 : 0.0f;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t done = 0;
-    if (vec) {
-        const int64_t n4 = n >> 2;
-        float4* xa = (float4*)x;
-        float4* xb = (float4*)(x + n);
-        const float4* pa = (const float4*)ph;
-        const float4* pb = (const float4*)(ph + n);
-        const float4* z4 = (const float4*)z;
-        for (int64_t i = tid; i < n4; i += stride) {
-            float4 a = xa[i];
-            float4 p = pa[i];
-            if (GUIDED) {
-                const float4 pu = pb[i];
-                p.x = cfg_mix(s, p.x, pu.x), p.y = cfg_mix(s, p.y, pu.y), p.z = cfg_mix(s, p.z, pu.z), p.w = cfg_mix(s, p.w, pu.w);
-            }
-            float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (noisy) zz = z4[i];
-            a.x = pred_update<V>(c, a.x, p.x, zz.x);
-            a.y = pred_update<V>(c, a.y, p.y, zz.y);
-            a.z = pred_update<V>(c, a.z, p.z, zz.z);
-            a.w = pred_update<V>(c, a.w, p.w, zz.w);
-            xa[i] = a;
-            if (GUIDED) xb[i] = a;
-        }
-        done = n4 << 2;
-    }
-    for (int64_t i = done + tid; i < n; i += stride) {
-        const float zz = noisy ? z[i] : 0.0f;
-        const float p = GUIDED ? cfg_mix(s, ph[i], ph[n + i]) : ph[i];
-        const float r = pred_update<V>(c, x[i], p, zz);
-        x[i] = r;
-        if (GUIDED) x[n + i] = r;
-    }
+    step_walk<GUIDED>(c, x, ph, z, noisy, s, n, vec);
 }
 
 extern "C" int rho_p_sample_step_spaced_pred(float* x, const float* pred, const float* z, const float* rows, const int32_t* k_dev,
                                              int32_t S, int64_t n, int guided, float scale, int clip, int pred_type, void* stream) {
     if (!x || !pred || !rows || !k_dev || S <= 0 || n <= 0) return RHO_E_ARG;
     if (pred_type != RHO_PRED_V && pred_type != RHO_PRED_SAMPLE) return RHO_E_ARG;     // epsilon: rho_p_sample_step_spaced
-    const bool aligned = (((uintptr_t)x | (uintptr_t)pred | (uintptr_t)z) & 15) == 0;
-    const int vec = (aligned && (!guided || n % 4 == 0)) ? 1 : 0;
-    const dim3 grid(grid_for(vec ? (n + 3) / 4 : n, 256)), block(256);
-    const int cl = clip ? 1 : 0;
+    const StepLaunch l = step_launch(x, pred, z, n, guided);
+    const dim3 grid = l.grid, block = l.block;
+    const int cl = clip ? 1 : 0, vec = l.vec;
     const float s = guided ? scale : 0.0f;
     hipStream_t st = as_stream(stream);
     if (guided && pred_type == RHO_PRED_V)
@@ -433,77 +372,30 @@ extern "C" int rho_p_sample_step_spaced_pred(float* x, const float* pred, const 
 // ----------------------------------------------------------------------------- DPM-Solver++(2M) on the spaced walk
 // The second-order multistep update (Lu et al. 2022; the reference has no few-step sampler) in place of the DDIM one, for all three
 // prediction types.  rows = float32 [S, 8], row k for the step from tau_k: {a_x, a_p, c_x, c_d0, c_d1, 0, 0, 0}
-// (dpmpp_2m_coefficients).  hist float32 [n], one row also under guidance: the x0 estimate the step before left behind, read only
+// (dpmpp_2m_coefficients).  hist float32 [n], step_walk's side operand: the x0 estimate the step before left behind, read only
 // where c_d1 != 0 (the first step of a walk has none: the buffer may be uninitialised) and always overwritten with this step's.
-// k, clip, the guided [2, n] operands and the 16-byte form follow k_p_sample_spaced; no noise enters.  One written-out contraction
-// for the 16-byte body, its tail and the scalar loop:
+// k and clip follow k_p_sample_spaced; no noise enters.
 //   x0 = fma(a_x, x, -(a_p * p))   (sample: x0 = p)        clip: x0 = clamp(x0, -1, 1)
 //   c_d1 != 0: r = fma(c_x, x, fma(c_d0, x0, c_d1 * hist))     c_d1 == 0: r = fma(c_x, x, c_d0 * x0), or c_d0 * x0 where c_x == 0
 struct Dpm2mRow {
     float a_x, a_p, c_x, c_d0, c_d1;
     int clip;
 };
-template <int TYPE>
-__device__ __forceinline__ float dpm2m_x0(const Dpm2mRow& c, float x, float p) {
-    float x0 = TYPE == RHO_PRED_SAMPLE ? p : __fmaf_rn(c.a_x, x, -(c.a_p * p));
-    if (c.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    return x0;
-}
 // ORDER 2: the row has c_d1 != 0; ORDER 1: c_d1 == 0, h is not used; ORDER 0: c_d1 == 0 and c_x == 0, the x0 estimate scaled
-template <int ORDER>
-__device__ __forceinline__ float dpm2m_update(const Dpm2mRow& c, float x, float x0, float h) {
-    if (ORDER == 2) return __fmaf_rn(c.c_x, x, __fmaf_rn(c.c_d0, x0, c.c_d1 * h));
-    if (ORDER == 1) return __fmaf_rn(c.c_x, x, c.c_d0 * x0);
-    return c.c_d0 * x0;
-}
-template <bool GUIDED, int TYPE, int ORDER>
-__device__ __forceinline__ void dpm2m_walk(const Dpm2mRow& c, float* __restrict__ x, const float* __restrict__ ph,
-                                           float* __restrict__ hist, float s, int64_t n, int vec) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t done = 0;
-    if (vec) {
-        const int64_t n4 = n >> 2;
-        float4* xa = (float4*)x;
-        float4* xb = (float4*)(x + n);
-        const float4* pa = (const float4*)ph;
-        const float4* pb = (const float4*)(ph + n);
-        float4* h4 = (float4*)hist;
-        for (int64_t i = tid; i < n4; i += stride) {
-            float4 a = xa[i];
-            float4 p = pa[i];
-            if (GUIDED) {
-                const float4 pu = pb[i];
-                p.x = cfg_mix(s, p.x, pu.x), p.y = cfg_mix(s, p.y, pu.y), p.z = cfg_mix(s, p.z, pu.z), p.w = cfg_mix(s, p.w, pu.w);
-            }
-            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ORDER == 2) h = h4[i];
-            float4 e;
-            e.x = dpm2m_x0<TYPE>(c, a.x, p.x), e.y = dpm2m_x0<TYPE>(c, a.y, p.y);
-            e.z = dpm2m_x0<TYPE>(c, a.z, p.z), e.w = dpm2m_x0<TYPE>(c, a.w, p.w);
-            a.x = dpm2m_update<ORDER>(c, a.x, e.x, h.x);
-            a.y = dpm2m_update<ORDER>(c, a.y, e.y, h.y);
-            a.z = dpm2m_update<ORDER>(c, a.z, e.z, h.z);
-            a.w = dpm2m_update<ORDER>(c, a.w, e.w, h.w);
-            h4[i] = e;
-            xa[i] = a;
-            if (GUIDED) xb[i] = a;
-        }
-        done = n4 << 2;
+template <int TYPE, int ORDER>
+struct Dpm2mOp : Dpm2mRow {
+    static constexpr bool WRITES_SIDE = true;
+    __device__ __forceinline__ float operator()(float x, float p, float h, float& e) const {
+        float x0 = TYPE == RHO_PRED_SAMPLE ? p : __fmaf_rn(a_x, x, -(a_p * p));
+        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        e = x0;
+        if (ORDER == 2) return __fmaf_rn(c_x, x, __fmaf_rn(c_d0, x0, c_d1 * h));
+        if (ORDER == 1) return __fmaf_rn(c_x, x, c_d0 * x0);
+        return c_d0 * x0;
     }
-    for (int64_t i = done + tid; i < n; i += stride) {
-        const float xi = x[i];
-        const float p = GUIDED ? cfg_mix(s, ph[i], ph[n + i]) : ph[i];
-        const float h = ORDER == 2 ? hist[i] : 0.0f;
-        const float e = dpm2m_x0<TYPE>(c, xi, p);
-        const float r = dpm2m_update<ORDER>(c, xi, e, h);
-        hist[i] = e;
-        x[i] = r;
-        if (GUIDED) x[n + i] = r;
-    }
-}
+};
 template <bool GUIDED, int TYPE>
-__global__ __launch_bounds__(256) void k_dpmpp_2m_step(float* __restrict__ x, const float* __restrict__ ph, float* __restrict__ hist,
+__global__ __launch_bounds__(STEP_BLOCK) void k_dpmpp_2m_step(float* __restrict__ x, const float* __restrict__ ph, float* __restrict__ hist,
                                                        const float* __restrict__ rows, const int32_t* __restrict__ k_dev, int32_t S,
                                                        float s, int64_t n, int clip, int vec) {
     const int k = *k_dev;
@@ -516,11 +408,11 @@ __global__ __launch_bounds__(256) void k_dpmpp_2m_step(float* __restrict__ x, co
     c.clip = clip;
     // uniform: the row is the same for every lane of the launch
     if (r4 != 0.0f)
-        dpm2m_walk<GUIDED, TYPE, 2>(c, x, ph, hist, s, n, vec);
+        step_walk<GUIDED>(Dpm2mOp<TYPE, 2>{c}, x, ph, hist, true, s, n, vec);
     else if (r2 != 0.0f)
-        dpm2m_walk<GUIDED, TYPE, 1>(c, x, ph, hist, s, n, vec);
+        step_walk<GUIDED>(Dpm2mOp<TYPE, 1>{c}, x, ph, hist, false, s, n, vec);
     else
-        dpm2m_walk<GUIDED, TYPE, 0>(c, x, ph, hist, s, n, vec);
+        step_walk<GUIDED>(Dpm2mOp<TYPE, 0>{c}, x, ph, hist, false, s, n, vec);
 }
 
 template <bool GUIDED>
@@ -538,10 +430,9 @@ extern "C" int rho_dpmpp_2m_step(float* x, const float* pred, float* hist, const
                                  int64_t n, int guided, float scale, int clip, int pred_type, void* stream) {
     if (!x || !pred || !hist || !rows || !k_dev || S <= 0 || n <= 0) return RHO_E_ARG;
     if (pred_type != RHO_PRED_EPSILON && pred_type != RHO_PRED_V && pred_type != RHO_PRED_SAMPLE) return RHO_E_ARG;
-    const bool aligned = (((uintptr_t)x | (uintptr_t)pred | (uintptr_t)hist) & 15) == 0;
-    const int vec = (aligned && (!guided || n % 4 == 0)) ? 1 : 0;
-    const dim3 grid(grid_for(vec ? (n + 3) / 4 : n, 256)), block(256);
-    const int cl = clip ? 1 : 0;
+    const StepLaunch l = step_launch(x, pred, hist, n, guided);
+    const dim3 grid = l.grid, block = l.block;
+    const int cl = clip ? 1 : 0, vec = l.vec;
     hipStream_t st = as_stream(stream);
     if (guided)
         dpmpp_2m_launch<true>(pred_type, grid, block, st, x, pred, hist, rows, k_dev, S, scale, n, cl, vec);

@@ -239,75 +239,88 @@ class DDPM(AbstractDiffusionPipeline):
                 ops.p_sample_step_cfg(x_all, pred, z, tables["coef"], t_dev, scale)
         if spaced is not None:
             return self._reverse_process_spaced(x_all, x_t, cc, engine, scale, spaced, bool(clip_denoised), t_dev, buf)
+        return self._run_walk(x_all, x_t, cc, engine, t_dev, buf, denoise_steps, host_t=lambda t: t, z_from=2, update=update,
+                              advance=lambda off_dev, delta: ops.step_advance(t_dev, off_dev, delta), state=(t_dev,),
+                              is_checkpoint=lambda t: t % steps_per_ckpt == 0)
+
+    def _run_walk(self, x_all, x_t, cc, engine, t_dev, buf, steps, host_t, z_from, update, advance, state, is_checkpoint) -> dict:
+        """The loop of every reverse process over the step index i = steps-1 .. 0 (t itself in the full loop, k in the spaced walk):
+        draw z where i >= ``z_from`` (None: never; before the backbone call, :196-199), evaluate the backbone at the timestep in
+        ``t_dev``, ``update(pred, z)``, copy x_t to the next row of ``buf`` where ``is_checkpoint(i)``, ``advance(offset_dev, delta)``.
+        ``x_all`` is what the backbone reads and ``update`` writes - ``x_t`` itself, or under guidance the doubled batch whose first
+        half ``x_t`` is (``cc`` then carries the null rows).  The step index and the timestep live on the device (``state``: the
+        scalars that ``advance`` moves), so the loop issues no host synchronisation and one captured graph serves every step
+        (_replay_walk); ``host_t(i)`` is the timestep on the host, which only a backbone without an engine needs.  At t = 0 the full
+        loop's update kernel writes nothing although the backbone is evaluated, as in the reference."""
+        num_checkpoints = buf.size(1) if buf is not None else 0
         t_idx = 0
-        if (self.hip_graph_sampling and engine is not None and denoise_steps > 2 and "noise" not in self.__dict__
+
+        def checkpoint(i):
+            nonlocal t_idx
+            if buf is not None and is_checkpoint(i) and t_idx < num_checkpoints:
+                buf[:, t_idx].copy_(x_t)
+                t_idx += 1
+
+        if (self.hip_graph_sampling and engine is not None and steps > 2 and "noise" not in self.__dict__
                 and type(self).noise is AbstractDiffusionPipeline.noise):
-            done = self._reverse_process_graph(x_all, x_t, cc, engine, update, t_dev, denoise_steps, buf, steps_per_ckpt, num_checkpoints)
-            if done:
+            if self._replay_walk(x_all, x_t, cc, engine, t_dev, buf, steps, z_from, update, advance, state, checkpoint):
                 self._check_backbone_errors()
                 return {"buffer": buf, "denoised": x_t}
-            t_dev.fill_(denoise_steps - 1)
-        for t in range(denoise_steps - 1, -1, -1):
-            z = self.noise(x_t) if t > 1 else None          # drawn before the backbone call (:196-199)
+            t_idx = 0
+        for i in range(steps - 1, -1, -1):
+            z = self.noise(x_t) if z_from is not None and i >= z_from else None
             if engine is not None:
                 pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
             else:
-                pred = self.backbone(x_t, torch.full((batch_size,), t, device=dev, dtype=torch.long), cc)
-            if t > 0:
-                update(pred.contiguous(), z)
-            if buf is not None and t % steps_per_ckpt == 0 and t_idx < num_checkpoints:
-                buf[:, t_idx].copy_(x_t)
-                t_idx += 1
-            ops.step_advance(t_dev, None, 0)
+                pred = self.backbone(x_t, torch.full((x_t.size(0),), host_t(i), device=x_t.device, dtype=torch.long), cc)
+            update(pred.contiguous(), z)
+            checkpoint(i)
+            advance(None, 0)
         self._check_backbone_errors()
         return {"buffer": buf, "denoised": x_t}
 
-    def _reverse_process_graph(self, x_all, x_t, cc, engine, update, t_dev, denoise_steps, buf, steps_per_ckpt, num_checkpoints) -> bool:
-        """The loop of reverse_process with steps t = T-2 .. 0 replayed from one captured HIP graph (step T-1 runs eagerly:
-        it builds the engine plan and its buffers).  Same arithmetic and the same Philox stream as the eager loop: z is
-        drawn at the offset the eager loop would use (the draws of t <= 1 are ignored by the update kernel either way).
-        ``x_all`` is what the backbone reads and ``update`` writes - ``x_t`` itself, or under guidance the doubled batch whose
-        first half ``x_t`` is.  Returns False (nothing modified but the RNG offset bookkeeping) if the capture fails."""
-        dev = x_t.device
-        n_elem = x_t.numel()
-        delta = (n_elem + 3) // 4
-        z = torch.empty_like(x_t)
-        off_dev = torch.full((1,), self._noise_offset, dtype=torch.int64, device=dev)
-        x_save = x_all.clone()
+    def _replay_walk(self, x_all, x_t, cc, engine, t_dev, buf, steps, z_from, update, advance, state, checkpoint) -> bool:
+        """The loop of _run_walk with steps i = steps-2 .. 0 replayed from one captured HIP graph (step steps-1 runs eagerly: it
+        builds the engine plan and its buffers).  Same arithmetic and the same Philox stream as the eager loop: where the walk draws
+        at all, the captured step draws z at every replay from a device-side offset that ``advance`` moves; the draws below
+        ``z_from`` are ignored by the update kernel (t <= 1 in the full loop, row 0 of the spaced walk has sigma = 0) and not counted,
+        so the offset ends where the eager loop leaves it.  A walk without noise has no Philox kernel in its graph.  Returns False
+        (x_all, ``state`` and ``buf`` as they were) if the capture fails."""
+        delta = (x_t.numel() + 3) // 4
+        noisy = z_from is not None
+        z = torch.empty_like(x_t) if noisy else None
+        off_dev = torch.full((1,), self._noise_offset, dtype=torch.int64, device=x_t.device) if noisy else None
+        x_save, state_save = x_all.clone(), [s.clone() for s in state]
 
         def step():
-            ops.philox_normal(z, self.noise_seed, 0, offset_dev=off_dev)
+            if noisy:
+                ops.philox_normal(z, self.noise_seed, 0, offset_dev=off_dev)
             pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
             update(pred, z)
-            ops.step_advance(t_dev, off_dev, delta)
-
-        t_idx = 0
-
-        def checkpoint(t):
-            nonlocal t_idx
-            if buf is not None and t % steps_per_ckpt == 0 and t_idx < num_checkpoints:
-                buf[:, t_idx].copy_(x_t)
-                t_idx += 1
+            advance(off_dev, delta)
 
         try:
-            step()                                      # t = T-1, eager
-            checkpoint(denoise_steps - 1)
+            step()                                      # i = steps-1, eager
+            checkpoint(steps - 1)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):   # other threads (RCCL watchdog) may call HIP
                 step()
         except Exception as exc:  # noqa: BLE001  (capture is an optimisation; any failure -> eager loop)
             torch.cuda.synchronize()
             x_all.copy_(x_save)
+            for s, saved in zip(state, state_save):
+                s.copy_(saved)
             if buf is not None:
                 buf.zero_()
             self.hip_graph_sampling = False
             import warnings
             warnings.warn(f"HIP graph capture of the sampling step failed ({type(exc).__name__}: {exc}); using the eager loop")
             return False
-        for t in range(denoise_steps - 2, -1, -1):
+        for i in range(steps - 2, -1, -1):
             graph.replay()
-            checkpoint(t)
-        self._noise_offset += delta * max(denoise_steps - 2, 0)      # eager-loop bookkeeping: one draw per t > 1
+            checkpoint(i)
+        if noisy:
+            self._noise_offset += delta * (steps - z_from)      # eager-loop bookkeeping: one draw per i >= z_from
         return True
 
     # ------------------------------------------------------------------ few-step sampling
@@ -357,101 +370,23 @@ class DDPM(AbstractDiffusionPipeline):
             ops.p_sample_step_spaced_pred(x_all, pred, z, rows, k_dev, PREDICTION_TYPES[kind], scale, clip)
 
     def _reverse_process_spaced(self, x_all, x_t, cc, engine, scale, spaced, clip, t_dev, buf) -> dict:
-        """The walk over ``spaced["taus"]`` from the top, k = S-1 .. 0: draw z (eta > 0 and k >= 1 only, before the backbone call as
-        in the full loop), evaluate the backbone at t = tau_k, rho_p_sample_step_spaced (rho_p_sample_step_spaced_pred for a v or
-        x0 model) on row k, checkpoint, rho_spaced_advance.
-        ``x_all`` is what the backbone reads and the update writes: ``x_t``, or under guidance the doubled batch whose first half
-        ``x_t`` is (``cc`` then carries the null rows).  k and t live on the device, so one captured graph serves every step
-        (_reverse_process_spaced_graph).
+        """The walk over ``spaced["taus"]`` from the top, k = S-1 .. 0, as _run_walk drives it: z is drawn for eta > 0 and k >= 1 only,
+        the backbone is evaluated at t = tau_k, the update is rho_p_sample_step_spaced (rho_p_sample_step_spaced_pred for a v or x0
+        model) on row k, the advance rho_spaced_advance on k and t.
 
         With sampler "dpmpp_2m" the update is rho_dpmpp_2m_step on the rows of dpmpp_2m_coefficients: no z is drawn, and ``hist``, an
-        ordinary device tensor of x_t's shape, carries the x0 estimate from one step to the next.  It is not zeroed: row S-1 is
-        first order and does not read it."""
-        taus, eta, kind = spaced["taus"], spaced["eta"], spaced["pred"]
+        ordinary device tensor of x_t's shape, carries the x0 estimate from one step to the next - read and written by the captured
+        step like x_all.  It is not zeroed: row S-1 is first order and does not read it."""
+        taus, kind = spaced["taus"], spaced["pred"]
         S = len(taus)
-        dev = x_all.device
-        batch_size = x_t.size(0)
-        rows, taus_dev = self._spaced_device(spaced, dev)
-        k_dev = torch.full((1,), S - 1, dtype=torch.int32, device=dev)
+        rows, taus_dev = self._spaced_device(spaced, x_all.device)
+        k_dev = torch.full((1,), S - 1, dtype=torch.int32, device=x_all.device)
         ckpt = spaced_checkpoints(spaced["T"], taus) if buf is not None else ()
-        num_checkpoints = buf.size(1) if buf is not None else 0
-        noisy = eta > 0.0
         hist = torch.empty_like(x_t) if spaced.get("sampler", "ddim") == "dpmpp_2m" else None
-        result = {"buffer": buf, "denoised": x_t}
-        if (self.hip_graph_sampling and engine is not None and S > 2 and "noise" not in self.__dict__
-                and type(self).noise is AbstractDiffusionPipeline.noise):
-            if self._reverse_process_spaced_graph(x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt,
-                                                  kind, hist):
-                self._check_backbone_errors()
-                return result
-            k_dev.fill_(S - 1)
-            t_dev.fill_(taus[-1])
-        t_idx = 0
-        for k in range(S - 1, -1, -1):
-            z = self.noise(x_t) if (noisy and k >= 1) else None
-            if engine is not None:
-                pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
-            else:
-                pred = self.backbone(x_t, torch.full((batch_size,), taus[k], device=dev, dtype=torch.long), cc)
-            self._spaced_update(x_all, pred.contiguous(), z, rows, k_dev, scale, clip, kind, hist)
-            if buf is not None and taus[k] in ckpt and t_idx < num_checkpoints:
-                buf[:, t_idx].copy_(x_t)
-                t_idx += 1
-            ops.spaced_advance(k_dev, t_dev, taus_dev, None, 0)
-        self._check_backbone_errors()
-        return result
-
-    def _reverse_process_spaced_graph(self, x_all, x_t, cc, engine, scale, clip, rows, taus_dev, k_dev, t_dev, taus, noisy, buf, ckpt,
-                                      kind="epsilon", hist=None) -> bool:
-        """_reverse_process_graph for the spaced walk: step S-1 runs eagerly (it builds the engine plan), one captured step is
-        replayed S-1 times.  With eta > 0 the captured step draws z at every replay from the device-side offset; the draw of k = 0
-        is ignored by the kernel (row 0 has sigma = 0) and not counted, so the offset ends where the eager loop leaves it.  With
-        eta = 0 no Philox kernel is in the graph.  ``hist`` (the dpmpp_2m walk; None otherwise) is read and written by the captured
-        step like x_all; the eager step S-1 fills it.  Returns False (nothing modified) if the capture fails."""
-        dev = x_t.device
-        S = len(taus)
-        delta = (x_t.numel() + 3) // 4
-        z = torch.empty_like(x_t) if noisy else None
-        off_dev = torch.full((1,), self._noise_offset, dtype=torch.int64, device=dev) if noisy else None
-        x_save = x_all.clone()
-        num_checkpoints = buf.size(1) if buf is not None else 0
-
-        def step():
-            if noisy:
-                ops.philox_normal(z, self.noise_seed, 0, offset_dev=off_dev)
-            pred = engine.forward(x_all, None, cc, t_scalar_dev=t_dev)
-            self._spaced_update(x_all, pred, z, rows, k_dev, scale, clip, kind, hist)
-            ops.spaced_advance(k_dev, t_dev, taus_dev, off_dev, delta)
-
-        t_idx = 0
-
-        def checkpoint(k):
-            nonlocal t_idx
-            if buf is not None and taus[k] in ckpt and t_idx < num_checkpoints:
-                buf[:, t_idx].copy_(x_t)
-                t_idx += 1
-
-        try:
-            step()                                      # k = S-1, eager
-            checkpoint(S - 1)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                step()
-        except Exception as exc:  # noqa: BLE001  (capture is an optimisation; any failure -> eager loop)
-            torch.cuda.synchronize()
-            x_all.copy_(x_save)
-            if buf is not None:
-                buf.zero_()
-            self.hip_graph_sampling = False
-            import warnings
-            warnings.warn(f"HIP graph capture of the sampling step failed ({type(exc).__name__}: {exc}); using the eager loop")
-            return False
-        for k in range(S - 2, -1, -1):
-            graph.replay()
-            checkpoint(k)
-        if noisy:
-            self._noise_offset += delta * (S - 1)       # eager-loop bookkeeping: one draw per k >= 1
-        return True
+        return self._run_walk(x_all, x_t, cc, engine, t_dev, buf, S, host_t=lambda k: taus[k], z_from=1 if spaced["eta"] > 0.0 else None,
+                              update=lambda pred, z: self._spaced_update(x_all, pred, z, rows, k_dev, scale, clip, kind, hist),
+                              advance=lambda off_dev, delta: ops.spaced_advance(k_dev, t_dev, taus_dev, off_dev, delta),
+                              state=(k_dev, t_dev), is_checkpoint=lambda k: taus[k] in ckpt)
 
     # ------------------------------------------------------------------ training
     def _draw_timesteps(self, batch_size: int, device) -> Tensor:

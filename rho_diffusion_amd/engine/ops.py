@@ -49,27 +49,37 @@ def q_sample(x0: Tensor, eps: Tensor, t: Tensor, alpha_bar: Tensor, out: Optiona
     return out
 
 
+def _step_operands(x: Tensor, pred: Tensor, side: Optional[Tensor], rows: Tensor, idx_dev: Tensor, scale: Optional[float],
+                   names: Sequence[str] = ("x", "pred", "z", "rows", "k_dev"), width: int = 8) -> Tuple[int, bool]:
+    """The operand checks of the five reverse-process updates, (n, guided): ``x`` / ``pred`` contiguous float32 holding one row of n
+    elements (``scale`` None) or the two rows of the doubled batch (guided), the optional side operand (z or hist) one row of n,
+    ``rows`` float32 [S, ``width``], ``idx_dev`` the int32[1] device scalar that picks the row.  ``names``: theirs in the caller."""
+    xn, pn, sn, rn, kn = names
+    _f32c(x, xn), _f32c(pred, pn), _f32c(rows, rn)
+    if side is not None:
+        _f32c(side, sn)
+    if rows.dim() != 2 or rows.shape[1] != width or rows.shape[0] < 1:
+        raise RhoHipError(f"{rn} must be float32 [S, {width}], got {tuple(rows.shape)}")
+    guided = scale is not None
+    n = x.numel() // 2 if guided else x.numel()
+    if n < 1 or x.numel() != (2 * n if guided else n) or pred.numel() != x.numel() or (side is not None and side.numel() != n):
+        raise RhoHipError(f"{xn} / {pn} hold {'two rows' if guided else 'one row'} of n elements and {sn} one: got {x.numel()}, "
+                          f"{pred.numel()}, {None if side is None else side.numel()}")
+    if idx_dev.dtype != torch.int32 or not idx_dev.is_cuda or idx_dev.numel() != 1:
+        raise RhoHipError(f"{kn} must be int32[1] on the GPU")
+    return n, guided
+
+
 def p_sample_step(x: Tensor, eps_hat: Tensor, z: Optional[Tensor], coef_table: Tensor, t_dev: Tensor) -> Tensor:
-    _f32c(x, "x"), _f32c(eps_hat, "eps_hat"), _f32c(coef_table, "coef_table")
-    if t_dev.dtype != torch.int32:
-        raise RhoHipError("t_dev must be int32[1] on the GPU")
-    check(hip.lib().rho_p_sample_step(ptr(x), ptr(eps_hat), ptr(z), ptr(coef_table), ptr(t_dev), x.numel(), stream()),
-          "rho_p_sample_step")
+    n, _ = _step_operands(x, eps_hat, z, coef_table, t_dev, None, ("x", "eps_hat", "z", "coef_table", "t_dev"), 3)
+    check(hip.lib().rho_p_sample_step(ptr(x), ptr(eps_hat), ptr(z), ptr(coef_table), ptr(t_dev), n, stream()), "rho_p_sample_step")
     return x
 
 
 def p_sample_step_cfg(x2: Tensor, eps2: Tensor, z: Optional[Tensor], coef_table: Tensor, t_dev: Tensor, scale: float) -> Tensor:
     """One guided reverse update (rho_p_sample_step_cfg).  ``x2`` [2B, ...]: x_t and its copy; ``eps2`` [2B, ...]: the conditional
     and the null-condition prediction; ``z`` [B, ...] or None.  Both halves of ``x2`` receive the update."""
-    _f32c(x2, "x2"), _f32c(eps2, "eps2"), _f32c(coef_table, "coef_table")
-    if z is not None:
-        _f32c(z, "z")
-    n = x2.numel() // 2
-    if x2.numel() != 2 * n or eps2.numel() != 2 * n or (z is not None and z.numel() != n):
-        raise RhoHipError(f"x2 / eps2 hold two rows of n elements and z one: got {x2.numel()}, {eps2.numel()}, "
-                          f"{None if z is None else z.numel()}")
-    if t_dev.dtype != torch.int32:
-        raise RhoHipError("t_dev must be int32[1] on the GPU")
+    n, _ = _step_operands(x2, eps2, z, coef_table, t_dev, float(scale), ("x2", "eps2", "z", "coef_table", "t_dev"), 3)
     check(hip.lib().rho_p_sample_step_cfg(ptr(x2), ptr(eps2), ptr(z), ptr(coef_table), ptr(t_dev), float(scale), n, stream()),
           "rho_p_sample_step_cfg")
     return x2
@@ -80,18 +90,7 @@ def p_sample_step_spaced(x: Tensor, eps_hat: Tensor, z: Optional[Tensor], rows: 
     """One reverse update of the spaced walk (rho_p_sample_step_spaced): row ``*k_dev`` of ``rows`` [S, 8].  ``scale`` None: ``x`` and
     ``eps_hat`` hold the sample and its prediction; a float: the guided form, both hold the doubled batch [2B, ...] and both halves
     of ``x`` receive the update.  ``z`` [B, ...] or None."""
-    _f32c(x, "x"), _f32c(eps_hat, "eps_hat"), _f32c(rows, "rows")
-    if z is not None:
-        _f32c(z, "z")
-    if rows.dim() != 2 or rows.shape[1] != 8 or rows.shape[0] < 1:
-        raise RhoHipError(f"rows must be float32 [S, 8], got {tuple(rows.shape)}")
-    guided = scale is not None
-    n = x.numel() // 2 if guided else x.numel()
-    if n < 1 or x.numel() != (2 * n if guided else n) or eps_hat.numel() != x.numel() or (z is not None and z.numel() != n):
-        raise RhoHipError(f"x / eps_hat hold {'two rows' if guided else 'one row'} of n elements and z one: got {x.numel()}, "
-                          f"{eps_hat.numel()}, {None if z is None else z.numel()}")
-    if k_dev.dtype != torch.int32 or not k_dev.is_cuda or k_dev.numel() != 1:
-        raise RhoHipError("k_dev must be int32[1] on the GPU")
+    n, guided = _step_operands(x, eps_hat, z, rows, k_dev, scale, ("x", "eps_hat", "z", "rows", "k_dev"))
     check(hip.lib().rho_p_sample_step_spaced(ptr(x), ptr(eps_hat), ptr(z), ptr(rows), ptr(k_dev), rows.shape[0], n, int(guided),
                                              float(scale) if guided else 0.0, int(bool(clip)), stream()), "rho_p_sample_step_spaced")
     return x
@@ -102,20 +101,9 @@ def p_sample_step_spaced_pred(x: Tensor, pred: Tensor, z: Optional[Tensor], rows
     """One reverse update of the spaced walk of a v- or x0-predicting backbone (rho_p_sample_step_spaced_pred): row ``*k_dev`` of
     ``rows`` [S, 8] as spaced_pred_coefficients writes them, ``pred_type`` 1 (v) or 2 (sample).  ``scale`` / ``z`` / ``clip`` as in
     p_sample_step_spaced."""
-    _f32c(x, "x"), _f32c(pred, "pred"), _f32c(rows, "rows")
-    if z is not None:
-        _f32c(z, "z")
-    if rows.dim() != 2 or rows.shape[1] != 8 or rows.shape[0] < 1:
-        raise RhoHipError(f"rows must be float32 [S, 8], got {tuple(rows.shape)}")
     if pred_type not in (1, 2):
         raise RhoHipError(f"pred_type must be 1 (v) or 2 (sample), got {pred_type}: epsilon takes p_sample_step_spaced")
-    guided = scale is not None
-    n = x.numel() // 2 if guided else x.numel()
-    if n < 1 or x.numel() != (2 * n if guided else n) or pred.numel() != x.numel() or (z is not None and z.numel() != n):
-        raise RhoHipError(f"x / pred hold {'two rows' if guided else 'one row'} of n elements and z one: got {x.numel()}, "
-                          f"{pred.numel()}, {None if z is None else z.numel()}")
-    if k_dev.dtype != torch.int32 or not k_dev.is_cuda or k_dev.numel() != 1:
-        raise RhoHipError("k_dev must be int32[1] on the GPU")
+    n, guided = _step_operands(x, pred, z, rows, k_dev, scale)
     check(hip.lib().rho_p_sample_step_spaced_pred(ptr(x), ptr(pred), ptr(z), ptr(rows), ptr(k_dev), rows.shape[0], n, int(guided),
                                                   float(scale) if guided else 0.0, int(bool(clip)), int(pred_type), stream()),
           "rho_p_sample_step_spaced_pred")
@@ -128,18 +116,9 @@ def dpmpp_2m_step(x: Tensor, pred: Tensor, hist: Tensor, rows: Tensor, k_dev: Te
     dpmpp_2m_coefficients writes them, ``pred_type`` 0 (epsilon), 1 (v) or 2 (sample).  ``hist`` [B, ...] holds the x0 estimate of the
     step before - one row also under guidance, read only by a second-order row - and receives this step's.  ``scale`` / ``clip`` as in
     p_sample_step_spaced."""
-    _f32c(x, "x"), _f32c(pred, "pred"), _f32c(hist, "hist"), _f32c(rows, "rows")
-    if rows.dim() != 2 or rows.shape[1] != 8 or rows.shape[0] < 1:
-        raise RhoHipError(f"rows must be float32 [S, 8], got {tuple(rows.shape)}")
     if pred_type not in (0, 1, 2):
         raise RhoHipError(f"pred_type must be 0 (epsilon), 1 (v) or 2 (sample), got {pred_type}")
-    guided = scale is not None
-    n = x.numel() // 2 if guided else x.numel()
-    if n < 1 or x.numel() != (2 * n if guided else n) or pred.numel() != x.numel() or hist.numel() != n:
-        raise RhoHipError(f"x / pred hold {'two rows' if guided else 'one row'} of n elements and hist one: got {x.numel()}, "
-                          f"{pred.numel()}, {hist.numel()}")
-    if k_dev.dtype != torch.int32 or not k_dev.is_cuda or k_dev.numel() != 1:
-        raise RhoHipError("k_dev must be int32[1] on the GPU")
+    n, guided = _step_operands(x, pred, _f32c(hist, "hist"), rows, k_dev, scale, ("x", "pred", "hist", "rows", "k_dev"))
     check(hip.lib().rho_dpmpp_2m_step(ptr(x), ptr(pred), ptr(hist), ptr(rows), ptr(k_dev), rows.shape[0], n, int(guided),
                                       float(scale) if guided else 0.0, int(bool(clip)), int(pred_type), stream()),
           "rho_dpmpp_2m_step")

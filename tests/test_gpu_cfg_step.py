@@ -10,7 +10,7 @@ Reference: the same expression in float64 on the float32 inputs,
     g = e_u + s * (e_c - e_u);   clamp(c0 * (x - c1 * g) + c2 * z, -1, 1),
 z dropped for t <= 1 or z = NULL, nothing written for t = 0.  Two bars: the rel-L2 of the p_sample_step test (2e-6) and a
 per-element bound 4 * 2^-24 * sum |terms|, sum |terms| = c0 * (|x| + c1 * (|s| * (|e_c| + |e_u|) + |e_u|)) + |c2 * z|.  The kernel's
-expression p_update(c0, c1, c2, x, fma(s, e_c - e_u, e_u), z) rounds five times: d = e_c - e_u, g = fma(s, d, e_u),
+expression PSampleOp(x, fma(s, e_c - e_u, e_u), z), of coefficients c0, c1, c2, rounds five times: d = e_c - e_u, g = fma(s, d, e_u),
 i = fma(-c1, g, x), c2 * z, fma(c0, i, c2 * z).  To first order their errors reach the result as
     c0 c1 |s| U|d|  +  c0 c1 U|g|  +  c0 U|i|  +  U|c2 z|  +  U|result|
 with |d| <= |e_c| + |e_u|, |g| <= |s| (|e_c| + |e_u|) + |e_u|, |i| <= |x| + c1 |g|, |result| <= c0 |i| + |c2 z|: at most
@@ -21,13 +21,11 @@ import pytest
 import torch
 
 from helpers import det_normal, rel_l2
-from gpu_util import DEV
+from gpu_util import DEV, Guarded, check_bound, same_bits
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-PAD = 64
-SENT = -776.0                      # exact in float32; the clamp keeps every result inside [-1, 1]
 T = 1000
 SMALL = [1, 3, 4, 5, 255, 257, 1029]
 WRAP_SCALAR = 525_065              # n % 4 == 1: scalar loop, 524288 threads -> second trip of 777 elements
@@ -62,33 +60,6 @@ def _coef():
     return LinearSchedule(T, 1e-3, 0.02).device_tables("cpu")["coef"].clone()       # float32 [T, 3]
 
 
-class Guarded:
-    """A device copy of a 1-D CPU tensor placed ``shift`` elements past a 256-byte aligned address, PAD sentinels on either side."""
-
-    def __init__(self, src: torch.Tensor, shift: int = 0):
-        n = src.numel()
-        self.n, self.shift = n, shift
-        self.buf = torch.full((PAD + shift + n + PAD,), SENT, dtype=torch.float32, device=DEV)
-        self.v = self.buf[PAD + shift: PAD + shift + n]
-        self.v.copy_(src)
-        assert self.v.data_ptr() % 16 == (4 * shift) % 16
-
-    @property
-    def ptr(self) -> int:
-        return self.v.data_ptr()
-
-    def cpu(self) -> torch.Tensor:
-        return self.v.cpu()
-
-    def intact(self) -> bool:
-        lo, hi = self.buf[:PAD + self.shift], self.buf[PAD + self.shift + self.n:]
-        return hi.numel() == PAD and bool((lo == SENT).all()) and bool((hi == SENT).all())
-
-
-def _same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return torch.equal(a.cpu().contiguous().view(torch.int32), b.cpu().contiguous().view(torch.int32))
-
-
 def _run(hip, x, ec, eu, z, t, scale, shifts=frozenset(), row1=None):
     """Launch on guarded copies; returns the [2, n] result.  Inputs must come back unchanged, every sentinel intact."""
     n = x.numel()
@@ -117,15 +88,6 @@ def _ref(x, ec, eu, z, t, scale):
     return ref, 4 * U * terms
 
 
-def _check(got, ref, bound, what):
-    got = got.double().cpu().flatten()
-    assert torch.isfinite(got).all(), what
-    excess = (got - ref).abs() - bound
-    i = int(excess.argmax())
-    assert float(excess[i]) <= 0.0, (what, "element", i, float(got[i]), float(ref[i]), "bound", float(bound[i]))
-    assert rel_l2(got, ref) < 2e-6, what
-
-
 def _step(hip, x, e, z, t):
     """rho_p_sample_step on a plain copy (its own edges are test_gpu_streaming_edges.py's business)."""
     xd, ed = x.to(DEV).clone(), e.to(DEV)
@@ -148,30 +110,30 @@ def test_p_sample_step_cfg_sizes(hip, n):
                 got = _run(hip, x, ec, eu, zz, t, scale)
                 ref, bound = _ref(x, ec, eu, zz, t, scale)
                 what = ("p_sample_step_cfg", n, t, zz is not None, scale)
-                _check(got[0], ref, bound, what)
-                assert _same_bits(got[1], got[0]), what        # the second row is the first, bit for bit
+                check_bound(got[0], ref, bound, what, 2e-6)
+                assert same_bits(got[1], got[0]), what        # the second row is the first, bit for bit
                 assert (got[0] != x).any(), what
     # t = 0: no update - both rows (row 1 made different here) and the sentinels stay as they were
     other = x + 1.0
     for zz in (z, None):
         got = _run(hip, x, ec, eu, zz, 0, 3.0, row1=other)
-        assert _same_bits(got[0], x) and _same_bits(got[1], other), (n, zz is not None)
+        assert same_bits(got[0], x) and same_bits(got[1], other), (n, zz is not None)
 
 
 @pytest.mark.parametrize("n", [1029, 1032, WRAP_VEC])
 def test_p_sample_step_cfg_alignment(hip, n):
     """Operands offset by 4 bytes take the scalar loop: the bits of the aligned run (16-byte form at 1032 and the wrap size),
-    both evaluate p_update_cfg."""
+    both are loops of step_walk over PSampleOp."""
     x, ec, eu, z = _inputs(n)
     t, scale = 500, 3.0
     base = _run(hip, x, ec, eu, z, t, scale)
     ref, bound = _ref(x, ec, eu, z, t, scale)
-    _check(base[0], ref, bound, ("aligned", n))
+    check_bound(base[0], ref, bound, ("aligned", n), 2e-6)
     for shifts in [frozenset([s]) for s in ("x2", "eps2", "z")] + [frozenset(("x2", "eps2", "z"))]:
         got = _run(hip, x, ec, eu, z, t, scale, shifts)
-        assert _same_bits(got, base), (n, sorted(shifts))
+        assert same_bits(got, base), (n, sorted(shifts))
         got0 = _run(hip, x, ec, eu, z, 0, scale, shifts)
-        assert _same_bits(got0[0], x) and _same_bits(got0[1], x), (n, sorted(shifts))
+        assert same_bits(got0[0], x) and same_bits(got0[1], x), (n, sorted(shifts))
 
 
 @pytest.mark.parametrize("n", [257, 1032, WRAP_SCALAR])
@@ -205,8 +167,18 @@ def test_wrapper_checks_shapes_and_updates_both_halves(hip):
     e2 = torch.cat([ec, eu]).view(6, 1, 16, 16).to(DEV)
     out = ops.p_sample_step_cfg(x2, e2, z.view(3, 1, 16, 16).to(DEV), coef, t_dev, 3.0)
     assert out is x2
-    assert _same_bits(x2.view(2, n)[0], _run(hip, x, ec, eu, z, 500, 3.0)[0]) and torch.equal(x2[:3], x2[3:])
+    assert same_bits(x2.view(2, n)[0], _run(hip, x, ec, eu, z, 500, 3.0)[0]) and torch.equal(x2[:3], x2[3:])
     with pytest.raises(RhoHipError):
         ops.p_sample_step_cfg(x2, e2, z.to(DEV)[:-1].contiguous(), coef, t_dev, 3.0)
     with pytest.raises(RhoHipError):
         ops.p_sample_step_cfg(x2, e2[:3].contiguous(), None, coef, t_dev, 3.0)
+    # the unguided wrapper checks what the guided one does: z one row of n contiguous elements, t_dev one element on the device
+    xd, ed, zd = x.view(3, 1, 16, 16).to(DEV), ec.view(3, 1, 16, 16).to(DEV), z.view(3, 1, 16, 16).to(DEV)
+    for bad in (lambda: ops.p_sample_step(xd, ed, zd[:2].contiguous(), coef, t_dev),
+                lambda: ops.p_sample_step(xd, ed, zd[:, :, :, :15], coef, t_dev),
+                lambda: ops.p_sample_step(xd, ed, zd, coef, t_dev.cpu()),
+                lambda: ops.p_sample_step(xd, ed, zd, coef, torch.tensor([500, 500], dtype=torch.int32, device=DEV)),
+                lambda: ops.p_sample_step_cfg(x2, e2, zd, coef, t_dev.cpu(), 3.0)):
+        with pytest.raises(RhoHipError):
+            bad()
+    assert same_bits(xd.flatten(), x)                            # nothing was launched

@@ -34,13 +34,11 @@ import pytest
 import torch
 
 from helpers import det_normal
-from gpu_util import DEV
+from gpu_util import DEV, Guarded, check_bound, same_bits
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-PAD = 64
-SENT = -776.0                      # exact in float32
 T = 1000
 S = 50
 KS = [S - 1, 24, 1, 0]
@@ -102,33 +100,6 @@ def _inputs(n, k, kind, schedule="linear"):
     return x, pc, pu, hist
 
 
-class Guarded:
-    """A device copy of a 1-D CPU tensor placed ``shift`` elements past a 256-byte aligned address, PAD sentinels on either side."""
-
-    def __init__(self, src: torch.Tensor, shift: int = 0):
-        n = src.numel()
-        self.n, self.shift = n, shift
-        self.buf = torch.full((PAD + shift + n + PAD,), SENT, dtype=torch.float32, device=DEV)
-        self.v = self.buf[PAD + shift: PAD + shift + n]
-        self.v.copy_(src)
-        assert self.v.data_ptr() % 16 == (4 * shift) % 16
-
-    @property
-    def ptr(self) -> int:
-        return self.v.data_ptr()
-
-    def cpu(self) -> torch.Tensor:
-        return self.v.cpu()
-
-    def intact(self) -> bool:
-        lo, hi = self.buf[:PAD + self.shift], self.buf[PAD + self.shift + self.n:]
-        return hi.numel() == PAD and bool((lo == SENT).all()) and bool((hi == SENT).all())
-
-
-def _same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return torch.equal(a.cpu().contiguous().view(torch.int32), b.cpu().contiguous().view(torch.int32))
-
-
 def _run(hip, rows, k, x, pc, pu, hist, scale, clip, kind, shifts=frozenset(), row1=None, expect=0):
     """Launch on guarded copies.  ``scale`` None: the plain form on (x, pc); else the guided form on [2, n] operands.  Returns
     (x after the call as [1, n] or [2, n], hist after the call [n]).  pred, rows and k must come back unchanged, every sentinel
@@ -183,34 +154,26 @@ def _ref(row, x, pc, pu, hist, scale, clip, kind):
     return r, 1.001 * U * terms, x0c, 1.001 * U * E0, x0
 
 
-def _check(got, ref, bound, what):
-    got = got.double().cpu().flatten()
-    assert torch.isfinite(got).all(), what
-    excess = (got - ref).abs() - bound
-    i = int(excess.argmax())
-    assert float(excess[i]) <= 0.0, (what, "element", i, float(got[i]), float(ref[i]), "bound", float(bound[i]))
-
-
 def _one(hip, n, k, clip, scale, kind, schedule="linear", shifts=frozenset()):
     rows = _rows(kind, schedule)
     x, pc, pu, hist = _inputs(n, k, kind, schedule)
     got, h = _run(hip, rows, k, x, pc, pu, hist, scale, clip, kind, shifts)
     ref, bound, x0c, b0, x0 = _ref(rows[k], x, pc, pu, hist, scale, clip, kind)
     what = ("dpmpp_2m_step", KINDS[kind], schedule, n, k, clip, scale, sorted(shifts))
-    _check(got[0], ref, bound, what)
-    _check(h, x0c, b0, what + ("hist",))
+    check_bound(got[0], ref, bound, what)
+    check_bound(h, x0c, b0, what + ("hist",))
     if clip:
         assert float(h.abs().max()) <= 1.0, what
         sure = x0.abs() > 1.0 + b0                              # the float32 estimate is beyond the clamp whatever it rounded to
         assert torch.equal(h[sure].double(), x0.sign()[sure]), what
     if scale is not None:
-        assert _same_bits(got[1], got[0]), what                # the second row is the first, bit for bit
+        assert same_bits(got[1], got[0]), what                # the second row is the first, bit for bit
     if n >= 1023 and k <= 24 and schedule == "linear":
         bites = int((x0.abs() > 1.0).sum())
         assert 0 < bites < n, (what, bites)                     # the clamp is exercised on some elements, not on all
         assert (got[0] != x).any() and (h != hist).any(), what
     if k == 0:                                                  # row 0 is {.., 0, 1, 0}: the last step returns the x0 estimate itself
-        assert rows[0, 2:5].tolist() == [0.0, 1.0, 0.0] and _same_bits(got[0], h), what
+        assert rows[0, 2:5].tolist() == [0.0, 1.0, 0.0] and same_bits(got[0], h), what
     return got, h
 
 
@@ -256,13 +219,13 @@ def test_first_order_rows_do_not_read_hist(hip, scale, kind):
                 got, h = _run(hip, rows, k, x, pc, pu, nan_h, scale, clip, kind)
                 base, hb = _run(hip, rows, k, x, pc, pu, hist, scale, clip, kind)
                 assert torch.isfinite(got).all() and torch.isfinite(h).all(), (n, k, clip)
-                assert _same_bits(got, base) and _same_bits(h, hb), (n, k, clip)
+                assert same_bits(got, base) and same_bits(h, hb), (n, k, clip)
                 _, _, x0c, b0, _ = _ref(rows[k], x, pc, pu, hist, scale, clip, kind)
-                _check(h, x0c, b0, ("hist after a NaN history", n, k, clip))
+                check_bound(h, x0c, b0, ("hist after a NaN history", n, k, clip))
         x, pc, pu, hist = _inputs(n, 24, kind)
         got, h = _run(hip, rows, 24, x, pc, pu, nan_h, scale, 1, kind)
         assert torch.isnan(got).all() and torch.isfinite(h).all()
-        assert _same_bits(h, _run(hip, rows, 24, x, pc, pu, hist, scale, 1, kind)[1])
+        assert same_bits(h, _run(hip, rows, 24, x, pc, pu, hist, scale, 1, kind)[1])
 
 
 @pytest.mark.parametrize("n", [5, 1024])
@@ -273,9 +236,9 @@ def test_k_outside_the_table_writes_nothing(hip, n, k):
         x, pc, pu, hist = _inputs(n, 1, kind)
         other = x + 1.0
         got, h = _run(hip, rows, k, x, pc, pu, hist, None, 1, kind)
-        assert _same_bits(got[0], x) and _same_bits(h, hist), (n, k)
+        assert same_bits(got[0], x) and same_bits(h, hist), (n, k)
         got, h = _run(hip, rows, k, x, pc, pu, hist, 3.0, 1, kind, row1=other)
-        assert _same_bits(got[0], x) and _same_bits(got[1], other) and _same_bits(h, hist), (n, k)
+        assert same_bits(got[0], x) and same_bits(got[1], other) and same_bits(h, hist), (n, k)
 
 
 @pytest.mark.parametrize("n", [5, 1024])
@@ -286,7 +249,7 @@ def test_bad_arguments_are_refused(hip, n):
     for bad in (3, -1, 7):
         for scale in (None, 3.0):
             got, h = _run(hip, rows, 24, x, pc, pu, hist, scale, 1, bad, expect=-1)
-            assert _same_bits(got[0], x) and _same_bits(h, hist), (n, bad, scale)
+            assert same_bits(got[0], x) and same_bits(h, hist), (n, bad, scale)
     lib = hip.lib()
     g, gh = Guarded(x), Guarded(hist)
     k_dev = torch.tensor([24], dtype=torch.int32, device=DEV)
@@ -298,7 +261,7 @@ def test_bad_arguments_are_refused(hip, n):
         for guided in (0, 1):
             assert lib.rho_dpmpp_2m_step(*args, guided, 0.0, 1, V, hip.stream()) == -1, (i, repl, guided)
     torch.cuda.synchronize()
-    assert _same_bits(g.cpu(), x) and g.intact() and _same_bits(gh.cpu(), hist) and gh.intact()
+    assert same_bits(g.cpu(), x) and g.intact() and same_bits(gh.cpu(), hist) and gh.intact()
 
 
 @pytest.mark.parametrize("n,scale,kind", [(n, s, kd) for n in (1027, 1024) for s in (None, 3.0) for kd in ALL]
@@ -313,11 +276,11 @@ def test_alignment(hip, n, scale, kind):
         x, pc, pu, hist = _inputs(n, k, kind)
         base, hb = _run(hip, rows, k, x, pc, pu, hist, scale, clip, kind)
         ref, bound, x0c, b0, _ = _ref(rows[k], x, pc, pu, hist, scale, clip, kind)
-        _check(base[0], ref, bound, ("aligned", n, scale, k, clip))
-        _check(hb, x0c, b0, ("aligned hist", n, scale, k, clip))
+        check_bound(base[0], ref, bound, ("aligned", n, scale, k, clip))
+        check_bound(hb, x0c, b0, ("aligned hist", n, scale, k, clip))
         for shifts in [frozenset([s]) for s in ("x", "pred", "hist")] + [frozenset(("x", "pred", "hist"))]:
             got, h = _run(hip, rows, k, x, pc, pu, hist, scale, clip, kind, shifts)
-            assert _same_bits(got, base) and _same_bits(h, hb), (n, scale, k, clip, sorted(shifts))
+            assert same_bits(got, base) and same_bits(h, hb), (n, scale, k, clip, sorted(shifts))
 
 
 @pytest.mark.parametrize("scale", [None, 3.0])
@@ -353,13 +316,13 @@ def test_wrapper_checks_dtypes_and_shapes(hip):
     xd, pd, hd = x.view(shape).to(DEV), pc.view(shape).to(DEV), hist.view(shape).to(DEV)
     out = ops.dpmpp_2m_step(xd, pd, hd, rows, k_dev, EPS)
     want, hw = _run(hip, rows_c, k, x, pc, pu, hist, None, 1, EPS)
-    assert out is xd and _same_bits(xd.flatten(), want[0]) and _same_bits(hd.flatten(), hw)
+    assert out is xd and same_bits(xd.flatten(), want[0]) and same_bits(hd.flatten(), hw)
     x2, p2 = torch.cat([x, x]).view(6, 1, 16, 16).to(DEV), torch.cat([pc, pu]).view(6, 1, 16, 16).to(DEV)
     hd = hist.view(shape).to(DEV)
     out = ops.dpmpp_2m_step(x2, p2, hd, rows_c.to(DEV), k_dev, EPS, 3.0, clip=False)
     want, hw = _run(hip, rows_c, k, x, pc, pu, hist, 3.0, 0, EPS)
     assert out is x2 and torch.equal(x2[:3], x2[3:]) and tuple(hd.shape) == shape
-    assert _same_bits(x2.view(2, n), want) and _same_bits(hd.flatten(), hw)
+    assert same_bits(x2.view(2, n), want) and same_bits(hd.flatten(), hw)
     xd, hd = x.view(shape).to(DEV), hist.view(shape).to(DEV)
     for bad in (lambda: ops.dpmpp_2m_step(xd.double(), pd, hd, rows, k_dev, EPS),
                 lambda: ops.dpmpp_2m_step(xd, pd[:2].contiguous(), hd, rows, k_dev, EPS),
@@ -373,4 +336,4 @@ def test_wrapper_checks_dtypes_and_shapes(hip):
                 lambda: ops.dpmpp_2m_step(x2, p2, torch.cat([hd, hd]), rows, k_dev, EPS, 3.0)):
         with pytest.raises(RhoHipError):
             bad()
-    assert _same_bits(xd.flatten(), x) and _same_bits(hd.flatten(), hist)         # nothing was launched
+    assert same_bits(xd.flatten(), x) and same_bits(hd.flatten(), hist)         # nothing was launched

@@ -29,8 +29,8 @@ import torch
 from torch import nn
 
 from helpers import UNET_CASES, det_normal, det_state_dict, det_uniform, golden_template, load_golden, rel_l2
-from gpu_util import DEV
-from test_gpu_streaming_edges import SMALL, U, WRAP4, Guarded, _check, _data, _same_bits, _shift_sets
+from gpu_util import DEV, Guarded, check_bound, same_bits
+from test_gpu_streaming_edges import SMALL, U, WRAP4, _data, _shift_sets
 
 pytestmark = pytest.mark.gpu
 
@@ -320,7 +320,7 @@ def check_against(got, ref, sh, what):
     ref = ref.detach().double().flatten()
     gap = (sh.v - ref).abs()
     assert float(gap.norm()) <= 1e-12 * float(ref.norm()) + 1e-300, (what, "the shadow expression is not torch's", float(gap.max()))
-    _check(got, ref, sh.e + gap, 1e-6 if float(ref.norm()) > 0 else None, what)
+    check_bound(got, ref, sh.e + gap, what, 1e-6 if float(ref.norm()) > 0 else None)
 
 
 def compare_with_torch(hip, case, n):
@@ -374,7 +374,7 @@ def test_alignment_variants_give_the_aligned_bits(hip, case):
     operands = ["p", "g"] + [nm for nm in abi_of(kind, o, 1, 1.0)[2] if nm]
     for shifts in _shift_sets(operands):
         for a, b in zip(run(shifts), base):
-            assert _same_bits(a, b), (case, sorted(shifts))
+            assert same_bits(a, b), (case, sorted(shifts))
 
 
 def test_argument_checks(hip):
@@ -430,7 +430,7 @@ def test_sumsq_against_float64(hip, n):
         assert gx.intact() and part.intact() and out.intact() and torch.equal(gx.cpu(), x)
         outs.append((part.cpu(), out.cpu()))
     for part, out in outs[1:]:
-        assert _same_bits(part, outs[0][0]) and _same_bits(out, outs[0][1])
+        assert same_bits(part, outs[0][0]) and same_bits(out, outs[0][1])
     part, out = outs[0]
     L = sumsq_chain(n, blocks)
     bound = min((L + 1) * U, 1e-5)
@@ -545,7 +545,7 @@ def test_clipping_below_the_norm_is_the_unclipped_step(hip, name):
     for a, b in zip(*flats):
         assert a.keys() == b.keys()
         for k in a:
-            assert _same_bits(a[k], b[k]), (name, k)
+            assert same_bits(a[k], b[k]), (name, k)
 
 
 def test_hip_adamw_default_path_still_calls_rho_adamw(hip, monkeypatch):
@@ -596,10 +596,10 @@ def test_checkpoint_resume_is_bit_equal(hip, name):
         assert name == "HipSGD" or a["step"] == b["step"] == 3       # torch's SGD state has no step: a loaded buffer means "past step 1"
         for k in a:
             if isinstance(a[k], torch.Tensor):
-                assert _same_bits(a[k], b[k]), (name, k)
+                assert same_bits(a[k], b[k]), (name, k)
     for g, g2 in zip(dev, dev2):
         for p, p2 in zip(g, g2):
-            assert _same_bits(p.detach(), p2.detach())
+            assert same_bits(p.detach(), p2.detach())
 
 
 @pytest.mark.parametrize("case", STARRED)
@@ -653,7 +653,7 @@ def test_state_dict_loads_into_torch_with_a_permuted_arena(hip, case):
     opt2.step()
     ref_opt.step()
     for i, (p, p2, rp) in enumerate(zip(ps, ps2, ref_ps)):
-        assert _same_bits(p.detach(), p2.detach()), (case, i)
+        assert same_bits(p.detach(), p2.detach()), (case, i)
         shp, shs = sh[i]
         shp = _shadow(kind, o, 3, shp, B(rp.grad.reshape(-1)), shs, mu_product=mu_product, mu_product_kernel=mu_product_kernel)
         check_against(p.detach().cpu(), rp, shp, (case, "p", i))

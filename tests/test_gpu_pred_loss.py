@@ -34,13 +34,11 @@ import pytest
 import torch
 
 from helpers import det_normal
-from gpu_util import DEV
+from gpu_util import DEV, Guarded, check_bound, same_bits
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-PAD = 64
-SENT = -776.0
 T = 1000
 EPSILON, V, SAMPLE = 0, 1, 2
 KINDS = {EPSILON: "epsilon", V: "v", SAMPLE: "sample"}
@@ -87,33 +85,6 @@ def _inputs(B, P, kind):
     return pred, x0, eps
 
 
-class Guarded:
-    """A device copy of a 1-D CPU tensor placed ``shift`` elements past a 256-byte aligned address, PAD sentinels on either side."""
-
-    def __init__(self, src: torch.Tensor, shift: int = 0):
-        n = src.numel()
-        self.n, self.shift = n, shift
-        self.buf = torch.full((PAD + shift + n + PAD,), SENT, dtype=torch.float32, device=DEV)
-        self.v = self.buf[PAD + shift: PAD + shift + n]
-        self.v.copy_(src)
-        assert self.v.data_ptr() % 16 == (4 * shift) % 16
-
-    @property
-    def ptr(self) -> int:
-        return self.v.data_ptr()
-
-    def cpu(self) -> torch.Tensor:
-        return self.v.cpu()
-
-    def intact(self) -> bool:
-        lo, hi = self.buf[:PAD + self.shift], self.buf[PAD + self.shift + self.n:]
-        return hi.numel() == PAD and bool((lo == SENT).all()) and bool((hi == SENT).all())
-
-
-def _same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return torch.equal(a.cpu().contiguous().view(torch.int32), b.cpu().contiguous().view(torch.int32))
-
-
 def _run(hip, B, P, kind, pred, x0, eps, t, w, want_grad, shifts=frozenset(), flag=True, expect=0):
     """Launch on guarded copies; returns (loss float32 [1] on the CPU, grad float32 [n] on the CPU or None, the flag's value)."""
     n = B * P
@@ -129,7 +100,7 @@ def _run(hip, B, P, kind, pred, x0, eps, t, w, want_grad, shifts=frozenset(), fl
     assert rc == expect, (rc, expect)
     what = (B, P, KINDS.get(kind), w is not None, want_grad, sorted(shifts))
     assert gp.intact() and gx.intact() and ge.intact() and out.intact() and (gg is None or gg.intact()), what
-    assert _same_bits(gp.cpu(), pred) and _same_bits(gx.cpu(), x0) and _same_bits(ge.cpu(), eps), what
+    assert same_bits(gp.cpu(), pred) and same_bits(gx.cpu(), x0) and same_bits(ge.cpu(), eps), what
     assert torch.equal(ab_d.cpu(), _alpha_bar()) and torch.equal(t_d.cpu(), t) and (w is None or torch.equal(w_d.cpu(), w)), what
     return out.cpu()[:1].clone(), (gg.cpu() if gg else None), (int(flag_d.item()) if flag else None)
 
@@ -169,14 +140,6 @@ def _case(B, P, kind, weighted):
     return pred, x0, eps, t, w, _ref(B, P, kind, pred, x0, eps, t, w)
 
 
-def _check_grad(got, ref, bound, what):
-    got = got.double().flatten()
-    assert torch.isfinite(got).all(), what
-    excess = (got - ref).abs() - bound
-    i = int(excess.argmax())
-    assert float(excess[i]) <= 0.0, (what, "element", i, float(got[i]), float(ref[i]), "bound", float(bound[i]))
-
-
 def _check_loss(got, ref, bound, what):
     got = float(got.double())
     print(what, "loss", got, "ref", ref, "err", abs(got - ref), "bound", bound)
@@ -190,7 +153,7 @@ def _one(hip, B, P, kind, weighted, want_grad, shifts=frozenset()):
     assert flag == 0, what
     _check_loss(loss, loss_ref, loss_bound, what)
     if want_grad:
-        _check_grad(grad, grad_ref, grad_bound, what)
+        check_bound(grad, grad_ref, grad_bound, what)
     return loss, grad
 
 
@@ -200,9 +163,9 @@ def test_loss_and_grad(hip, B, P, kind):
     for weighted in (False, True):
         with_grad = _one(hip, B, P, kind, weighted, True)
         without = _one(hip, B, P, kind, weighted, False)
-        assert _same_bits(with_grad[0], without[0]), (B, P, kind, weighted)       # grad == NULL changes nothing about the sum
+        assert same_bits(with_grad[0], without[0]), (B, P, kind, weighted)       # grad == NULL changes nothing about the sum
         again = _one(hip, B, P, kind, weighted, True)
-        assert _same_bits(again[0], with_grad[0]) and _same_bits(again[1], with_grad[1]), (B, P, kind, weighted)   # run to run
+        assert same_bits(again[0], with_grad[0]) and same_bits(again[1], with_grad[1]), (B, P, kind, weighted)   # run to run
 
 
 def test_weights_matter(hip):
@@ -213,8 +176,8 @@ def test_weights_matter(hip):
         lw, gw, _ = _run(hip, B, P, kind, pred, x0, eps, t, w, True)
         l1, g1, _ = _run(hip, B, P, kind, pred, x0, eps, t, None, True)
         lo, go, _ = _run(hip, B, P, kind, pred, x0, eps, t, torch.ones(T), True)
-        assert not _same_bits(lw, l1) and not _same_bits(gw, g1), kind
-        assert _same_bits(lo, l1) and _same_bits(go, g1), kind
+        assert not same_bits(lw, l1) and not same_bits(gw, g1), kind
+        assert same_bits(lo, l1) and same_bits(go, g1), kind
 
 
 @pytest.mark.parametrize("B,P", SHAPES + [BIG])
@@ -227,7 +190,7 @@ def test_epsilon_with_unit_weight_has_the_gradient_of_rho_mse_ws(hip, B, P):
     hip.check(hip.lib().rho_mse_ws(a.ptr, b.ptr, out.data_ptr(), g.ptr, n, out.data_ptr() + 4, NPART, hip.stream()), "rho_mse_ws")
     for w in (None, torch.ones(T)):
         loss, grad, _ = _run(hip, B, P, EPSILON, pred, x0, eps, t, w, True)
-        assert _same_bits(grad, g.cpu()), (B, P, w is not None)
+        assert same_bits(grad, g.cpu()), (B, P, w is not None)
         # the two losses are sums of the same terms in the same tree; rho_mse_ws leaves the contraction of d * d + sum to the
         # compiler, so only the bound is claimed
         _, (loss_ref, loss_bound, _, _) = _case(B, P, EPSILON, False)[4:]
@@ -242,14 +205,14 @@ def test_alignment(hip, B, P, kind):
     base = _one(hip, B, P, kind, True, True)
     for shifts in [frozenset([s]) for s in ("pred", "x0", "eps", "grad")] + [frozenset(("pred", "x0", "eps", "grad"))]:
         loss, grad = _one(hip, B, P, kind, True, True, shifts)
-        assert _same_bits(grad, base[1]), (B, P, kind, sorted(shifts))
+        assert same_bits(grad, base[1]), (B, P, kind, sorted(shifts))
 
 
 def test_alignment_at_the_large_size(hip):
     B, P = BIG
     base = _one(hip, B, P, V, True, True)
     loss, grad = _one(hip, B, P, V, True, True, frozenset(["x0"]))
-    assert _same_bits(grad, base[1])
+    assert same_bits(grad, base[1])
 
 
 @pytest.mark.parametrize("B,P", [(3, 5), (5, 257)])
@@ -263,12 +226,12 @@ def test_timestep_outside_the_table_sets_bit_2_and_reads_the_clamped_row(hip, B,
         loss, grad, flag = _run(hip, B, P, kind, pred, x0, eps, bad, w, True)
         assert flag == 4, (kind, flag)
         want_loss, want_grad, flag = _run(hip, B, P, kind, pred, x0, eps, clamped, w, True)
-        assert flag == 0 and _same_bits(loss, want_loss) and _same_bits(grad, want_grad), kind
+        assert flag == 0 and same_bits(loss, want_loss) and same_bits(grad, want_grad), kind
         loss_ref, loss_bound, grad_ref, grad_bound = _ref(B, P, kind, pred, x0, eps, clamped, w)
-        _check_grad(grad, grad_ref, grad_bound, ("clamped", B, P, kind))
+        check_bound(grad, grad_ref, grad_bound, ("clamped", B, P, kind))
         _check_loss(loss, loss_ref, loss_bound, ("clamped", B, P, kind))
         loss2, grad2, none = _run(hip, B, P, kind, pred, x0, eps, bad, w, True, flag=False)      # the flag is optional
-        assert none is None and _same_bits(loss2, loss) and _same_bits(grad2, grad)
+        assert none is None and same_bits(loss2, loss) and same_bits(grad2, grad)
 
 
 def test_bad_arguments_are_refused(hip):
@@ -285,7 +248,7 @@ def test_bad_arguments_are_refused(hip):
         args = list(ok)
         args[i] = v
         assert lib.rho_pred_loss_ws(*args, hip.stream()) == -1, i
-    assert float(out.abs().max()) == 0.0 and _same_bits(g.cpu(), pred)
+    assert float(out.abs().max()) == 0.0 and same_bits(g.cpu(), pred)
 
 
 def test_wrapper_and_autograd(hip):
@@ -300,13 +263,13 @@ def test_wrapper_and_autograd(hip):
     flag = torch.zeros(1, dtype=torch.int32, device=DEV)
     loss, grad = ops.pred_loss(pd, xd, ed, td, ab, wd, V, want_grad=True, err_flag=flag)
     raw_loss, raw_grad, _ = _run(hip, B, P, V, pred, x0, eps, t, w, True)
-    assert loss.shape == (1,) and grad.shape == shape and _same_bits(loss, raw_loss) and _same_bits(grad.flatten(), raw_grad)
+    assert loss.shape == (1,) and grad.shape == shape and same_bits(loss, raw_loss) and same_bits(grad.flatten(), raw_grad)
     assert ops.pred_loss(pd, xd, ed, td, ab, None, V)[1] is None and int(flag.item()) == 0
     leaf = pd.clone().requires_grad_(True)
     out = pred_loss(leaf, xd, ed, td, ab, wd, V, flag)
-    assert out.shape == () and _same_bits(out.detach().reshape(1), raw_loss)
+    assert out.shape == () and same_bits(out.detach().reshape(1), raw_loss)
     (3.0 * out).backward()                                       # the upstream gradient is applied on the device
-    _check_grad(leaf.grad.cpu() / 3.0, grad_ref, grad_bound + 2.0 * U * grad_ref.abs(), "autograd")
+    check_bound(leaf.grad.cpu() / 3.0, grad_ref, grad_bound + 2.0 * U * grad_ref.abs(), "autograd")
     for bad in (lambda: ops.pred_loss(pd.double(), xd, ed, td, ab, wd, V),
                 lambda: ops.pred_loss(pd, xd[:1].contiguous(), ed, td, ab, wd, V),
                 lambda: ops.pred_loss(pd, xd, ed, td.int(), ab, wd, V),

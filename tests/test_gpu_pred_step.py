@@ -33,13 +33,11 @@ import pytest
 import torch
 
 from helpers import det_normal
-from gpu_util import DEV
+from gpu_util import DEV, Guarded, check_bound, same_bits
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-PAD = 64
-SENT = -776.0                      # exact in float32
 T = 1000
 S = 50
 KS = [S - 1, 24, 1, 0]
@@ -88,33 +86,6 @@ def _inputs(n, row, kind):
     return x, pc, pu, _pool("z")[:n]
 
 
-class Guarded:
-    """A device copy of a 1-D CPU tensor placed ``shift`` elements past a 256-byte aligned address, PAD sentinels on either side."""
-
-    def __init__(self, src: torch.Tensor, shift: int = 0):
-        n = src.numel()
-        self.n, self.shift = n, shift
-        self.buf = torch.full((PAD + shift + n + PAD,), SENT, dtype=torch.float32, device=DEV)
-        self.v = self.buf[PAD + shift: PAD + shift + n]
-        self.v.copy_(src)
-        assert self.v.data_ptr() % 16 == (4 * shift) % 16
-
-    @property
-    def ptr(self) -> int:
-        return self.v.data_ptr()
-
-    def cpu(self) -> torch.Tensor:
-        return self.v.cpu()
-
-    def intact(self) -> bool:
-        lo, hi = self.buf[:PAD + self.shift], self.buf[PAD + self.shift + self.n:]
-        return hi.numel() == PAD and bool((lo == SENT).all()) and bool((hi == SENT).all())
-
-
-def _same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return torch.equal(a.cpu().contiguous().view(torch.int32), b.cpu().contiguous().view(torch.int32))
-
-
 def _run(hip, rows, k, x, pc, pu, z, scale, clip, kind, shifts=frozenset(), row1=None, expect=0):
     """Launch on guarded copies.  ``scale`` None: the plain form on (x, pc), returns [1, n]; else the guided form on [2, n] operands,
     returns [2, n].  Inputs must come back unchanged (z bit for bit, NaN payloads included), every sentinel intact."""
@@ -132,7 +103,7 @@ def _run(hip, rows, k, x, pc, pu, z, scale, clip, kind, shifts=frozenset(), row1
     res = gx.cpu().view(2 if guided else 1, n)
     what = (n, k, scale, clip, kind, sorted(shifts))
     assert gx.intact() and gp.intact() and (gz is None or gz.intact()), what
-    assert torch.equal(gp.cpu(), ps) and (gz is None or _same_bits(gz.cpu(), z)), what
+    assert torch.equal(gp.cpu(), ps) and (gz is None or same_bits(gz.cpu(), z)), what
     assert int(k_dev.item()) == k and torch.equal(rows_d.cpu(), rows), what
     return res
 
@@ -180,14 +151,6 @@ def _ref(row, x, pc, pu, z, scale, clip, kind):
     return r, 1.001 * U * terms, x0
 
 
-def _check(got, ref, bound, what):
-    got = got.double().cpu().flatten()
-    assert torch.isfinite(got).all(), what
-    excess = (got - ref).abs() - bound
-    i = int(excess.argmax())
-    assert float(excess[i]) <= 0.0, (what, "element", i, float(got[i]), float(ref[i]), "bound", float(bound[i]))
-
-
 def _one(hip, n, k, eta, with_z, clip, scale, kind, rows=None):
     rows = _rows(eta) if rows is None else rows
     x, pc, pu, z = _inputs(n, rows[k], kind)
@@ -195,15 +158,15 @@ def _one(hip, n, k, eta, with_z, clip, scale, kind, rows=None):
     got = _run(hip, rows, k, x, pc, pu, zz, scale, clip, kind)
     ref, bound, x0 = _ref(rows[k], x, pc, pu, zz, scale, clip, kind)
     what = ("p_sample_step_spaced_pred", KINDS[kind], n, k, eta, with_z, clip, scale)
-    _check(got[0], ref, bound, what)
+    check_bound(got[0], ref, bound, what)
     if scale is not None:
-        assert _same_bits(got[1], got[0]), what                # the second row is the first, bit for bit
+        assert same_bits(got[1], got[0]), what                # the second row is the first, bit for bit
     if n >= 255:
         bites = int((x0.abs() > 1.0).sum())
         assert 0 < bites < n, (what, bites)                     # the clamp is exercised on some elements, not on all
         assert (got[0] != x).any(), what
     if k == 0:                                                  # the last step returns the (clamped) x0 estimate
-        _check(got[0], x0.clamp(-1.0, 1.0) if clip else x0, bound, what + ("x0",))
+        check_bound(got[0], x0.clamp(-1.0, 1.0) if clip else x0, bound, what + ("x0",))
     return got
 
 
@@ -241,7 +204,7 @@ def test_last_step_does_not_read_z(hip, scale, kind):
         for clip in (1, 0):
             got = _run(hip, rows, k, x, pc, pu, nan_z, scale, clip, kind)
             assert torch.isfinite(got).all(), (eta, k, clip)
-            assert _same_bits(got, _run(hip, rows, k, x, pc, pu, None, scale, clip, kind)), (eta, k, clip)
+            assert same_bits(got, _run(hip, rows, k, x, pc, pu, None, scale, clip, kind)), (eta, k, clip)
     rows = _rows(1.0)
     x, pc, pu, _ = _inputs(n, rows[24], kind)
     assert torch.isnan(_run(hip, rows, 24, x, pc, pu, nan_z, scale, 1, kind)).all()
@@ -256,9 +219,9 @@ def test_k_outside_the_table_writes_nothing(hip, n, k):
         other = x + 1.0
         for zz in (z, None):
             got = _run(hip, rows, k, x, pc, pu, zz, None, 1, kind)
-            assert _same_bits(got[0], x), (n, k)
+            assert same_bits(got[0], x), (n, k)
             got = _run(hip, rows, k, x, pc, pu, zz, 3.0, 1, kind, row1=other)
-            assert _same_bits(got[0], x) and _same_bits(got[1], other), (n, k)
+            assert same_bits(got[0], x) and same_bits(got[1], other), (n, k)
 
 
 @pytest.mark.parametrize("n", [5, 1032])
@@ -269,7 +232,7 @@ def test_epsilon_and_unknown_types_are_refused(hip, n):
     for bad in (0, 3, -1):
         for scale in (None, 3.0):
             got = _run(hip, rows, 24, x, pc, pu, z, scale, 1, bad, expect=-1)
-            assert _same_bits(got[0], x), (n, bad, scale)
+            assert same_bits(got[0], x), (n, bad, scale)
     lib = hip.lib()
     g = Guarded(x)
     k_dev = torch.tensor([24], dtype=torch.int32, device=DEV)
@@ -278,7 +241,7 @@ def test_epsilon_and_unknown_types_are_refused(hip, n):
                  (g.ptr, g.ptr, None, None, k_dev.data_ptr(), S, n), (g.ptr, g.ptr, None, rd.data_ptr(), None, S, n),
                  (g.ptr, g.ptr, None, rd.data_ptr(), k_dev.data_ptr(), 0, n), (g.ptr, g.ptr, None, rd.data_ptr(), k_dev.data_ptr(), S, 0)):
         assert lib.rho_p_sample_step_spaced_pred(*args, 0, 0.0, 1, V, hip.stream()) == -1
-    assert _same_bits(g.cpu(), x) and g.intact()
+    assert same_bits(g.cpu(), x) and g.intact()
 
 
 @pytest.mark.parametrize("n,scale,kind", [(n, s, kd) for n in (1029, 1032) for s in (None, 3.0) for kd in (V, SAMPLE)]
@@ -291,14 +254,14 @@ def test_alignment(hip, n, scale, kind):
     x, pc, pu, z = _inputs(n, rows[k], kind)
     base = _run(hip, rows, k, x, pc, pu, z, scale, clip, kind)
     ref, bound, _ = _ref(rows[k], x, pc, pu, z, scale, clip, kind)
-    _check(base[0], ref, bound, ("aligned", n, scale))
+    check_bound(base[0], ref, bound, ("aligned", n, scale))
     for shifts in [frozenset([s]) for s in ("x", "pred", "z")] + [frozenset(("x", "pred", "z"))]:
         got = _run(hip, rows, k, x, pc, pu, z, scale, clip, kind, shifts)
-        assert _same_bits(got, base), (n, scale, sorted(shifts))
+        assert same_bits(got, base), (n, scale, sorted(shifts))
         if n < WRAP_VEC:
             for kk, cl in ((0, 0), (24, 0)):
                 got0 = _run(hip, rows, kk, x, pc, pu, z, scale, cl, kind, shifts)
-                assert _same_bits(got0, _run(hip, rows, kk, x, pc, pu, z, scale, cl, kind)), (n, scale, kk, sorted(shifts))
+                assert same_bits(got0, _run(hip, rows, kk, x, pc, pu, z, scale, cl, kind)), (n, scale, kk, sorted(shifts))
 
 
 @pytest.mark.parametrize("scale", [None, 3.0])
@@ -333,11 +296,11 @@ def test_wrapper_checks_dtypes_and_shapes(hip):
     shape = (3, 1, 16, 16)
     xd, pd, zd = x.view(shape).to(DEV), pc.view(shape).to(DEV), z.view(shape).to(DEV)
     out = ops.p_sample_step_spaced_pred(xd, pd, zd, rows, k_dev, V)
-    assert out is xd and _same_bits(xd.flatten(), _run(hip, rows_c, k, x, pc, pu, z, None, 1, V)[0])
+    assert out is xd and same_bits(xd.flatten(), _run(hip, rows_c, k, x, pc, pu, z, None, 1, V)[0])
     x2, p2 = torch.cat([x, x]).view(6, 1, 16, 16).to(DEV), torch.cat([pc, pu]).view(6, 1, 16, 16).to(DEV)
     out = ops.p_sample_step_spaced_pred(x2, p2, zd, rows, k_dev, SAMPLE, 3.0, clip=False)
     assert out is x2 and torch.equal(x2[:3], x2[3:])
-    assert _same_bits(x2.view(2, n), _run(hip, rows_c, k, x, pc, pu, z, 3.0, 0, SAMPLE))
+    assert same_bits(x2.view(2, n), _run(hip, rows_c, k, x, pc, pu, z, 3.0, 0, SAMPLE))
     xd = x.view(shape).to(DEV)
     for bad in (lambda: ops.p_sample_step_spaced_pred(xd.double(), pd, zd, rows, k_dev, V),
                 lambda: ops.p_sample_step_spaced_pred(xd, pd[:2].contiguous(), zd, rows, k_dev, V),
@@ -349,4 +312,4 @@ def test_wrapper_checks_dtypes_and_shapes(hip):
                 lambda: ops.p_sample_step_spaced_pred(x2, pd, zd, rows, k_dev, V, 3.0)):
         with pytest.raises(RhoHipError):
             bad()
-    assert _same_bits(xd.flatten(), x)                           # nothing was launched
+    assert same_bits(xd.flatten(), x)                           # nothing was launched

@@ -31,13 +31,11 @@ import pytest
 import torch
 
 from helpers import det_normal, det_uniform
-from gpu_util import DEV
+from gpu_util import DEV, Guarded, check_bound, same_bits
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-PAD = 64
-SENT = -776.0                      # exact in float32
 T = 1000
 S = 50
 KS = [S - 1, 24, 1, 0]
@@ -82,33 +80,6 @@ def _inputs(n, k):
     return x, ec, eu, _pool("z")[:n]
 
 
-class Guarded:
-    """A device copy of a 1-D CPU tensor placed ``shift`` elements past a 256-byte aligned address, PAD sentinels on either side."""
-
-    def __init__(self, src: torch.Tensor, shift: int = 0):
-        n = src.numel()
-        self.n, self.shift = n, shift
-        self.buf = torch.full((PAD + shift + n + PAD,), SENT, dtype=torch.float32, device=DEV)
-        self.v = self.buf[PAD + shift: PAD + shift + n]
-        self.v.copy_(src)
-        assert self.v.data_ptr() % 16 == (4 * shift) % 16
-
-    @property
-    def ptr(self) -> int:
-        return self.v.data_ptr()
-
-    def cpu(self) -> torch.Tensor:
-        return self.v.cpu()
-
-    def intact(self) -> bool:
-        lo, hi = self.buf[:PAD + self.shift], self.buf[PAD + self.shift + self.n:]
-        return hi.numel() == PAD and bool((lo == SENT).all()) and bool((hi == SENT).all())
-
-
-def _same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return torch.equal(a.cpu().contiguous().view(torch.int32), b.cpu().contiguous().view(torch.int32))
-
-
 def _run(hip, rows, k, x, ec, eu, z, scale, clip, shifts=frozenset(), row1=None):
     """Launch on guarded copies.  ``scale`` None: the plain form on (x, ec), returns [1, n]; else the guided form on [2, n] operands,
     returns [2, n].  Inputs must come back unchanged (z bit for bit, NaN payloads included), every sentinel intact."""
@@ -126,7 +97,7 @@ def _run(hip, rows, k, x, ec, eu, z, scale, clip, shifts=frozenset(), row1=None)
     res = gx.cpu().view(2 if guided else 1, n)
     what = (n, k, scale, clip, sorted(shifts))
     assert gx.intact() and ge.intact() and (gz is None or gz.intact()), what
-    assert torch.equal(ge.cpu(), es) and (gz is None or _same_bits(gz.cpu(), z)), what
+    assert torch.equal(ge.cpu(), es) and (gz is None or same_bits(gz.cpu(), z)), what
     assert int(k_dev.item()) == k and torch.equal(rows_d.cpu(), rows), what
     return res
 
@@ -167,14 +138,6 @@ def _ref(row, x, ec, eu, z, scale, clip):
     return r, 1.001 * U * terms, x0
 
 
-def _check(got, ref, bound, what):
-    got = got.double().cpu().flatten()
-    assert torch.isfinite(got).all(), what
-    excess = (got - ref).abs() - bound
-    i = int(excess.argmax())
-    assert float(excess[i]) <= 0.0, (what, "element", i, float(got[i]), float(ref[i]), "bound", float(bound[i]))
-
-
 def _one(hip, n, k, eta, with_z, clip, scale):
     rows = _rows(eta)
     x, ec, eu, z = _inputs(n, k)
@@ -182,15 +145,15 @@ def _one(hip, n, k, eta, with_z, clip, scale):
     got = _run(hip, rows, k, x, ec, eu, zz, scale, clip)
     ref, bound, x0 = _ref(rows[k], x, ec, eu, zz, scale, clip)
     what = ("p_sample_step_spaced", n, k, eta, with_z, clip, scale)
-    _check(got[0], ref, bound, what)
+    check_bound(got[0], ref, bound, what)
     if scale is not None:
-        assert _same_bits(got[1], got[0]), what                # the second row is the first, bit for bit
+        assert same_bits(got[1], got[0]), what                # the second row is the first, bit for bit
     if n >= 255:
         bites = int((x0.abs() > 1.0).sum())
         assert 0 < bites < n, (what, bites)                     # the clamp is exercised on some elements, not on all
         assert (got[0] != x).any(), what
     if k == 0:                                                  # the last step returns the (clamped) x0 estimate
-        _check(got[0], x0.clamp(-1.0, 1.0) if clip else x0, bound, what + ("x0",))
+        check_bound(got[0], x0.clamp(-1.0, 1.0) if clip else x0, bound, what + ("x0",))
     return got
 
 
@@ -224,7 +187,7 @@ def test_last_step_does_not_read_z(hip, scale):
         for clip in (1, 0):
             got = _run(hip, _rows(eta), k, x, ec, eu, nan_z, scale, clip)
             assert torch.isfinite(got).all(), (eta, k, clip)
-            assert _same_bits(got, _run(hip, _rows(eta), k, x, ec, eu, None, scale, clip)), (eta, k, clip)
+            assert same_bits(got, _run(hip, _rows(eta), k, x, ec, eu, None, scale, clip)), (eta, k, clip)
     x, ec, eu, _ = _inputs(n, 24)                               # and where noise enters, the NaNs do arrive: z is read there
     assert torch.isnan(_run(hip, _rows(1.0), 24, x, ec, eu, nan_z, scale, 1)).all()
 
@@ -236,9 +199,9 @@ def test_k_outside_the_table_writes_nothing(hip, n, k):
     other = x + 1.0
     for zz in (z, None):
         got = _run(hip, _rows(1.0), k, x, ec, eu, zz, None, 1)
-        assert _same_bits(got[0], x), (n, k)
+        assert same_bits(got[0], x), (n, k)
         got = _run(hip, _rows(1.0), k, x, ec, eu, zz, 3.0, 1, row1=other)
-        assert _same_bits(got[0], x) and _same_bits(got[1], other), (n, k)
+        assert same_bits(got[0], x) and same_bits(got[1], other), (n, k)
 
 
 @pytest.mark.parametrize("n", [1029, 1032, WRAP_VEC])
@@ -250,13 +213,13 @@ def test_alignment(hip, n, scale):
     rows = _rows(1.0)
     base = _run(hip, rows, k, x, ec, eu, z, scale, clip)
     ref, bound, _ = _ref(rows[k], x, ec, eu, z, scale, clip)
-    _check(base[0], ref, bound, ("aligned", n, scale))
+    check_bound(base[0], ref, bound, ("aligned", n, scale))
     for shifts in [frozenset([s]) for s in ("x", "eps", "z")] + [frozenset(("x", "eps", "z"))]:
         got = _run(hip, rows, k, x, ec, eu, z, scale, clip, shifts)
-        assert _same_bits(got, base), (n, scale, sorted(shifts))
+        assert same_bits(got, base), (n, scale, sorted(shifts))
         if n < WRAP_VEC:
             got0 = _run(hip, rows, 0, x, ec, eu, z, scale, 0, shifts)
-            assert _same_bits(got0, _run(hip, rows, 0, x, ec, eu, z, scale, 0)), (n, scale, sorted(shifts))
+            assert same_bits(got0, _run(hip, rows, 0, x, ec, eu, z, scale, 0)), (n, scale, sorted(shifts))
 
 
 @pytest.mark.parametrize("scale", [None, 3.0])
@@ -278,10 +241,10 @@ def test_degenerate_rows_of_the_cosine_schedule(hip, scale):
                 got = _run(hip, rows, k, x, ec, eu, zz, scale, 1)
                 assert torch.isfinite(got).all() and float(got.abs().max()) <= 1.0, (eta, k, zz is not None)
                 if scale is not None:
-                    assert _same_bits(got[0], got[1])
+                    assert same_bits(got[0], got[1])
         # t = 0: the update is the clamp of x itself (c_recip = 1, c_recipm1 = 0)
         got = _run(hip, rows, 0, x, ec, eu, z, scale, 1)
-        assert _same_bits(got[0], x)
+        assert same_bits(got[0], x)
 
 
 def test_spaced_advance(hip):
@@ -321,11 +284,11 @@ def test_wrappers_check_dtypes_and_shapes(hip):
     shape = (3, 1, 16, 16)
     xd, ed, zd = x.view(shape).to(DEV), ec.view(shape).to(DEV), z.view(shape).to(DEV)
     out = ops.p_sample_step_spaced(xd, ed, zd, rows, k_dev)
-    assert out is xd and _same_bits(xd.flatten(), _run(hip, _rows(1.0), k, x, ec, eu, z, None, 1)[0])
+    assert out is xd and same_bits(xd.flatten(), _run(hip, _rows(1.0), k, x, ec, eu, z, None, 1)[0])
     x2, e2 = torch.cat([x, x]).view(6, 1, 16, 16).to(DEV), torch.cat([ec, eu]).view(6, 1, 16, 16).to(DEV)
     out = ops.p_sample_step_spaced(x2, e2, zd, rows, k_dev, 3.0, clip=False)
     assert out is x2 and torch.equal(x2[:3], x2[3:])
-    assert _same_bits(x2.view(2, n), _run(hip, _rows(1.0), k, x, ec, eu, z, 3.0, 0))
+    assert same_bits(x2.view(2, n), _run(hip, _rows(1.0), k, x, ec, eu, z, 3.0, 0))
     xd = x.view(shape).to(DEV)
     for bad in (lambda: ops.p_sample_step_spaced(xd.double(), ed, zd, rows, k_dev),
                 lambda: ops.p_sample_step_spaced(xd, ed[:2].contiguous(), zd, rows, k_dev),
@@ -339,7 +302,7 @@ def test_wrappers_check_dtypes_and_shapes(hip):
                 lambda: ops.p_sample_step_spaced(xd[:, :, :, :15], ed, zd, rows, k_dev)):
         with pytest.raises(RhoHipError):
             bad()
-    assert _same_bits(xd.flatten(), x)                           # nothing was launched
+    assert same_bits(xd.flatten(), x)                           # nothing was launched
     taus = torch.tensor([3, 11, 17], dtype=torch.int32, device=DEV)
     t_dev = torch.tensor([17], dtype=torch.int32, device=DEV)
     off = torch.zeros(1, dtype=torch.int64, device=DEV)

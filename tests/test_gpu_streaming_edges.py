@@ -15,13 +15,11 @@ import pytest
 import torch
 
 from helpers import det_normal, rel_l2
-from gpu_util import DEV
+from gpu_util import DEV, Guarded, bits, check_bound, same_bits
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24                     # unit roundoff of float32: one correctly rounded operation errs by at most U * |result|
-PAD = 64
-SENT = -776.0                      # exact in float32 and bfloat16; no kernel below produces it from these inputs
 SMALL = [1, 3, 4, 5, 255, 257, 1029]
 WRAP4 = 2_100_227                  # > 2048 * 256 * 4: second trip of a 4-wide kernel, 3-element tail
 WRAP1 = 525_065                    # > 2048 * 256: second trip of a scalar kernel
@@ -43,54 +41,6 @@ def _pool(salt: str) -> torch.Tensor:
 
 def _data(salt: str, n: int) -> torch.Tensor:
     return _pool(salt)[:n]
-
-
-class Guarded:
-    """A device copy of a 1-D CPU tensor (or n NaNs) placed ``shift`` elements past a 256-byte aligned address, with at least PAD
-    sentinel elements on either side."""
-
-    def __init__(self, src, shift: int = 0, dtype=torch.float32):
-        n = src if isinstance(src, int) else src.numel()
-        dtype = dtype if isinstance(src, int) else src.dtype
-        self.n, self.shift = n, shift
-        self.buf = torch.full((PAD + shift + n + PAD,), SENT, dtype=dtype, device=DEV)
-        self.v = self.buf[PAD + shift: PAD + shift + n]
-        if isinstance(src, int):
-            self.v.fill_(float("nan"))
-        else:
-            self.v.copy_(src)
-        assert self.v.data_ptr() % 16 == (shift * self.buf.element_size()) % 16
-
-    @property
-    def ptr(self) -> int:
-        return self.v.data_ptr()
-
-    def cpu(self) -> torch.Tensor:
-        return self.v.cpu()
-
-    def intact(self) -> bool:
-        lo, hi = self.buf[:PAD + self.shift], self.buf[PAD + self.shift + self.n:]
-        return hi.numel() == PAD and bool((lo == SENT).all()) and bool((hi == SENT).all())
-
-
-def _bits(t: torch.Tensor) -> torch.Tensor:
-    return t.cpu().contiguous().view(torch.int32 if t.element_size() == 4 else torch.int16)
-
-
-def _same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _check(got: torch.Tensor, ref: torch.Tensor, bound: torch.Tensor, rel_bar, what):
-    """Per-element |got - ref| <= bound (float64 tensors), then rel-L2 < rel_bar."""
-    got = got.double().cpu().flatten()
-    ref, bound = ref.flatten(), bound.flatten()
-    assert torch.isfinite(got).all(), what
-    excess = (got - ref).abs() - bound
-    i = int(excess.argmax())
-    assert float(excess[i]) <= 0.0, (what, "element", i, float(got[i]), float(ref[i]), "bound", float(bound[i]))
-    if rel_bar is not None:
-        assert rel_l2(got, ref) < rel_bar, what
 
 
 def _shift_sets(names):
@@ -164,7 +114,7 @@ def test_q_sample_sizes(hip, which, B, per):
     x0, eps, t = _data("qx0", B * per) * 0.5 + 0.5, _data("qeps", B * per), _timesteps(B)
     got = _q_run(hip, which, x0, eps, t, B, per)
     ref, bound = _q_ref(which, x0, eps, t, B, per)
-    _check(got, ref, bound, 1e-6, (which, B, per))
+    check_bound(got, ref, bound, (which, B, per), 1e-6)
 
 
 # 1029 and 2100227 elements (odd: the scalar kernel either way); per_sample % 4 == 0 at 1032 elements and at the wrap shape, where
@@ -176,10 +126,10 @@ def test_q_sample_alignment(hip, B, per):
     x0, eps, t = _data("qx0", B * per) * 0.5 + 0.5, _data("qeps", B * per), _timesteps(B)
     base = _q_run(hip, "q_sample", x0, eps, t, B, per)
     ref, bound = _q_ref("q_sample", x0, eps, t, B, per)
-    _check(base, ref, bound, 1e-6, ("aligned", B, per))
+    check_bound(base, ref, bound, ("aligned", B, per), 1e-6)
     for shifts in _shift_sets(["x0", "eps", "out"]):
         got = _q_run(hip, "q_sample", x0, eps, t, B, per, shifts)
-        assert _same_bits(got, base), (B, per, sorted(shifts))
+        assert same_bits(got, base), (B, per, sorted(shifts))
 
 
 # ----------------------------------------------------------------------------- p_sample_step
@@ -220,22 +170,22 @@ def test_p_sample_step_sizes(hip, n):
     for t, zz in ((500, z), (1, z), (500, None), (2, z)):
         got = _p_run(hip, x, eh, zz, t)
         ref, bound = _p_ref(x, eh, zz, t)
-        _check(got, ref, bound, 2e-6, ("p_sample_step", n, t, zz is not None))
+        check_bound(got, ref, bound, ("p_sample_step", n, t, zz is not None), 2e-6)
         assert (got != x).any()
-    assert _same_bits(_p_run(hip, x, eh, z, 0), x)                            # t = 0: no update
-    assert _same_bits(_p_run(hip, x, eh, None, 0), x)
+    assert same_bits(_p_run(hip, x, eh, z, 0), x)                            # t = 0: no update
+    assert same_bits(_p_run(hip, x, eh, None, 0), x)
 
 
 @pytest.mark.parametrize("n", [1029, WRAP4])
 def test_p_sample_step_alignment(hip, n):
-    """The 4-byte-aligned fallback against the 16-byte body + tail: the same bits (all three evaluate p_update)."""
+    """The 4-byte-aligned fallback against the 16-byte body + tail: the same bits (all are loops of step_walk over PSampleOp)."""
     x, eh, z = _data("px", n) * 0.7, _data("pe", n), _data("pz", n)
     base = _p_run(hip, x, eh, z, 500)
     ref, bound = _p_ref(x, eh, z, 500)
-    _check(base, ref, bound, 2e-6, ("aligned", n))
+    check_bound(base, ref, bound, ("aligned", n), 2e-6)
     for shifts in _shift_sets(["x", "eh", "z"]):
-        assert _same_bits(_p_run(hip, x, eh, z, 500, shifts), base), (n, sorted(shifts))
-        assert _same_bits(_p_run(hip, x, eh, z, 0, shifts), x), (n, sorted(shifts))
+        assert same_bits(_p_run(hip, x, eh, z, 500, shifts), base), (n, sorted(shifts))
+        assert same_bits(_p_run(hip, x, eh, z, 0, shifts), x), (n, sorted(shifts))
 
 
 # ----------------------------------------------------------------------------- mse (scratch of its own), mse_ws (caller's scratch)
@@ -272,13 +222,13 @@ def test_mse_sizes(hip, form, n):
     loss, grad = _mse_run(hip, form, a, b)
     print(f"{form} n={n}: |loss - ref| = {abs(loss - ref_loss):.3e}")
     assert abs(loss - ref_loss) < 1e-6, (form, n, loss, ref_loss)
-    _check(grad, ref_grad, bound, 1e-6, (form, n))
+    check_bound(grad, ref_grad, bound, (form, n), 1e-6)
     loss2, none = _mse_run(hip, form, a, b, want_grad=False)                  # the loss alone
     assert none is None and abs(loss2 - ref_loss) < 1e-6
     if form == "mse_ws":
         assert loss2 == loss                                                  # ordered reduction: the same bits with and without grad
         l3, g3 = ops.mse(a.to(DEV), b.to(DEV), want_grad=True)                # the wrapper the pipelines call
-        assert float(l3.item()) == loss and _same_bits(g3, grad)
+        assert float(l3.item()) == loss and same_bits(g3, grad)
 
 
 @pytest.mark.parametrize("n", [1029, WRAP4])
@@ -291,8 +241,8 @@ def test_mse_ws_alignment(hip, n):
     for shifts in _shift_sets(["a", "b", "grad"]):
         loss, grad = _mse_run(hip, "mse_ws", a, b, shifts)
         assert abs(loss - ref_loss) < 1e-6, (n, sorted(shifts), loss, ref_loss)
-        assert _same_bits(grad, base), (n, sorted(shifts))
-    _check(base, ref_grad, bound, 1e-6, ("aligned", n))
+        assert same_bits(grad, base), (n, sorted(shifts))
+    check_bound(base, ref_grad, bound, ("aligned", n), 1e-6)
 
 
 # ----------------------------------------------------------------------------- mean_flat
@@ -307,9 +257,9 @@ def test_mean_flat_sizes(hip, B, per):
     assert out.intact() and gx.intact() and torch.equal(gx.cpu(), x)
     xd = x.double().view(B, per)
     k = math.ceil(per / 256) + 8
-    _check(out.cpu(), xd.mean(1), k * U * xd.abs().mean(1), None, ("mean_flat", B, per))
+    check_bound(out.cpu(), xd.mean(1), k * U * xd.abs().mean(1), ("mean_flat", B, per))
     from rho_diffusion_amd.engine import ops
-    assert _same_bits(ops.mean_flat(x.view(B, per).to(DEV)), out.cpu())       # fixed summation order: reproducible bits
+    assert same_bits(ops.mean_flat(x.view(B, per).to(DEV)), out.cpu())       # fixed summation order: reproducible bits
 
 
 # ----------------------------------------------------------------------------- adamw
@@ -343,9 +293,9 @@ def test_adamw_sizes(hip, n):
         upd_abs = (lr / bc1) * m_abs / denom
         ep = ep + 4 * U * p.abs() + 29 * U * upd_abs
         p = p * (1 - lr * wd) - (lr / bc1) * m / denom
-        _check(gm.cpu(), m, em, 1e-6, ("adamw m", n, step))
-        _check(gv.cpu(), v, ev, 1e-6, ("adamw v", n, step))
-        _check(gp.cpu(), p, ep, 1e-6, ("adamw p", n, step))
+        check_bound(gm.cpu(), m, em, ("adamw m", n, step), 1e-6)
+        check_bound(gv.cpu(), v, ev, ("adamw v", n, step), 1e-6)
+        check_bound(gp.cpu(), p, ep, ("adamw p", n, step), 1e-6)
     assert rel_l2(gp.cpu(), p0) > 1e-4                                        # the parameters moved
 
 
@@ -373,7 +323,7 @@ def test_ema_update_sizes(hip, n):
     s, p = _data("ema_s", n), _data("ema_p", n)
     got, ref = _ema_run(hip, s, p), _ema_ref(s, p)
     assert ref.dtype == torch.float32 and not torch.equal(ref, s)
-    assert _same_bits(got, ref), (n, int((_bits(got) != _bits(ref)).sum()))
+    assert same_bits(got, ref), (n, int((bits(got) != bits(ref)).sum()))
 
 
 @pytest.mark.parametrize("n", [1029, WRAP4])
@@ -381,7 +331,7 @@ def test_ema_update_alignment(hip, n):
     s, p = _data("ema_s", n), _data("ema_p", n)
     ref = _ema_ref(s, p)
     for shifts in [frozenset()] + _shift_sets(["shadow", "param"]):
-        assert _same_bits(_ema_run(hip, s, p, shifts), ref), (n, sorted(shifts))
+        assert same_bits(_ema_run(hip, s, p, shifts), ref), (n, sorted(shifts))
 
 
 # ----------------------------------------------------------------------------- add_inplace
@@ -400,16 +350,16 @@ def test_add_inplace_sizes(hip, dtype, n):
         dst, src = Guarded(_data("add_d", n).to(dtype)), Guarded(_data("add_s", n).to(dtype))
         before = dst.cpu()
         assert L.rho_add_inplace(dst.ptr, src.ptr, code, n, hip.stream()) == -1            # RHO_E_ARG
-        assert _same_bits(dst.cpu(), before) and dst.intact()
+        assert same_bits(dst.cpu(), before) and dst.intact()
         n = (n + pe - 1) // pe * pe
     d0 = torch.cat([_data("add_d", min(n, POOL)), _data("add_d2", n - min(n, POOL))]).to(dtype)
     s0 = torch.cat([_data("add_s", min(n, POOL)), _data("add_s2", n - min(n, POOL))]).to(dtype)
     dst, src = Guarded(d0), Guarded(s0)
     hip.check(L.rho_add_inplace(dst.ptr, src.ptr, code, n, hip.stream()), "rho_add_inplace")
-    assert dst.intact() and src.intact() and _same_bits(src.cpu(), s0)
+    assert dst.intact() and src.intact() and same_bits(src.cpu(), s0)
     ref = (d0.float() + s0.float()).to(dtype)
-    assert _same_bits(dst.cpu(), ref), (n, int((_bits(dst.cpu()) != _bits(ref)).sum()))
-    assert not _same_bits(ref, d0)
+    assert same_bits(dst.cpu(), ref), (n, int((bits(dst.cpu()) != bits(ref)).sum()))
+    assert not same_bits(ref, d0)
 
 
 # ----------------------------------------------------------------------------- scale_by_device_scalar
@@ -420,4 +370,4 @@ def test_scale_by_device_scalar_sizes(hip, n):
     gx, gs = Guarded(x), Guarded(sc)
     hip.check(hip.lib().rho_scale_by_device_scalar(gx.ptr, gs.ptr, n, hip.stream()), "rho_scale_by_device_scalar")
     assert gx.intact() and gs.intact() and torch.equal(gs.cpu(), sc)
-    assert _same_bits(gx.cpu(), x * sc)                                       # one float32 product per element
+    assert same_bits(gx.cpu(), x * sc)                                       # one float32 product per element
