@@ -744,7 +744,8 @@ int rho_gn_apply(const void* x1, int64_t c1, const void* x2, int64_t c2, int dty
  * Dynamic thresholding, gaussian_diffusion.py:400-415: out[b] = torch.quantile(|x[b, :]|, q) ("linear"
  * interpolation, evaluated in float32 exactly as ATen does: rank = float(q) * float(n-1), floor / ceil order
  * statistics found EXACTLY by a radix select, then lerp).  x: float32 [batch, n] contiguous; workspace: at least
- * rho_abs_quantile_workspace_bytes(batch) bytes of device memory (contents undefined on entry). */
+ * rho_abs_quantile_workspace_bytes(batch) bytes of device memory (contents undefined on entry).  x at any alignment: the
+ * 16-byte loads need a 16-byte aligned x and n (and stride) % 4 == 0; every other case gives the same bits. */
 int64_t rho_abs_quantile_workspace_bytes(int64_t batch);
 int rho_abs_quantile(const float* x, int64_t batch, int64_t n, double q, void* workspace, float* out, void* stream);
 /* The same over rows that start stride >= n elements apart (ABI 10: the mean half of a learned-variance output, stride = 2n). */
@@ -876,7 +877,9 @@ int rho_gd_vlb_terms_lv(const float* x_start, const float* x_t, const float* mod
  *   loss[b] = mse[b] + vb[b]        (mse, vb may be NULL; fixed-order two-stage reduction, bit-reproducible)
  * Backward, grad [batch, 2*per_sample]: the mean half -((g_m/n) * (2*(target - m))) with g_m = g_loss + g_mse (the VLB sees a detached
  * mean: exactly 0 there), the variance half (g_v*scale/ln2/n) * d term/d logvar * d logvar/d v with g_v = g_loss + g_vb; at t == 0
- * through the tanh CDF, zero where a 1e-12 clamp cuts the path.  g_loss / g_mse / g_vb [batch], each may be NULL (= 0). */
+ * through the tanh CDF, zero where a 1e-12 clamp cuts the path.  g_loss / g_mse / g_vb [batch], each may be NULL (= 0).
+ * Any alignment: the 16-byte form needs per_sample % 4 == 0 and 16-byte aligned x_start / x_t / target / model_out (/ grad); every
+ * other case takes the scalar form (the same gradient bits; the per-sample sums in another fixed order). */
 int rho_gd_hybrid_loss(const float* x_start, const float* x_t, const float* target, const float* model_out, const int64_t* t,
                        const float* tab, int64_t table_len, int mean_type, int var_type, int rescaled, float vb_scale, float* loss,
                        float* mse, float* vb, void* workspace, int64_t batch, int64_t per_sample, int32_t* err_flag, void* stream);

@@ -544,7 +544,7 @@ extern "C" int rho_gd_vlb_terms_lv(const float* x_start, const float* x_t, const
 //   vb[b]   = _vb_terms_bpd(frozen m, v; clip_denoised=False) (* vb_scale = T/1000 for RESCALED_MSE);  loss = mse + vb
 // Only the term where(t == 0, nll, kl) selects is evaluated.  Backward: the mean half gets the MSE gradient only (the reference
 // detaches m for the VLB), the variance half g_vb / ln2 / n * d term / d logvar * d logvar / d v.
-// Pure streaming passes: 16-byte loads when per_sample % 4 == 0 (then every row of both halves is 16-byte aligned).
+// Pure streaming passes: 16-byte loads when per_sample % 4 == 0 and every base pointer is 16-byte aligned (gd_hyb_vec), else scalar.
 namespace {
 constexpr int GD_HYB_K = 2;
 
@@ -738,6 +738,13 @@ __global__ __launch_bounds__(GD_THREADS) void k_gd_hybrid_bwd(const float* __res
 
 namespace {
 int64_t gd_hyb_chunks(int64_t batch, int64_t per_sample, int v) { return gd_chunks(batch, (per_sample + v - 1) / v); }
+// the 16-byte path: per_sample % 4 == 0 (then every row of both halves is as aligned as its base) and every base 16-byte aligned
+bool gd_hyb_vec(int64_t per_sample, std::initializer_list<const void*> bases) {
+    if ((per_sample & 3) != 0) return false;
+    for (const void* p : bases)
+        if (((uintptr_t)p & 15) != 0) return false;
+    return true;
+}
 }  // namespace
 
 extern "C" int rho_gd_hybrid_loss(const float* x_start, const float* x_t, const float* target, const float* model_out, const int64_t* t,
@@ -746,7 +753,7 @@ extern "C" int rho_gd_hybrid_loss(const float* x_start, const float* x_t, const 
     if (!x_start || !x_t || !target || !model_out || !t || !tab || !loss || !workspace) return RHO_E_ARG;
     if (batch <= 0 || per_sample <= 0 || table_len <= 0 || !gd_lv_ok(mean_type, var_type)) return RHO_E_ARG;
     if (batch > 65535) return RHO_E_SHAPE;
-    const int v = (per_sample & 3) == 0 ? 4 : 1;
+    const int v = gd_hyb_vec(per_sample, {x_start, x_t, target, model_out}) ? 4 : 1;
     const int64_t chunks = gd_hyb_chunks(batch, per_sample, v);      // <= gd_chunks(batch, per_sample): the workspace of the VLB pass fits
     hipStream_t st = as_stream(stream);
     dim3 grid((unsigned)chunks, (unsigned)batch);
@@ -770,7 +777,7 @@ extern "C" int rho_gd_hybrid_loss_bwd(const float* x_start, const float* x_t, co
     if (!x_start || !x_t || !target || !model_out || !t || !tab || !grad) return RHO_E_ARG;
     if (batch <= 0 || per_sample <= 0 || table_len <= 0 || !gd_lv_ok(mean_type, var_type)) return RHO_E_ARG;
     if (batch > 65535) return RHO_E_SHAPE;
-    const int v = (per_sample & 3) == 0 ? 4 : 1;
+    const int v = gd_hyb_vec(per_sample, {x_start, x_t, target, model_out, grad}) ? 4 : 1;
     dim3 grid((unsigned)gd_hyb_chunks(batch, per_sample, v), (unsigned)batch);
     hipStream_t st = as_stream(stream);
     const int em = mean_type == RHO_GD_EPSILON ? 1 : 0, rg = var_type == RHO_GD_LEARNED_RANGE ? 1 : 0;

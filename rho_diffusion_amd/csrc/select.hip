@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void k_sel_init(uint32_t* __restrict__ ws, int
 }
 
 template <int PASS>
-__global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ x, int64_t N, int64_t stride, int64_t B, uint32_t* __restrict__ ws) {
+__global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ x, int64_t N, int64_t stride, int64_t B, int vec4, uint32_t* __restrict__ ws) {
     constexpr int SHIFT = 24 - 8 * PASS;
     __shared__ uint32_t h[2][SEL_BINS];
     const int b = blockIdx.y;
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ x, i
     };
     const int64_t per = (N + gridDim.x - 1) / gridDim.x;
     int64_t i0 = (int64_t)blockIdx.x * per, i1 = i0 + per < N ? i0 + per : N;
-    if ((N & 3) == 0 && (stride & 3) == 0 && (per & 3) == 0) {     // 16-byte pieces (rows are 16-byte aligned when N, stride % 4 == 0)
+    if (vec4 && (per & 3) == 0) {     // 16-byte pieces (the host passes vec4 only where every row starts 16-byte aligned)
         for (int64_t i = i0 + 4 * tid; i < i1; i += 4 * 256) {
             const float4 v = *reinterpret_cast<const float4*>(xb + i);
             tally(v.x); tally(v.y); tally(v.z); tally(v.w);
@@ -83,6 +83,9 @@ __global__ __launch_bounds__(256) void k_sel_pick(uint32_t* __restrict__ ws, int
     const uint32_t* g = ws + (((size_t)PASS * B + b) * 2) * SEL_BINS;
 #pragma unroll
     for (int sel = 0; sel < 2; ++sel) cum[sel][tid] = g[sel * SEL_BINS + tid];
+    // both ranks into registers before the scan's barriers: the matching thread below overwrites st[2 + sel], and a wave that read it
+    // only then would see the reduced rank
+    const uint32_t ranks[2] = {st[2], st[3]};
     __syncthreads();
     // inclusive scan (Hillis-Steele, 256 entries x 2)
     for (int off = 1; off < SEL_BINS; off <<= 1) {
@@ -95,7 +98,7 @@ __global__ __launch_bounds__(256) void k_sel_pick(uint32_t* __restrict__ ws, int
     }
 #pragma unroll
     for (int sel = 0; sel < 2; ++sel) {
-        const uint32_t rank = st[2 + sel];
+        const uint32_t rank = ranks[sel];
         const uint32_t incl = cum[sel][tid], excl = tid ? cum[sel][tid - 1] : 0u;
         if (excl <= rank && rank < incl) {            // exactly one bin (the counts of the prefix bucket sum to > rank)
             st[sel] |= (uint32_t)tid << SHIFT;
@@ -138,8 +141,10 @@ int abs_quantile(const float* x, int64_t batch, int64_t n, int64_t stride, doubl
     if (nblk > 128) nblk = 128;
     if (nblk < 1) nblk = 1;
     dim3 gh((unsigned)nblk, (unsigned)batch), gp((unsigned)batch);
+    // 16-byte loads only where every row starts 16-byte aligned: the base itself, and n and stride multiples of 4
+    const int vec4 = (n & 3) == 0 && (stride & 3) == 0 && ((uintptr_t)x & 15) == 0 ? 1 : 0;
 #define RHO_SEL_PASS(P)                                                                      \
-    hipLaunchKernelGGL(k_sel_hist<P>, gh, dim3(256), 0, st, x, n, stride, batch, ws);          \
+    hipLaunchKernelGGL(k_sel_hist<P>, gh, dim3(256), 0, st, x, n, stride, batch, vec4, ws);    \
     hipLaunchKernelGGL(k_sel_pick<P>, gp, dim3(256), 0, st, ws, batch, weight, out);
     RHO_SEL_PASS(0)
     RHO_SEL_PASS(1)

@@ -169,7 +169,8 @@ def _sample_rows(v: Tensor, name: str, batch: int, n: int) -> int:
 
 def abs_quantile(x: Tensor, q: float, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
     """Per-sample torch.quantile(|x|.flatten(1), q) (float32, linear interpolation), exact radix select on the device.  ``x`` is any
-    per-sample view (``_sample_rows``), read in place: e.g. the mean half of a learned-variance output."""
+    per-sample view (``_sample_rows``), read in place: e.g. the mean half of a learned-variance output.  Any storage offset: the 16-byte
+    loads are taken only where the base is 16-byte aligned (the same bits either way)."""
     B = x.shape[0]
     n = x.numel() // B
     stride = _sample_rows(x, "x", B, n)
