@@ -15,7 +15,7 @@
 // with V^T read as plain 16-byte rows of 8 consecutive keys (A operand) -- no transposes, no LDS
 // round trip for P (cdna_hip_programming.md section 3, "An accumulator tile as the next MFMA's operand").
 #include "attention_plan.h"
-#include "common.h"
+#include "attention_tiles.h"
 
 // max / sum of a value over the two half-waves of a column (lanes l and l ^ 32), in every lane: one v_permlane32_swap (gfx950: the
 // operand pair comes back as {x[l & 31], x[(l & 31) + 32]}) instead of a ds_bpermute round trip through the LDS crossbar and the
@@ -66,8 +66,7 @@ __global__ __launch_bounds__(256, CH <= 128 ? 2 : 1) void k_attn_bf16(const bf16
         for (int r = 0; r < 16; ++r) o[ct][r] = 0.0f;
     float m_run = -INFINITY, l_run = 0.0f;
 
-    // permuted K row for the A operand: swap bits 2 and 3 of the tile row
-    const int prow = (col & 0x13) | ((col & 4) << 1) | ((col & 8) >> 1);
+    const int prow = pi_row(col);     // permuted K row for the A operand
     const bool vec_v = ((T & 7) == 0);
 
     // staging addresses: thread -> (row, 16-byte piece), fixed for the whole key walk; only the tile origin moves
@@ -191,8 +190,7 @@ __global__ __launch_bounds__(256, CH <= 128 ? 2 : 1) void k_attn_bf16(const bf16
                 for (int g = 0; g < KG; ++g) a[g] = *reinterpret_cast<const uint4*>(kp + 32 * (k0 + g));
 #pragma unroll
                 for (int g = 0; g < KG; ++g)
-                    s[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[g]),
-                                                                  __builtin_bit_cast(bf16x8_t, qf[k0 + g]), s[u], 0, 0, 0);
+                    s[u] = mma_bf16(a[g], qf[k0 + g], s[u]);
             }
         }
         // ---- online softmax (base-2).  Only the last, partial tile needs the key mask (uniform branch).
@@ -202,8 +200,7 @@ __global__ __launch_bounds__(256, CH <= 128 ? 2 : 1) void k_attn_bf16(const bf16
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = (r & 3) + 8 * (r >> 2) + 4 * half;               // accumulator row
-                    const int krow = (row & 0x13) | ((row & 4) << 1) | ((row & 8) >> 1);  // key held there (pi)
-                    if (kt0 + 32 * u + krow >= T) s[u][r] = -INFINITY;
+                    if (kt0 + 32 * u + pi_row(row) >= T) s[u][r] = -INFINITY;        // pi(row): the key held there
                 }
         }
         float mx = s[0][0];
@@ -241,16 +238,11 @@ __global__ __launch_bounds__(256, CH <= 128 ? 2 : 1) void k_attn_bf16(const bf16
         for (int u = 0; u < NU; ++u)
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                uint4 pb;
-                pb.x = pack_bf16x2(s[u][8 * st + 0], s[u][8 * st + 1]);
-                pb.y = pack_bf16x2(s[u][8 * st + 2], s[u][8 * st + 3]);
-                pb.z = pack_bf16x2(s[u][8 * st + 4], s[u][8 * st + 5]);
-                pb.w = pack_bf16x2(s[u][8 * st + 6], s[u][8 * st + 7]);
+                const uint4 pb = acc_to_frag(s[u], st);
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct) {
                     const uint4 a = *reinterpret_cast<const uint4*>(v_lds + (32 * ct + col) * VP + (32 * u + 16 * st + 8 * half) * 2);
-                    o[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, pb),
-                                                                   o[ct], 0, 0, 0);
+                    o[ct] = mma_bf16(a, pb, o[ct]);
                 }
             }
         if (more) {

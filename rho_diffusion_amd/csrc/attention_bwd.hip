@@ -10,41 +10,14 @@
 // Two MFMA kernels instead of one with atomics (deterministic, no cross-workgroup traffic):
 //   k_attn_dq  : query-stationary (128 queries / workgroup), sweeps key tiles, accumulates dQ^T[c][q]
 //   k_attn_dkv : key-stationary   (128 keys / workgroup),    sweeps query tiles, accumulates dK^T, dV^T[c][key]
+//                (one body, attn_dkv_body, behind k_attn_dkv<.,.,dV | dK> and k_attn_dkv_fused, which does both in one sweep)
 // Both keep the "stationary" index on the lane, so softmax terms are lane-local, the score tile is
 // used directly as the next MFMA's B operand (accumulator-as-operand, rows permuted by pi), and every
 // operand that needs the contraction index contiguous is fetched from the row-major LDS tiles with the
-// transposing read ds_read_b64_tr_b16.
+// transposing read ds_read_b64_tr_b16.  The operand helpers, the LDS row tile (RowTile) and the stager of the key-stationary
+// kernels' query tiles (QdStage: Q + dO rows, -lse, -delta * scale) are in attention_tiles.h, shared with the forward kernel.
 #include "attention_plan.h"
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-
-__device__ __forceinline__ uint4 tr_frag2(const char* lds, int r0, int r1) {
-    const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(lds + r0));
-    const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(lds + r1));
-    uint4 f;
-    f.x = (uint32_t)(uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-    f.y = (uint32_t)(uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-    f.z = (uint32_t)(uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-    f.w = (uint32_t)(uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-    return f;
-}
-
-__device__ __forceinline__ f32x16_t mma_bf16(const uint4& a, const uint4& b, f32x16_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int pi_row(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
-
-// accumulator registers 8s..8s+7 -> bf16 B-operand fragment of k-step s
-__device__ __forceinline__ uint4 acc_to_frag(const f32x16_t& v, int st) {
-    uint4 f;
-    f.x = pack_bf16x2(v[8 * st + 0], v[8 * st + 1]);
-    f.y = pack_bf16x2(v[8 * st + 2], v[8 * st + 3]);
-    f.z = pack_bf16x2(v[8 * st + 4], v[8 * st + 5]);
-    f.w = pack_bf16x2(v[8 * st + 6], v[8 * st + 7]);
-    return f;
-}
+#include "attention_tiles.h"
 
 // ------------------------------------------------------------------------------------------------ delta
 // One 16-byte piece (8 bf16 / 4 f32 channels) of one (b, q) row per lane; the ch / PE lanes of a head are
@@ -85,23 +58,6 @@ __global__ __launch_bounds__(256) void k_attn_delta(const T* __restrict__ o, con
         delta[(b_ * heads + h) * T_ + q] = acc;
     }
 }
-
-// ------------------------------------------------------------------------------------------------ LDS tile layout
-// A [row][CH] bf16 tile is read two ways: whole 16-byte row pieces (ds_read_b128, 16 different rows per lane group)
-// and transposed 4-row x 64-byte windows (ds_read_b64_tr_b16, one half-wave = rows r..r+3 of one window).  A padded
-// pitch serves only one of them (odd 16-byte-slot pitch: b128 conflict-free, the 4 windows overlap 4-fold - PMC:
-// SQ_LDS_BANK_CONFLICT = 50 % of SQ_LDS_IDX_ACTIVE in these kernels).  For CH = 128 the rows are therefore unpadded
-// (256 B = all 64 banks) and the 16-byte slot is XORed with a bit-permutation of the row index: bits 0-1 of the row
-// pick the 64-byte window (4 consecutive rows -> 4 windows: tr reads conflict-free), bits 2-3 the slot inside it
-// (any 16 rows distinct mod 16 -> 16 distinct slots: b128 reads conflict-free).
-template <int CH>
-struct RowTile {
-    static constexpr bool SWZ = (CH == 128);
-    static constexpr int P = SWZ ? 256 : CH * 2 + 16;
-    static __device__ __forceinline__ int swz(int row) { return SWZ ? ((((row & 3) << 2) | ((row >> 2) & 3)) << 4) : 0; }
-    // byte offset of 16-byte-aligned `byte` (may carry an 8-byte sub-offset) in `row`
-    static __device__ __forceinline__ int at(int row, int byte) { return row * P + (byte ^ swz(row)); }
-};
 
 // ------------------------------------------------------------------------------------------------ dQ (bf16)
 template <int CH, int KT>
@@ -302,23 +258,34 @@ __global__ __launch_bounds__(256, CH <= 128 ? 2 : 1) void k_attn_dq(const bf16_r
 }
 
 // ------------------------------------------------------------------------------------------------ dK / dV (bf16)
-// Key-stationary (128 keys / workgroup, key on the lane), sweeping query tiles.  One kernel per gradient
-// (WHAT = 0: dV = P^T dO, WHAT = 1: dK = dS^T Q): together they hold two 64-register accumulators plus the K and V
-// operand fragments (another 64), which forces one wave per SIMD with every LDS / barrier wait exposed; apart they run
-// two workgroups per CU, for one extra recompute of S.
-template <int CH, int QT, int WHAT>
-__global__ __launch_bounds__(256, CH <= 128 ? 2 : 1) void k_attn_dkv(const bf16_raw* __restrict__ qk, const bf16_raw* __restrict__ vt,
-                                                  const bf16_raw* __restrict__ dout, const float* __restrict__ lse,
-                                                  const float* __restrict__ delta, bf16_raw* __restrict__ dst, int T, int C,
-                                                  float scale_log2e, float scale, int dst_rs, int dst_off) {
+// Key-stationary (128 keys / workgroup, key on the lane), sweeping query tiles: one body behind three kernels.
+//   MODE 0 / 1 (k_attn_dkv<.,.,WHAT>): one kernel per gradient (dV = P^T dO | dK = dS^T Q).  Both gradients with the K and V operand
+//     fragments in registers are two 64-register accumulators plus another 64, which forces one wave per SIMD with every LDS /
+//     barrier wait exposed; apart they run two workgroups per CU, for one extra recompute of S (5 contractions: S, P^T dO | S, dP,
+//     dS^T Q).
+//   MODE 2 (k_attn_dkv_fused): S is computed once (4 contractions, -20 % MFMAs of the pair).  The V fragments (lane = key, 8
+//     consecutive channels) stay in LDS - the workgroup's 128 V rows are staged once as [key][ch] (transposed out of the
+//     channel-major vt) and read per k-step - so a wave holds 128 (accumulators) + 32 (K fragments) + 32 (S, dP) + operands: two
+//     workgroups per CU as before.  Dispatched at CH = 64 only (attention_plan.h says why).
+// dk / dv point at channel 0 of head 0 of row 0 of the respective output; either may be null where MODE leaves it out.
+enum { ATTN_DV = 0, ATTN_DK = 1, ATTN_DKDV = 2 };
+
+template <int CH, int QT, int MODE>
+__device__ __forceinline__ void attn_dkv_body(const bf16_raw* __restrict__ qk, const bf16_raw* __restrict__ vt,
+                                              const bf16_raw* __restrict__ dout, const float* __restrict__ lse,
+                                              const float* __restrict__ delta, bf16_raw* __restrict__ dk, int dk_rs,
+                                              bf16_raw* __restrict__ dv, int dv_rs, int T, int C, float scale_log2e, float scale) {
     using QL = RowTile<CH>;
     constexpr int KP = QL::P;
+    constexpr int VBP = CH * 2 + 16;      // V rows [key][ch]: odd number of 16-byte slots, conflict-free ds_read_b128
     constexpr int NKK = CH / 16;
     constexpr int NCT = (CH + 31) / 32;
     constexpr int NU = QT / 32;
-    constexpr bool DK = (WHAT == 1);
+    constexpr bool DV = (MODE != ATTN_DK), DK = (MODE != ATTN_DV), BOTH = (MODE == ATTN_DKDV);
+    static_assert(!BOTH || CH % 32 == 0, "fused dK / dV: whole 32-channel tiles");
     __shared__ __attribute__((aligned(16))) char q_lds[QT * KP];                 // Q  [query][ch]
     __shared__ __attribute__((aligned(16))) char d_lds[QT * KP];                 // dO [query][ch]
+    __shared__ __attribute__((aligned(16))) char vb_lds[BOTH ? 128 * VBP : 16];  // V  [key][ch] of this workgroup's keys
     __shared__ __attribute__((aligned(16))) float nlse_s[QT];                    // -lse           (+inf rows: masked)
     __shared__ __attribute__((aligned(16))) float ndel_s[DK ? QT : 4];           // -delta * scale
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
@@ -330,224 +297,15 @@ __global__ __launch_bounds__(256, CH <= 128 ? 2 : 1) void k_attn_dkv(const bf16_
     const size_t row2c = (size_t)2 * C;
 
     // K fragments (B operand: lane = key, 8 consecutive channels)
-    uint4 kf[NKK], vf[DK ? NKK : 1];
+    uint4 kf[NKK], vf[(DK && !BOTH) ? NKK : 1];
     {
         const bf16_raw* kp = qk + ((size_t)b * T + kc) * row2c + C + (size_t)h * CH + 8 * half;
 #pragma unroll
         for (int kk = 0; kk < NKK; ++kk) kf[kk] = *reinterpret_cast<const uint4*>(kp + 16 * kk);
     }
-    // V fragments (B operand: lane = key, k = channel): V^T is channel-major, so each element is its own
-    // 2-byte load -- once per workgroup, outside the query sweep
-    if constexpr (DK) {
-        const bf16_raw* vp = vt + ((size_t)b * C + (size_t)h * CH + 8 * half) * T + kc;
-#pragma unroll
-        for (int kk = 0; kk < NKK; ++kk) {
-            uint32_t w[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t lo = vp[(size_t)(16 * kk + 2 * j) * T];
-                const uint32_t hi = vp[(size_t)(16 * kk + 2 * j + 1) * T];
-                w[j] = lo | (hi << 16);
-            }
-            vf[kk] = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-    }
-
-    f32x16_t acc[NCT];
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[ct][r] = 0.0f;
-    const int prow = pi_row(col);
-
-    constexpr int QPC = CH / 8;
-    constexpr int QIT = (QT * QPC + 255) / 256;
-    constexpr bool QEXACT = (QIT * 256 == QT * QPC);
-    const bf16_raw* const qbase = qk + (size_t)b * T * row2c + (size_t)h * CH;
-    const bf16_raw* const dbase = dout + (size_t)b * T * C + (size_t)h * CH;
-    const float* const lbase = lse + ((size_t)b * heads + h) * T;
-    const float* const ebase = delta + ((size_t)b * heads + h) * T;
-
-    // Q / dO tiles.  PRE (CH <= 64): issue-early / write-late (T14), tile t + 1 fetched under the MFMAs of tile t; CH = 128 has no
-    // registers for that (232 of 256) and loads between the barriers.  Whole tiles use a scalar tile origin + per-thread 32-bit
-    // offsets computed once instead of clamps, selects and 64-bit multiplies per tile.
-    constexpr bool PRE = (CH <= 64);
-    uint4 vq[QIT], vd[QIT];
-    float nl_r = 0.0f, nd_r = 0.0f;
-    unsigned qoff[QIT], doff[QIT], qlds[QIT];
-#pragma unroll
-    for (int i = 0; i < QIT; ++i) {
-        const int pc = tid + 256 * i, q = pc / QPC, piece = pc % QPC;
-        qoff[i] = (unsigned)(((size_t)q * row2c + piece * 8) * 2);
-        doff[i] = (unsigned)(((size_t)q * C + piece * 8) * 2);
-        qlds[i] = (unsigned)QL::at(q, piece * 16);
-    }
-    auto load_q = [&](int qt0) {
-        if (QEXACT && qt0 + QT <= T) {                       // (uniform)
-            const char* const qb = reinterpret_cast<const char*>(qbase) + (size_t)qt0 * row2c * 2;
-            const char* const db = reinterpret_cast<const char*>(dbase) + (size_t)qt0 * C * 2;
-#pragma unroll
-            for (int i = 0; i < QIT; ++i) {
-                vq[i] = *reinterpret_cast<const uint4*>(qb + qoff[i]);
-                vd[i] = *reinterpret_cast<const uint4*>(db + doff[i]);
-            }
-            if (tid < QT) {
-                nl_r = -lbase[qt0 + tid];
-                if constexpr (DK) nd_r = -ebase[qt0 + tid] * scale;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < QIT; ++i) {
-                const int pc = tid + 256 * i;
-                const int q = QEXACT ? pc / QPC : min(pc / QPC, QT - 1), piece = pc % QPC;
-                const size_t qr = (size_t)min(qt0 + q, T - 1);
-                vq[i] = *reinterpret_cast<const uint4*>(qbase + qr * row2c + piece * 8);
-                vd[i] = *reinterpret_cast<const uint4*>(dbase + qr * C + piece * 8);
-            }
-            if (tid < QT) {
-                const bool ok = qt0 + tid < T;
-                nl_r = ok ? -lbase[qt0 + tid] : -INFINITY;          // exp2(-inf) = 0 masks the row
-                if constexpr (DK) nd_r = ok ? -ebase[qt0 + tid] * scale : 0.0f;
-            }
-        }
-    };
-    auto store_q = [&](int qt0) {
-        if (tid < QT) {
-            nlse_s[tid] = nl_r;
-            if constexpr (DK) ndel_s[tid] = nd_r;
-        }
-        if (QEXACT && qt0 + QT <= T) {
-#pragma unroll
-            for (int i = 0; i < QIT; ++i) {
-                *reinterpret_cast<uint4*>(q_lds + qlds[i]) = vq[i];
-                *reinterpret_cast<uint4*>(d_lds + qlds[i]) = vd[i];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < QIT; ++i) {
-                const int pc = tid + 256 * i;
-                const int q = pc / QPC, piece = pc % QPC;
-                if (QEXACT || pc < QT * QPC) {
-                    const bool ok = qt0 + q < T;
-                    *reinterpret_cast<uint4*>(q_lds + QL::at(q, piece * 16)) = ok ? vq[i] : make_uint4(0u, 0u, 0u, 0u);
-                    *reinterpret_cast<uint4*>(d_lds + QL::at(q, piece * 16)) = ok ? vd[i] : make_uint4(0u, 0u, 0u, 0u);
-                }
-            }
-        }
-    };
-    if constexpr (PRE) load_q(0);
-    for (int qt0 = 0; qt0 < T; qt0 += QT) {
-        __syncthreads();
-        if constexpr (!PRE) load_q(qt0);
-        store_q(qt0);
-        __syncthreads();
-        if constexpr (PRE) {
-            if (qt0 + QT < T) load_q(qt0 + QT);             // in flight under this tile's MFMAs
-        }
-
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            f32x16_t s, dp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = 0.0f; dp[r] = 0.0f; }
-            const int qrow = 32 * u + prow;
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                const uint4 aq = *reinterpret_cast<const uint4*>(q_lds + QL::at(qrow, 16 * half + 32 * kk));
-                s = mma_bf16(aq, kf[kk], s);                 // S[q][key]
-                if constexpr (DK) {
-                    const uint4 ad = *reinterpret_cast<const uint4*>(d_lds + QL::at(qrow, 16 * half + 32 * kk));
-                    dp = mma_bf16(ad, vf[kk], dp);           // dP[q][key]
-                }
-            }
-            // accumulator registers 4g..4g+3 hold the 4 consecutive queries 32u + pi(8g + 4 half) + {0..3}
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int q4 = 32 * u + pi_row(8 * g + 4 * half);
-                const float4 nl = *reinterpret_cast<const float4*>(&nlse_s[q4]);
-                const float nlv[4] = {nl.x, nl.y, nl.z, nl.w};
-                if constexpr (DK) {
-                    const float4 nd = *reinterpret_cast<const float4*>(&ndel_s[q4]);
-                    const float ndv[4] = {nd.x, nd.y, nd.z, nd.w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float pv = __builtin_amdgcn_exp2f(fmaf(s[4 * g + j], scale_log2e, nlv[j]));
-                        s[4 * g + j] = pv * fmaf(dp[4 * g + j], scale, ndv[j]);     // dS
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) s[4 * g + j] = __builtin_amdgcn_exp2f(fmaf(s[4 * g + j], scale_log2e, nlv[j]));   // P
-                }
-            }
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                const uint4 bf = acc_to_frag(s, st);
-                const int rq = 32 * u + 16 * st + 8 * (grp >> 1) + qq;
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) {
-                    const int cb = (32 * ct + 16 * (grp & 1) + 4 * pp) * 2;
-                    // dV: dO^T[c][q] * P[q][key];  dK: Q^T[c][q] * dS[q][key]
-                    const uint4 a = tr_frag2(DK ? q_lds : d_lds, QL::at(rq, cb), QL::at(rq + 4, cb));
-                    acc[ct] = mma_bf16(a, bf, acc[ct]);
-                }
-            }
-        }
-    }
-    if (kj < T) {
-        bf16_raw* op = dst + ((size_t)b * T + kj) * dst_rs + dst_off + (size_t)h * CH;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int c = 32 * ct + 8 * rg + 4 * half;
-                if (c < CH)
-                    *reinterpret_cast<uint2*>(op + c) = make_uint2(pack_bf16x2(acc[ct][4 * rg + 0], acc[ct][4 * rg + 1]),
-                                                                   pack_bf16x2(acc[ct][4 * rg + 2], acc[ct][4 * rg + 3]));
-            }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ dK and dV in one kernel (bf16)
-// Round 3: the key-stationary pair above recomputes S once per gradient (5 contractions: S, P^T dO | S, dP, dS^T Q).  Fused, S is
-// computed once (4 contractions, -20 % MFMAs of the pair).  What kept r2 from fusing was registers: two 64-register accumulators
-// plus the K and V B-operand fragments (64) left one wave per SIMD.  Here the V fragments (lane = key, 8 consecutive channels) stay
-// in LDS - the workgroup's 128 V rows are staged once as [key][ch] (transposed out of the channel-major vt) and read per k-step -
-// so a wave holds 128 (accumulators) + 32 (K fragments) + 32 (S, dP) + operands: two workgroups per CU as before.
-template <int CH, int QT>
-__global__ __launch_bounds__(256, 2) void k_attn_dkv_fused(const bf16_raw* __restrict__ qk, const bf16_raw* __restrict__ vt,
-                                                           const bf16_raw* __restrict__ dout, const float* __restrict__ lse,
-                                                           const float* __restrict__ delta, bf16_raw* __restrict__ dqk,
-                                                           bf16_raw* __restrict__ dv, int T, int C, float scale_log2e, float scale,
-                                                           int dqk_rs, int dv_rs) {
-    using QL = RowTile<CH>;
-    constexpr int KP = QL::P;
-    constexpr int VBP = CH * 2 + 16;      // V rows [key][ch]: odd number of 16-byte slots, conflict-free ds_read_b128
-    constexpr int NKK = CH / 16;
-    constexpr int NCT = (CH + 31) / 32;
-    constexpr int NU = QT / 32;
-    static_assert(CH % 32 == 0, "fused dK / dV: whole 32-channel tiles");
-    __shared__ __attribute__((aligned(16))) char q_lds[QT * KP];                 // Q  [query][ch]
-    __shared__ __attribute__((aligned(16))) char d_lds[QT * KP];                 // dO [query][ch]
-    __shared__ __attribute__((aligned(16))) char vb_lds[128 * VBP];              // V  [key][ch] of this workgroup's keys
-    __shared__ __attribute__((aligned(16))) float nlse_s[QT];
-    __shared__ __attribute__((aligned(16))) float ndel_s[QT];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
-    const int grp = lane >> 4, li = lane & 15, qq = li >> 2, pp = li & 3;
-    const int b = blockIdx.z, h = blockIdx.y, heads = gridDim.y;
-    const int k0 = blockIdx.x * 128;
-    const int kj = k0 + wave * 32 + col;
-    const int kc = kj < T ? kj : T - 1;
-    const size_t row2c = (size_t)2 * C;
-
-    uint4 kf[NKK];
-    {
-        const bf16_raw* kp = qk + ((size_t)b * T + kc) * row2c + C + (size_t)h * CH + 8 * half;
-#pragma unroll
-        for (int kk = 0; kk < NKK; ++kk) kf[kk] = *reinterpret_cast<const uint4*>(kp + 16 * kk);
-    }
-    // V rows of the workgroup's 128 keys: vt is channel-major [ch][T] - a thread reads 8 consecutive keys of one channel (16 bytes)
-    // and scatters them into 8 rows; once per workgroup, outside the query sweep
-    {
+    if constexpr (BOTH) {
+        // V rows of the workgroup's 128 keys: vt is channel-major [ch][T] - a thread reads 8 consecutive keys of one channel (16 bytes)
+        // and scatters them into 8 rows; once per workgroup, outside the query sweep
         const bf16_raw* vbase = vt + ((size_t)b * C + (size_t)h * CH) * T;
         const bool vec = ((T & 7) == 0);
         for (int pc = tid; pc < CH * 16; pc += 256) {
@@ -563,96 +321,50 @@ __global__ __launch_bounds__(256, 2) void k_attn_dkv_fused(const bf16_raw* __res
 #pragma unroll
             for (int j = 0; j < 8; ++j) *reinterpret_cast<bf16_raw*>(vb_lds + (piece * 8 + j) * VBP + c * 2) = e[j];
         }
+    } else if constexpr (DK) {
+        // V fragments (B operand: lane = key, k = channel): V^T is channel-major, so each element is its own
+        // 2-byte load -- once per workgroup, outside the query sweep
+        const bf16_raw* vp = vt + ((size_t)b * C + (size_t)h * CH + 8 * half) * T + kc;
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) {
+            uint32_t w[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t lo = vp[(size_t)(16 * kk + 2 * j) * T];
+                const uint32_t hi = vp[(size_t)(16 * kk + 2 * j + 1) * T];
+                w[j] = lo | (hi << 16);
+            }
+            vf[kk] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
     }
-    const char* const vrow = vb_lds + (wave * 32 + col) * VBP + 16 * half;
+    const char* const vrow = vb_lds + (wave * 32 + col) * VBP + 16 * half;     // BOTH: this lane's V row
 
-    f32x16_t adv[NCT], adk[NCT];
+    f32x16_t adv[DV ? NCT : 1], adk[DK ? NCT : 1];
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { adv[ct][r] = 0.0f; adk[ct][r] = 0.0f; }
+        for (int r = 0; r < 16; ++r) {
+            if constexpr (DV) adv[ct][r] = 0.0f;
+            if constexpr (DK) adk[ct][r] = 0.0f;
+        }
     const int prow = pi_row(col);
 
-    constexpr int QPC = CH / 8;
-    constexpr int QIT = (QT * QPC + 255) / 256;
-    constexpr bool QEXACT = (QIT * 256 == QT * QPC);
-    const bf16_raw* const qbase = qk + (size_t)b * T * row2c + (size_t)h * CH;
-    const bf16_raw* const dbase = dout + (size_t)b * T * C + (size_t)h * CH;
-    const float* const lbase = lse + ((size_t)b * heads + h) * T;
-    const float* const ebase = delta + ((size_t)b * heads + h) * T;
-
-    // Q / dO tiles: issue-early / write-late as in the forward kernel (cdna_hip_programming.md T14) - tile t + 1 is fetched into
-    // registers under the MFMAs of tile t and written to LDS between the two barriers; whole tiles (all but a ragged last one) use a
-    // scalar tile origin + per-thread 32-bit offsets computed once instead of clamps, selects and 64-bit multiplies per tile.
-    uint4 vq[QIT], vd[QIT];
-    float nl_r = 0.0f, nd_r = 0.0f;
-    unsigned qoff[QIT], doff[QIT], qlds[QIT];
-#pragma unroll
-    for (int i = 0; i < QIT; ++i) {
-        const int pc = tid + 256 * i, q = pc / QPC, piece = pc % QPC;
-        qoff[i] = (unsigned)(((size_t)q * row2c + piece * 8) * 2);
-        doff[i] = (unsigned)(((size_t)q * C + piece * 8) * 2);
-        qlds[i] = (unsigned)QL::at(q, piece * 16);
-    }
-    auto load_q = [&](int qt0) {
-        if (QEXACT && qt0 + QT <= T) {                       // (uniform)
-            const char* const qb = reinterpret_cast<const char*>(qbase) + (size_t)qt0 * row2c * 2;
-            const char* const db = reinterpret_cast<const char*>(dbase) + (size_t)qt0 * C * 2;
-#pragma unroll
-            for (int i = 0; i < QIT; ++i) {
-                vq[i] = *reinterpret_cast<const uint4*>(qb + qoff[i]);
-                vd[i] = *reinterpret_cast<const uint4*>(db + doff[i]);
-            }
-            if (tid < QT) {
-                nl_r = -lbase[qt0 + tid];
-                nd_r = -ebase[qt0 + tid] * scale;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < QIT; ++i) {
-                const int pc = tid + 256 * i;
-                const int q = QEXACT ? pc / QPC : min(pc / QPC, QT - 1), piece = pc % QPC;
-                const size_t qr = (size_t)min(qt0 + q, T - 1);
-                vq[i] = *reinterpret_cast<const uint4*>(qbase + qr * row2c + piece * 8);
-                vd[i] = *reinterpret_cast<const uint4*>(dbase + qr * C + piece * 8);
-            }
-            if (tid < QT) {
-                const bool ok = qt0 + tid < T;
-                nl_r = ok ? -lbase[qt0 + tid] : -INFINITY;
-                nd_r = ok ? -ebase[qt0 + tid] * scale : 0.0f;
-            }
-        }
-    };
-    auto store_q = [&](int qt0) {
-        if (tid < QT) {
-            nlse_s[tid] = nl_r;
-            ndel_s[tid] = nd_r;
-        }
-        if (QEXACT && qt0 + QT <= T) {
-#pragma unroll
-            for (int i = 0; i < QIT; ++i) {
-                *reinterpret_cast<uint4*>(q_lds + qlds[i]) = vq[i];
-                *reinterpret_cast<uint4*>(d_lds + qlds[i]) = vd[i];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < QIT; ++i) {
-                const int pc = tid + 256 * i;
-                const int q = pc / QPC, piece = pc % QPC;
-                if (QEXACT || pc < QT * QPC) {
-                    const bool ok = qt0 + q < T;
-                    *reinterpret_cast<uint4*>(q_lds + QL::at(q, piece * 16)) = ok ? vq[i] : make_uint4(0u, 0u, 0u, 0u);
-                    *reinterpret_cast<uint4*>(d_lds + QL::at(q, piece * 16)) = ok ? vd[i] : make_uint4(0u, 0u, 0u, 0u);
-                }
-            }
-        }
-    };
-    load_q(0);
+    // Q / dO tiles.  PRE (CH <= 64): issue-early / write-late as in the forward kernel (cdna_hip_programming.md T14), tile t + 1 is
+    // fetched into registers under the MFMAs of tile t and written to LDS between the two barriers; CH = 128 has no registers for
+    // that (232 of 256) and loads between the barriers.
+    constexpr bool PRE = (CH <= 64);
+    QdStage<CH, QT, DK> qds;
+    qds.init(qk + (size_t)b * T * row2c + (size_t)h * CH, row2c, dout + (size_t)b * T * C + (size_t)h * CH, C,
+             lse + ((size_t)b * heads + h) * T, delta + ((size_t)b * heads + h) * T, scale, T, q_lds, d_lds, nlse_s, ndel_s);
+    if constexpr (PRE) qds.load(0);
     for (int qt0 = 0; qt0 < T; qt0 += QT) {
         __syncthreads();                  // the previous tile is consumed (first pass: also publishes vb_lds)
-        store_q(qt0);
+        if constexpr (!PRE) qds.load(qt0);
+        qds.store(qt0);
         __syncthreads();
-        if (qt0 + QT < T) load_q(qt0 + QT);      // in flight under this tile's MFMAs
+        if constexpr (PRE) {
+            if (qt0 + QT < T) qds.load(qt0 + QT);           // in flight under this tile's MFMAs
+        }
 
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
@@ -663,53 +375,89 @@ __global__ __launch_bounds__(256, 2) void k_attn_dkv_fused(const bf16_raw* __res
 #pragma unroll
             for (int kk = 0; kk < NKK; ++kk) {
                 const uint4 aq = *reinterpret_cast<const uint4*>(q_lds + QL::at(qrow, 16 * half + 32 * kk));
-                const uint4 ad = *reinterpret_cast<const uint4*>(d_lds + QL::at(qrow, 16 * half + 32 * kk));
-                const uint4 vf = *reinterpret_cast<const uint4*>(vrow + 32 * kk);
                 s = mma_bf16(aq, kf[kk], s);                 // S[q][key]
-                dp = mma_bf16(ad, vf, dp);                   // dP[q][key]
+                if constexpr (DK) {
+                    const uint4 ad = *reinterpret_cast<const uint4*>(d_lds + QL::at(qrow, 16 * half + 32 * kk));
+                    if constexpr (BOTH) dp = mma_bf16(ad, *reinterpret_cast<const uint4*>(vrow + 32 * kk), dp);
+                    else dp = mma_bf16(ad, vf[kk], dp);      // dP[q][key]
+                }
             }
+            // accumulator registers 4g..4g+3 hold the 4 consecutive queries 32u + pi(8g + 4 half) + {0..3}
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int q4 = 32 * u + pi_row(8 * g + 4 * half);
                 const float4 nl = *reinterpret_cast<const float4*>(&nlse_s[q4]);
-                const float4 nd = *reinterpret_cast<const float4*>(&ndel_s[q4]);
-                const float nlv[4] = {nl.x, nl.y, nl.z, nl.w}, ndv[4] = {nd.x, nd.y, nd.z, nd.w};
+                const float nlv[4] = {nl.x, nl.y, nl.z, nl.w};
+                float ndv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if constexpr (DK) {
+                    const float4 nd = *reinterpret_cast<const float4*>(&ndel_s[q4]);
+                    ndv[0] = nd.x, ndv[1] = nd.y, ndv[2] = nd.z, ndv[3] = nd.w;
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float pv = __builtin_amdgcn_exp2f(fmaf(s[4 * g + j], scale_log2e, nlv[j]));
-                    s[4 * g + j] = pv;                                             // P
-                    dp[4 * g + j] = pv * fmaf(dp[4 * g + j], scale, ndv[j]);       // dS
+                    s[4 * g + j] = pv;                                                            // P
+                    if constexpr (DK) dp[4 * g + j] = pv * fmaf(dp[4 * g + j], scale, ndv[j]);    // dS
                 }
             }
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                const uint4 bp = acc_to_frag(s, st), bs = acc_to_frag(dp, st);
+                uint4 bp, bs;
+                if constexpr (DV) bp = acc_to_frag(s, st);
+                if constexpr (DK) bs = acc_to_frag(dp, st);
                 const int rq = 32 * u + 16 * st + 8 * (grp >> 1) + qq;
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct) {
                     const int cb = (32 * ct + 16 * (grp & 1) + 4 * pp) * 2;
-                    const uint4 aD = tr_frag2(d_lds, QL::at(rq, cb), QL::at(rq + 4, cb));
-                    adv[ct] = mma_bf16(aD, bp, adv[ct]);     // dV^T[c][key] += dO^T[c][q] P[q][key]
-                    const uint4 aQ = tr_frag2(q_lds, QL::at(rq, cb), QL::at(rq + 4, cb));
-                    adk[ct] = mma_bf16(aQ, bs, adk[ct]);     // dK^T[c][key] += Q^T[c][q] dS[q][key]
+                    if constexpr (DV) {                      // dV^T[c][key] += dO^T[c][q] P[q][key]
+                        const uint4 aD = tr_frag2(d_lds, QL::at(rq, cb), QL::at(rq + 4, cb));
+                        adv[ct] = mma_bf16(aD, bp, adv[ct]);
+                    }
+                    if constexpr (DK) {                      // dK^T[c][key] += Q^T[c][q] dS[q][key]
+                        const uint4 aQ = tr_frag2(q_lds, QL::at(rq, cb), QL::at(rq + 4, cb));
+                        adk[ct] = mma_bf16(aQ, bs, adk[ct]);
+                    }
                 }
             }
         }
     }
     if (kj < T) {
-        bf16_raw* okp = dqk + ((size_t)b * T + kj) * dqk_rs + C + (size_t)h * CH;
-        bf16_raw* ovp = dv + ((size_t)b * T + kj) * dv_rs + (size_t)h * CH;
+        bf16_raw* okp = DK ? dk + ((size_t)b * T + kj) * dk_rs + (size_t)h * CH : nullptr;
+        bf16_raw* ovp = DV ? dv + ((size_t)b * T + kj) * dv_rs + (size_t)h * CH : nullptr;
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) {
                 const int c = 32 * ct + 8 * rg + 4 * half;
-                *reinterpret_cast<uint2*>(okp + c) = make_uint2(pack_bf16x2(adk[ct][4 * rg + 0], adk[ct][4 * rg + 1]),
-                                                                pack_bf16x2(adk[ct][4 * rg + 2], adk[ct][4 * rg + 3]));
-                *reinterpret_cast<uint2*>(ovp + c) = make_uint2(pack_bf16x2(adv[ct][4 * rg + 0], adv[ct][4 * rg + 1]),
-                                                                pack_bf16x2(adv[ct][4 * rg + 2], adv[ct][4 * rg + 3]));
+                if (CH % 32 == 0 || c < CH) {
+                    if constexpr (DK)
+                        *reinterpret_cast<uint2*>(okp + c) = make_uint2(pack_bf16x2(adk[ct][4 * rg + 0], adk[ct][4 * rg + 1]),
+                                                                        pack_bf16x2(adk[ct][4 * rg + 2], adk[ct][4 * rg + 3]));
+                    if constexpr (DV)
+                        *reinterpret_cast<uint2*>(ovp + c) = make_uint2(pack_bf16x2(adv[ct][4 * rg + 0], adv[ct][4 * rg + 1]),
+                                                                        pack_bf16x2(adv[ct][4 * rg + 2], adv[ct][4 * rg + 3]));
+                }
             }
     }
+}
+
+// WHAT = 0: dV into dst, WHAT = 1: dK into dst (dst_off = the channel offset of K in a dqk row)
+template <int CH, int QT, int WHAT>
+__global__ __launch_bounds__(256, CH <= 128 ? 2 : 1) void k_attn_dkv(const bf16_raw* __restrict__ qk, const bf16_raw* __restrict__ vt,
+                                                  const bf16_raw* __restrict__ dout, const float* __restrict__ lse,
+                                                  const float* __restrict__ delta, bf16_raw* __restrict__ dst, int T, int C,
+                                                  float scale_log2e, float scale, int dst_rs, int dst_off) {
+    if constexpr (WHAT == 1) attn_dkv_body<CH, QT, ATTN_DK>(qk, vt, dout, lse, delta, dst + dst_off, dst_rs, nullptr, 0, T, C, scale_log2e, scale);
+    else attn_dkv_body<CH, QT, ATTN_DV>(qk, vt, dout, lse, delta, nullptr, 0, dst + dst_off, dst_rs, T, C, scale_log2e, scale);
+}
+
+template <int CH, int QT>
+__global__ __launch_bounds__(256, 2) void k_attn_dkv_fused(const bf16_raw* __restrict__ qk, const bf16_raw* __restrict__ vt,
+                                                           const bf16_raw* __restrict__ dout, const float* __restrict__ lse,
+                                                           const float* __restrict__ delta, bf16_raw* __restrict__ dqk,
+                                                           bf16_raw* __restrict__ dv, int T, int C, float scale_log2e, float scale,
+                                                           int dqk_rs, int dv_rs) {
+    attn_dkv_body<CH, QT, ATTN_DKDV>(qk, vt, dout, lse, delta, dqk + C, dqk_rs, dv, dv_rs, T, C, scale_log2e, scale);
 }
 
 // ------------------------------------------------------------------------------------------------ exact-f32 (VALU) variants
