@@ -8,7 +8,11 @@ out on purpose: the fixed kernel reads the model_var row where the learned one c
 same values, so the strided and the plain entry points agree bit for bit too.
 
 Shapes: (3, 1, 7, 79) is 553 elements per sample, three workgroups of 256 with a ragged tail; (2, 1, 5) is one partial workgroup.
-t = [0, 7, 19] (the first B of them): t == 0 masks the noise and selects the decoder NLL, 19 is the last row of the table."""
+t = [0, 7, 19] (the first B of them): t == 0 masks the noise and selects the decoder NLL, 19 is the last row of the table.
+
+Left to other files: the values themselves at the sizes where the grids loop again, with ``grad``, other strides, offset bases, err_flag
+and the refusals of the step kernels are in test_gpu_gaussian_step_edges.py (restatement and bounds: gd_step_ref.py, checked on the
+CPU by test_gd_step_ref_host.py); the loss side in test_gpu_gaussian_loss_bounds.py (gd_loss_ref.py)."""
 import functools
 
 import numpy as np

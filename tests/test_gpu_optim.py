@@ -30,6 +30,7 @@ from torch import nn
 
 from helpers import UNET_CASES, det_normal, det_state_dict, det_uniform, golden_template, load_golden, rel_l2
 from gpu_util import DEV, Guarded, check_bound, same_bits
+from running_error import B, _r, add, div, maxf, mul, neg, sqrt, sub          # noqa: F401  (the analysis of the docstring below)
 from test_gpu_streaming_edges import SMALL, U, WRAP4, _data, _shift_sets
 
 pytestmark = pytest.mark.gpu
@@ -166,55 +167,11 @@ class KernelRun:
 
 
 # ----------------------------------------------------------------------------- running error analysis (module docstring)
-class B:
-    """value and a bound on |float32 result - value|, float64 tensors"""
-
-    def __init__(self, v, e=None):
-        self.v = torch.as_tensor(v, dtype=torch.float64)
-        self.e = torch.zeros_like(self.v) if e is None else torch.as_tensor(e, dtype=torch.float64)
-
-
-def _r(v, e):
-    return B(v, e + U * (v.abs() + e))               # one rounding of a result that is itself within e of v
-
-
 def cast(x, kernel_x=None):
     """A double the launcher casts to float32.  ``kernel_x``: the launcher's double where it is known to differ from the reference's
     ``x`` (NAdam's factors once mu_product has been through a float64 state_dict)."""
     kx = x if kernel_x is None else kernel_x
     return B(torch.tensor(float(x), dtype=torch.float64), torch.tensor(abs(float(kx) - float(x)) + U * abs(float(kx)), dtype=torch.float64))
-
-
-def add(a, b):
-    return _r(a.v + b.v, a.e + b.e)
-
-
-def sub(a, b):
-    return _r(a.v - b.v, a.e + b.e)
-
-
-def mul(a, b):
-    return _r(a.v * b.v, a.v.abs() * b.e + b.v.abs() * a.e + a.e * b.e)
-
-
-def div(a, b):
-    assert bool((b.v.abs() > b.e).all())
-    q = a.v / b.v
-    return _r(q, (a.e + q.abs() * b.e) / (b.v.abs() - b.e))
-
-
-def sqrt(a):
-    assert bool((a.v >= 0).all())
-    v = a.v.sqrt()
-    return _r(v, v - (a.v - a.e).clamp_min(0.0).sqrt())
-
-
-def maxf(a, b):
-    return B(torch.maximum(a.v, b.v), torch.maximum(a.e, b.e))
-
-
-def neg(a):
-    return B(-a.v, a.e)
 
 
 def lerp(s, g, w):                                   # s + w * (g - s)
