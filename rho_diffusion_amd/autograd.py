@@ -21,12 +21,13 @@ class UNetFunction(torch.autograd.Function):
         ctx.engine = engine
         ctx.hooks = hooks
         out = engine.forward(x, timesteps, y, train=True)
+        ctx.generation = engine._train_generation      # this forward's number: backward refuses to run for an older one
         return out.clone()
 
     @staticmethod
     def backward(ctx, dout):
         cb = ctx.hooks.on_ready if ctx.hooks is not None else None
-        ctx.engine.backward(dout.contiguous().float(), on_ready=cb)
+        ctx.engine.backward(dout.contiguous().float(), on_ready=cb, generation=ctx.generation)
         return None, None, None, None, None, None
 
 

@@ -89,6 +89,10 @@ class ExponentialMovingAverage(nn.Module):
         base = self._flat.data_ptr()
         for off, src, k in self._runs:
             hip.check(L.rho_ema_update(base + 4 * off, src, k, omf, stream), "rho_ema_update")
+        # the shadow parameters changed in place through the arena: bump their version counters (no kernel) so dependants
+        # (the shadow engine's prepared conv weights) refresh, as HipAdamW.step does for the live ones
+        for _, sh in self._pairs:
+            torch.autograd.graph.increment_version(sh)
         live = dict(self.model.named_buffers())
         for name, buf in self.ema_model.named_buffers():
             buf.copy_(live[name])

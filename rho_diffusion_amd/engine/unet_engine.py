@@ -77,6 +77,7 @@ class UNetEngine:
         self._prep_sig = None
         self._prep_eager: List[_ConvW] = []
         self._last_train_plan: Optional["_Plan"] = None
+        self._train_generation = 0      # counts forward(train=True) calls: a backward names the forward it belongs to (backward())
         self._cond_keep: Optional[Tensor] = None      # label-dropout mask for the next training forward (set_cond_keep)
         with torch.inference_mode(False):
             self._collect()
@@ -162,7 +163,13 @@ class UNetEngine:
 
     def refresh_weights(self, force: bool = False) -> None:
         """Re-run the weight preparation kernels if any parameter changed (optimizer step, load_state_dict);
-        drop the plans if parameter storage moved (e.g. re-homed into an optimizer arena)."""
+        drop the plans if parameter storage moved (e.g. re-homed into an optimizer arena).
+
+        A change is seen through the parameters' version counters: every in-place torch op bumps them (``p.copy_`` under
+        ``no_grad``, the stock optimizers, ``load_state_dict``), and the library's own raw-pointer writers bump them by hand
+        (``HipAdamW.step``, ``ExponentialMovingAverage.update``).  A write through ``p.data`` - or any other raw-pointer write -
+        bypasses the counter: after one, call ``refresh_weights(force=True)``, or the convolutions keep the layouts prepared from
+        the old values."""
         sig = self._pointer_signature()
         if self._ptr_sig is not None and sig != self._ptr_sig:
             self._plans.clear()
@@ -274,6 +281,7 @@ class UNetEngine:
         keep = None
         if train:
             self._last_train_plan = plan
+            self._train_generation += 1
             keep, self._cond_keep = self._cond_keep, None
         return plan.run(x, timesteps, y, t_scalar_dev, keep)
 
@@ -329,13 +337,25 @@ class UNetEngine:
         self._plans = {k: v for k, v in self._plans.items() if train_only and not k[2]}
         self._last_train_plan = None
 
-    def backward(self, dpred: Tensor, on_ready: Optional[Callable[[List[nn.Parameter]], None]] = None) -> None:
+    def backward(self, dpred: Tensor, on_ready: Optional[Callable[[List[nn.Parameter]], None]] = None,
+                 generation: Optional[int] = None) -> None:
         """Backward of the most recent ``forward(train=True)``: accumulates into ``p.grad`` of every
         parameter (allocated as zeros if missing).  ``on_ready(params)`` is called as groups of
-        parameter gradients become final (used to overlap the data-parallel all-reduce)."""
+        parameter gradients become final (used to overlap the data-parallel all-reduce).
+
+        ``generation``: the value of ``_train_generation`` right after the forward this backward belongs to (UNetFunction
+        remembers it).  The engine keeps the activations of ONE training forward - a plan's buffers are overwritten by the next
+        forward of that shape, and another shape selects another plan - so a backward of an older forward cannot be computed
+        and raises instead of returning the gradients of the wrong forward."""
         plan = self._last_train_plan
         if plan is None:
             raise hip.RhoHipError("backward() without a preceding forward(train=True)")
+        if generation is not None and generation != self._train_generation:
+            raise hip.RhoHipError(
+                f"backward() of training forward #{generation}, but the most recent forward(train=True) of this engine is "
+                f"#{self._train_generation}: the engine keeps the activations of the most recent training forward only - "
+                "run each forward's backward before the next training forward (one forward over the concatenated batch, or "
+                "forward / backward per micro-batch with gradient accumulation)")
         with torch.no_grad():
             plan.run_backward(dpred, on_ready)
 
