@@ -75,20 +75,44 @@ def _c32(v: int) -> int:
 
 
 def _grad_of(p: nn.Parameter) -> torch.Tensor:
-    """``p.grad`` as it is NOW (HipAdamW re-homes it into its arena after the first step): resolved at launch time."""
+    """``p.grad`` as it is NOW (HipAdamW re-homes it into its arena after the first step): resolved at launch time.  Only for a
+    parameter that requires grad: a frozen one keeps ``.grad`` None (``_wants`` / ``_grad_or_scratch``)."""
+    assert p.requires_grad
     if p.grad is None:
         p.grad = torch.zeros_like(p)
     return p.grad
 
 
+def _wants(p: Optional[nn.Parameter]) -> bool:
+    return p is not None and p.requires_grad
+
+
+def _grad_or_scratch(p: nn.Parameter) -> torch.Tensor:
+    """Target of a kernel that writes this parameter's gradient next to other results (LayerNorm's dgamma / dbeta): ``p.grad``, or
+    for a frozen parameter a scratch tensor that is dropped."""
+    return _grad_of(p) if p.requires_grad else torch.zeros_like(p)
+
+
 class _Gemm:
     """The GEMM forms of one parameter viewed as W [P, Q]: y = x W^T (an nn.Linear / kernel = stride convolution) or, ``transposed``,
-    y = x W (a ConvTranspose with kernel = stride).  Prepared layouts are cached until the parameter's version counter moves."""
+    y = x W (a ConvTranspose with kernel = stride).  Prepared layouts are cached until the parameter's storage or version counter
+    moves.  The parameters are looked up on their module at every use, never held: ``load_state_dict(..., assign=True)`` and
+    ``module.weight = nn.Parameter(...)`` put ANOTHER object there, and a held one would go on serving the old weights and
+    collecting the gradients."""
 
-    def __init__(self, weight: nn.Parameter, P: int, Q: int, bias: Optional[nn.Parameter] = None, transposed: bool = False):
-        self.weight, self.bias, self.P, self.Q, self.transposed = weight, bias, int(P), int(Q), transposed
+    def __init__(self, owner: nn.Module, wname: str, P: int, Q: int, bname: Optional[str] = None, transposed: bool = False):
+        self._owner, self._wname, self._bname = owner, wname, bname
+        self.P, self.Q, self.transposed = int(P), int(Q), transposed
         self._key = None
         self._zero = {}
+
+    @property
+    def weight(self) -> nn.Parameter:
+        return getattr(self._owner, self._wname)
+
+    @property
+    def bias(self) -> Optional[nn.Parameter]:
+        return getattr(self._owner, self._bname) if self._bname is not None else None
 
     def _w2d(self) -> torch.Tensor:
         return self.weight.detach().view(self.P, self.Q)
@@ -136,30 +160,37 @@ class _Gemm:
         return y
 
     def wgrad(self, x, dy) -> None:
-        """Accumulates the weight (and bias) gradient of y = fwd(x) into ``p.grad``."""
+        """Accumulates the weight (and bias) gradient of y = fwd(x) into ``p.grad``; nothing is launched for frozen parameters."""
         from .. import hip
         from ..engine import ops
+        want_b = self.bias is not None and not self.transposed and self.bias.requires_grad
+        if not (self.weight.requires_grad or want_b):
+            return
         a, b = (dy, x) if self.transposed else (x, dy)                       # dw[P, Q] = sum_pos b[pos, P] a[pos, Q]
         P32, Q32 = _c32(self.P), _c32(self.Q)
         wA = self.prepared(x.dtype)[1 if self.transposed else 0]
         desc = ops.make_conv_desc(a, None, wA, self.zero_bias(P32, x.device), kernel=(1, 1, 1), cout=P32, split=P32, y=b, y2=None)
         dw = torch.zeros(1, P32, Q32, dtype=torch.float32, device=x.device)
-        want_b = self.bias is not None and not self.transposed
         db = torch.zeros(P32, dtype=torch.float32, device=x.device) if want_b else None
         ops.conv_wgrad(desc, b, dw, db)
-        g = _grad_of(self.weight)
-        hip.check(hip.lib().rho_wgrad_finalize(hip.ptr(dw), hip.ptr(g), self.P, self.Q, 1, P32, Q32, None, 1, hip.stream()),
-                  "rho_wgrad_finalize")
+        if self.weight.requires_grad:
+            g = _grad_of(self.weight)
+            hip.check(hip.lib().rho_wgrad_finalize(hip.ptr(dw), hip.ptr(g), self.P, self.Q, 1, P32, Q32, None, 1, hip.stream()),
+                      "rho_wgrad_finalize")
         if want_b:
             gb = _grad_of(self.bias)
             hip.check(hip.lib().rho_add_inplace(hip.ptr(gb), hip.ptr(db), hip.RHO_F32, self.P, hip.stream()), "rho_add_inplace")
 
 
 def _small_linear_bwd(dz, x, lin: nn.Linear) -> None:
-    """Parameter gradients of z = lin(x) for the [B, E] / [N, E] sized host-side pieces, accumulated into ``p.grad``."""
+    """Parameter gradients of z = lin(x) for the [B, E] / [N, E] sized host-side pieces, accumulated into ``p.grad`` (a frozen
+    parameter gets none; with both frozen nothing is launched)."""
     from ..engine import ops
-    w = lin.weight.detach()
-    ops.linear_bwd(dz, x, w, _grad_of(lin.weight), _grad_of(lin.bias) if lin.bias is not None else None, None, acc_params=True)
+    dw = _grad_of(lin.weight) if lin.weight.requires_grad else None
+    db = _grad_of(lin.bias) if _wants(lin.bias) else None
+    if dw is None and db is None:
+        return
+    ops.linear_bwd(dz, x, lin.weight.detach(), dw, db, None, acc_params=True)
 
 
 class PatchEmbedding(nn.Module):
@@ -175,7 +206,7 @@ class PatchEmbedding(nn.Module):
         self._conv_type = registry.get("nn", f"Conv{data_dims}d")
         self.conv_shaper = self._conv_type(num_channels, embedding_dim, kernel_size=patch_size, stride=patch_size)
         self.stored_shape = None
-        self._gemm = _Gemm(self.conv_shaper.weight, embedding_dim, num_channels * patch_size ** data_dims, self.conv_shaper.bias)
+        self._gemm = _Gemm(self.conv_shaper, "weight", embedding_dim, num_channels * patch_size ** data_dims, "bias")
 
     def tokens(self, data: torch.Tensor, dt) -> torch.Tensor:
         """float32 [B, C, *spatial] -> embedded tokens, channels-last [B, 1, 1, N, E] in ``dt`` (+ the patch operand for the backward)."""
@@ -223,10 +254,10 @@ class AttentionBlock(nn.Module):
         self.time_transform = nn.Sequential(SinusoidalPositionEmbedding(time_dim), nn.Linear(time_dim, embed_dim, bias=False),
                                             _act_module(activation))
         at = self.attention_layer
-        self._qkv = _Gemm(at.in_proj_weight, 3 * embed_dim, embed_dim, at.in_proj_bias)
-        self._proj = _Gemm(at.out_proj.weight, embed_dim, embed_dim, at.out_proj.bias)
-        self._lin1 = _Gemm(self.linear_block[0].weight, hidden_dim, embed_dim, self.linear_block[0].bias)
-        self._lin2 = _Gemm(self.linear_block[3].weight, embed_dim, hidden_dim, self.linear_block[3].bias)
+        self._qkv = _Gemm(at, "in_proj_weight", 3 * embed_dim, embed_dim, "in_proj_bias")
+        self._proj = _Gemm(at.out_proj, "weight", embed_dim, embed_dim, "bias")
+        self._lin1 = _Gemm(self.linear_block[0], "weight", hidden_dim, embed_dim, "bias")
+        self._lin2 = _Gemm(self.linear_block[3], "weight", embed_dim, hidden_dim, "bias")
 
     def _check_dropout(self):
         if self.training and self.dropout > 0:
@@ -268,8 +299,8 @@ class AttentionBlock(nn.Module):
         self._lin1.wgrad(s["n2"], dz1)
         dn2 = self._lin1.dgrad(dz1)
         n2 = self.norm_2
-        ops.layernorm_bwd(dn2, s["ar"], s["st2"], n2.weight.detach(), _grad_of(n2.weight), _grad_of(n2.bias), dx=dout, acc_dx=True,
-                          acc_params=True)
+        ops.layernorm_bwd(dn2, s["ar"], s["st2"], n2.weight.detach(), _grad_or_scratch(n2.weight), _grad_or_scratch(n2.bias), dx=dout,
+                          acc_dx=True, acc_params=True)
         dar = dout                                                                                        # d attn_residual
         # ar = n1 + out_proj(attention(qkv(n1)))
         self._proj.wgrad(s["ao"], dar)
@@ -280,10 +311,11 @@ class AttentionBlock(nn.Module):
         dn1 = self._qkv.dgrad(dqkv5, res=dar)
         # n1 = norm_1(x + t_embed): x reaches the output through the norm only (vit.py:178-184)
         n1 = self.norm_1
-        dx, dtemb = ops.layernorm_bwd(dn1, s["x"], s["st1"], n1.weight.detach(), _grad_of(n1.weight), _grad_of(n1.bias), add=s["temb"],
-                                      acc_params=True)
-        dtz = ops.bias_act_bwd(s["tz"], dtemb, act)
-        _small_linear_bwd(dtz, s["pe"], self.time_transform[1])
+        dx, dtemb = ops.layernorm_bwd(dn1, s["x"], s["st1"], n1.weight.detach(), _grad_or_scratch(n1.weight), _grad_or_scratch(n1.bias),
+                                      add=s["temb"], acc_params=True)
+        if self.time_transform[1].weight.requires_grad:
+            dtz = ops.bias_act_bwd(s["tz"], dtemb, act)
+            _small_linear_bwd(dtz, s["pe"], self.time_transform[1])
         return dx
 
     def forward(self, data: torch.Tensor, t: torch.Tensor) -> dict:
@@ -354,8 +386,8 @@ class VisionTransformer(nn.Module):
             raise ValueError(f"compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
         self.compute_dtype = _DTYPES.get(compute_dtype, compute_dtype)
         self.num_channels, self.embedding_dim, self.hidden_dim = num_channels, embedding_dim, hidden_dim
-        self._oproj = _Gemm(self.output_projection.weight, hidden_dim, embedding_dim)
-        self._oconv = _Gemm(self.output_conv.weight, hidden_dim, num_channels * patch_size ** data_dims, transposed=True)
+        self._oproj = _Gemm(self.output_projection, "weight", hidden_dim, embedding_dim)
+        self._oconv = _Gemm(self.output_conv, "weight", hidden_dim, num_channels * patch_size ** data_dims, transposed=True)
         self._pos_cache = None
 
     # ------------------------------------------------------------------ reference properties
@@ -382,10 +414,10 @@ class VisionTransformer(nn.Module):
     # ------------------------------------------------------------------ host-side pieces
     def _pos_table(self, n: int, dev, keep: bool):
         """act(Linear(sinusoid(arange(N)))) float32 [N, E] (vit.py:349-351); cached on the no-grad path (``keep`` False, whatever
-        train() / eval() says) until the weights' version counters move."""
+        train() / eval() says) until the version counter or the storage of its weight or bias moves."""
         from ..engine import ops
         lin = self.pos_embedding[1]
-        key = (n, str(dev), lin.weight._version, lin.bias._version, lin.weight.data_ptr())
+        key = (n, str(dev), lin.weight._version, lin.bias._version, lin.weight.data_ptr(), lin.bias.data_ptr())
         if not keep and self._pos_cache is not None and self._pos_cache[0] == key:
             return self._pos_cache[1], None
         idx = torch.arange(n, device=dev, dtype=torch.int64)
@@ -426,7 +458,7 @@ class VisionTransformer(nn.Module):
         from ..engine import ops
         dt = self.compute_dtype
         B = s["shape"][0]
-        dtk = ops.patchify(dpred, self.patch_size, dt, dbias=_grad_of(self.output_conv.bias), acc_dbias=True)
+        dtk = ops.patchify(dpred, self.patch_size, dt, dbias=_grad_or_scratch(self.output_conv.bias), acc_dbias=True)
         dtk5 = dtk.view(B, 1, 1, dtk.shape[1], dtk.shape[2])
         self._oconv.wgrad(s["hp"], dtk5)
         dhp = self._oconv.dgrad(dtk5)
@@ -435,10 +467,11 @@ class VisionTransformer(nn.Module):
         for blk, sb in zip(reversed(self.transformer_blocks), reversed(s["blocks"])):
             dh = blk.run_bwd(dh, sb)
         # embedded = conv_shaper(patches) + pos
-        pe, z = s["pos"]
-        dpos = ops.pos_add_bwd(dh.view(B, dh.shape[3], dh.shape[4]))
-        dz = ops.bias_act_bwd(z, dpos, self.act_code)
-        _small_linear_bwd(dz, pe, self.pos_embedding[1])
+        if any(p.requires_grad for p in self.pos_embedding[1].parameters()):
+            pe, z = s["pos"]
+            dpos = ops.pos_add_bwd(dh.view(B, dh.shape[3], dh.shape[4]))
+            dz = ops.bias_act_bwd(z, dpos, self.act_code)
+            _small_linear_bwd(dz, pe, self.pos_embedding[1])
         g = self.patch_embedder._gemm
         g.wgrad(s["pt5"], dh)
         if not want_dx:
