@@ -316,7 +316,8 @@ int rho_tap_gather_sum(const void* t, int dtype, int64_t n, int64_t d, int64_t h
 
 /* Conv weight [Cout, Cin, kd, kh, kw] float32 (PyTorch layout) -> [taps][CoutP][CinP] dtype,
  * zero padded.  Optional row permutation `row_src` (int32[CoutP], device; -1 = zero row) lets
- * the qkv projection be re-ordered (legacy vs new attention order, unet_v2.py:384,419-431). */
+ * the qkv projection be re-ordered (legacy vs new attention order, unet_v2.py:384,419-431); with it CoutP may be below Cout.
+ * (Here, in rho_prep_conv_weight_dgrad and in rho_wgrad_finalize a tap count beyond INT32_MAX is RHO_E_ARG.) */
 int rho_prep_conv_weight(const float* w, void* out, int dtype, int64_t cout, int64_t cin, int64_t taps,
                          int64_t coutp, int64_t cinp, const int32_t* row_src, void* stream);
 
@@ -478,7 +479,9 @@ int rho_head_conv3d(const void* x, const float* pre_a, const float* pre_b, int p
                     int64_t n, int64_t d, int64_t h, int64_t w_, int64_t c, void* stream);
 
 /* Batched form of rho_wgrad_finalize / rho_wgrad_finalize_phase (ABI 7): a device table of ops, op j on launch blocks
- * [blk0, blk0 + nblk) (ascending, contiguous from 0).  total = cout * cin * kd * kh * kw (elements of the parameter gradient walked,
+ * [blk0, blk0 + nblk) (ascending, contiguous from 0).  rho_wgrad_finalize is the same device code (csrc/weight_tables.hip: one
+ * element map, one LDS walk) on ONE kind-0 op passed by value, with or without accumulation; rho_wgrad_finalize_phase adds one phase
+ * per call where kind 1 sums all phases first - another floating-point order - and is a kernel of its own over the same tap map.  total = cout * cin * kd * kh * kw (elements of the parameter gradient walked,
  * in buffer-row order).  kind 0: grad[row_src ? row_src[r] : r][ci][tap] += dw[tap][r][ci] (dw rows coutp, row width cinb; a bias
  * gradient is cin = kd = kh = kw = cinb = 1 with coutp = the width of the channel-sum vector).  kind 1: all sub-pixel phases of a conv
  * behind a nearest x2 upsample (up_h / up_w say which axes are phased; the phase buffers lie phase_stride floats apart in the order
@@ -500,7 +503,9 @@ int rho_wgrad_finalize_batch(const rho_wfin_op* ops_dev, int64_t n_ops, int64_t 
  * per-tensor rho_prep_conv_weight / _dgrad / _phase / _sel calls above write, the zero-padded (and, for the qkv projection,
  * row-gathered) fp32 bias vectors, and plain fp32 copies (the batched FiLM matrix of ResBlock.emb_layers, unet_v2.py:225-232) -
  * from a table of rho_prep_op in DEVICE memory.  Op j owns launch blocks [blk0, blk0 + nblk) (blk0 ascending, contiguous, op 0 at 0;
- * n_blocks = their sum); field meanings per kind are those of the per-tensor call of the same name:
+ * n_blocks = their sum).  The per-tensor calls run the same device code (csrc/weight_tables.hip: one element map, one LDS walk): each
+ * fills one rho_prep_op from its arguments, checks it and passes it by value to a launch of max(1, min(ceil(total / 256), 2048))
+ * blocks, so a layout has the same bits either way.  Field meanings per kind are those of the per-tensor call of the same name:
  *   RHO_PREP_FWD   out[kd*kh*kw][d1 = coutp][d2 = cinp], perm = row_src;   RHO_PREP_DGRAD  out[taps][d1 = rowsp][d2 = colsp], perm = col_src;
  *   RHO_PREP_PHASE ph_h / ph_w / dgrad, d1 x d2 as rho_prep_conv_weight_phase;   RHO_PREP_SEL kh2 / kw2 / sel_h / sel_w / flip_d / dgrad;
  *   RHO_PREP_VEC   out[d1] (a general gather): out[i] = w[perm ? perm[i] : i] for i < cout (source length cin; perm[i] < 0: zero), 0 beyond -

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "librho_hip.so")
-SOURCES = ["elementwise.hip", "groupnorm.hip", "conv.hip", "wgrad.hip", "attention.hip", "attention_bwd.hip", "select.hip", "embedding.hip",
+SOURCES = ["elementwise.hip", "groupnorm.hip", "conv.hip", "wgrad.hip", "weight_tables.hip", "attention.hip", "attention_bwd.hip", "select.hip", "embedding.hip",
            "sph_harm.hip", "unet_v1.hip", "ends.hip",
            "gaussian.hip", "image.hip", "spectrum.hip", "vit.hip", "optim.hip", "sinkhorn.hip", "ssim.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",

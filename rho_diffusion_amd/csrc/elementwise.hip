@@ -1,4 +1,5 @@
-// HBM-bound kernels of the DDPM loops and the small embedding GEMVs.
+// HBM-bound kernels: the DDPM loops, the small embedding GEMVs, the input packing and the pointwise / resampling helpers of
+// the backward pass (weight preparation and weight-gradient finalize live in weight_tables.hip).
 // Each kernel is a grid-stride loop over 16-byte-per-lane accesses (coalesced 1 KiB per wave
 // instruction), grid capped at 256 CUs x 8 blocks.
 #include <cstdlib>
@@ -772,13 +773,6 @@ extern "C" int rho_linear(const float* x, const float* w, const float* bias, con
 
 // ----------------------------------------------------------------------------- layout
 template <typename T>
-__device__ __forceinline__ T cvt_out(float v);
-template <>
-__device__ __forceinline__ float cvt_out<float>(float v) { return v; }
-template <>
-__device__ __forceinline__ bf16_raw cvt_out<bf16_raw>(float v) { return f32_to_bf16(v); }
-
-template <typename T>
 __global__ __launch_bounds__(256) void k_pack_input(const float* __restrict__ x, T* __restrict__ y, int64_t n, int64_t c,
                                                     int64_t s, int64_t cpad) {
     // thread per (sample, position, 16-byte piece): consecutive lanes write consecutive 16-byte pieces of the
@@ -974,270 +968,7 @@ extern "C" int rho_tap_gather_sum(const void* t, int dtype, int64_t n, int64_t d
     return 0;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_prep_w(const float* __restrict__ w, T* __restrict__ out, int64_t cout, int64_t cin,
-                                                int64_t taps, int64_t coutp, int64_t cinp, const int32_t* __restrict__ row_src) {
-    const int64_t total = taps * coutp * cinp;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t ci = i % cinp;
-        const int64_t co = (i / cinp) % coutp;
-        const int64_t tap = i / (cinp * coutp);
-        int64_t src = row_src ? (int64_t)row_src[co] : (co < cout ? co : -1);
-        float v = 0.0f;
-        if (src >= 0 && src < cout && ci < cin) v = w[(src * cin + ci) * taps + tap];
-        out[i] = cvt_out<T>(v);
-    }
-}
-
-extern "C" int rho_prep_conv_weight(const float* w, void* out, int dtype, int64_t cout, int64_t cin, int64_t taps,
-                                    int64_t coutp, int64_t cinp, const int32_t* row_src, void* stream) {
-    if (!w || !out || cout <= 0 || cin <= 0 || taps <= 0 || cinp < cin || (!row_src && coutp < cout)) return RHO_E_ARG;
-    dim3 grid(grid_for(taps * coutp * cinp, 256)), block(256);
-    if (dtype == RHO_BF16)
-        hipLaunchKernelGGL(k_prep_w<bf16_raw>, grid, block, 0, as_stream(stream), w, (bf16_raw*)out, cout, cin, taps, coutp, cinp, row_src);
-    else if (dtype == RHO_F32)
-        hipLaunchKernelGGL(k_prep_w<float>, grid, block, 0, as_stream(stream), w, (float*)out, cout, cin, taps, coutp, cinp, row_src);
-    else
-        return RHO_E_ARG;
-    RHO_LAUNCH_CHECK();
-    return 0;
-}
-
-// One sub-pixel phase of a conv behind a nearest x2 upsample: on a phased axis (3 taps -> 2) tap r of parity a sums the source
-// taps that land on the same source row: a = 0: {0}, {1, 2};  a = 1: {0, 1}, {2}.
-__device__ __forceinline__ float phase_weight(const float* __restrict__ w, int64_t co, int64_t ci, int64_t cin, int tap2, int kd, int kh,
-                                              int kw, int ph_h, int ph_w) {
-    const int kh2 = ph_h ? 2 : kh, kw2 = ph_w ? 2 : kw;
-    const int c2 = tap2 % kw2, r2 = (tap2 / kw2) % kh2, dz = tap2 / (kw2 * kh2);
-    int rlo = r2, rhi = r2, clo = c2, chi = c2;          // source tap range per axis
-    if (ph_h) { if (ph_h == 1) { rlo = r2 ? 1 : 0; rhi = r2 ? 2 : 0; } else { rlo = r2 ? 2 : 0; rhi = r2 ? 2 : 1; } }
-    if (ph_w) { if (ph_w == 1) { clo = c2 ? 1 : 0; chi = c2 ? 2 : 0; } else { clo = c2 ? 2 : 0; chi = c2 ? 2 : 1; } }
-    const float* base = w + (co * cin + ci) * ((int64_t)kd * kh * kw) + (int64_t)dz * kh * kw;
-    float v = 0.0f;
-    for (int r = rlo; r <= rhi; ++r)
-        for (int c = clo; c <= chi; ++c) v += base[r * kw + c];
-    return v;
-}
-
-// dgrad = 0: forward layout [tap2][coutp][cinp];  dgrad = 1: data-gradient layout [tap'][rowsp = ceil32(cin)][colsp] with flipped
-// taps and transposed channels (as k_prep_w_dgrad), so the forward kernel run on the phase's dY computes its share of dX
-template <typename T>
-__global__ __launch_bounds__(256) void k_prep_w_phase(const float* __restrict__ w, T* __restrict__ out, int64_t cout, int64_t cin, int kd,
-                                                      int kh, int kw, int ph_h, int ph_w, int64_t d1, int64_t d2, int dgrad) {
-    const int64_t taps2 = (int64_t)kd * (ph_h ? 2 : kh) * (ph_w ? 2 : kw);
-    const int64_t total = taps2 * d1 * d2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i2 = i % d2, i1 = (i / d2) % d1;
-        const int tap = (int)(i / (d2 * d1));
-        float v = 0.0f;
-        if (!dgrad) {                 // d1 = coutp, d2 = cinp
-            if (i1 < cout && i2 < cin) v = phase_weight(w, i1, i2, cin, tap, kd, kh, kw, ph_h, ph_w);
-        } else {                      // d1 = rows (input channels), d2 = columns (output channels)
-            if (i2 < cout && i1 < cin) v = phase_weight(w, i2, i1, cin, (int)(taps2 - 1 - tap), kd, kh, kw, ph_h, ph_w);
-        }
-        out[i] = cvt_out<T>(v);
-    }
-}
-
-extern "C" int rho_prep_conv_weight_phase(const float* w, void* out, int dtype, int64_t cout, int64_t cin, int kd, int kh, int kw, int ph_h,
-                                          int ph_w, int64_t coutp, int64_t cinp, int dgrad, void* stream) {
-    if (!w || !out || cout <= 0 || cin <= 0 || kd <= 0 || kh <= 0 || kw <= 0 || cinp < cin || coutp < cout) return RHO_E_ARG;
-    if (ph_h < 0 || ph_h > 2 || ph_w < 0 || ph_w > 2 || (!ph_h && !ph_w) || (ph_h && kh != 3) || (ph_w && kw != 3)) return RHO_E_ARG;
-    const int64_t d1 = dgrad ? cinp : coutp, d2 = dgrad ? coutp : cinp;
-    const int64_t total = (int64_t)kd * (ph_h ? 2 : kh) * (ph_w ? 2 : kw) * d1 * d2;
-    dim3 grid(grid_for(total, 256)), block(256);
-    if (dtype == RHO_BF16)
-        hipLaunchKernelGGL(k_prep_w_phase<bf16_raw>, grid, block, 0, as_stream(stream), w, (bf16_raw*)out, cout, cin, kd, kh, kw, ph_h, ph_w, d1, d2, dgrad);
-    else if (dtype == RHO_F32)
-        hipLaunchKernelGGL(k_prep_w_phase<float>, grid, block, 0, as_stream(stream), w, (float*)out, cout, cin, kd, kh, kw, ph_h, ph_w, d1, d2, dgrad);
-    else
-        return RHO_E_ARG;
-    RHO_LAUNCH_CHECK();
-    return 0;
-}
-
-// Tap selection for the parity splits of a stride-2 conv (rho_prep_conv_weight_sel): new tap r of an axis takes source tap
-// sel >> (4 * r) & 15 of the 3-tap parameter (an axis that keeps its taps passes kh2 = kh and the identity selection).
-template <typename T>
-__global__ __launch_bounds__(256) void k_prep_w_sel(const float* __restrict__ w, T* __restrict__ out, int64_t cout, int64_t cin, int kd,
-                                                    int kh, int kw, int kh2, int kw2, int sel_h, int sel_w, int flip_d, int64_t d1,
-                                                    int64_t d2, int dgrad) {
-    const int64_t taps2 = (int64_t)kd * kh2 * kw2, taps = (int64_t)kd * kh * kw;
-    const int64_t total = taps2 * d1 * d2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i2 = i % d2, i1 = (i / d2) % d1;
-        const int tap = (int)(i / (d2 * d1));
-        const int c2 = tap % kw2, r2 = (tap / kw2) % kh2, dz = tap / (kw2 * kh2);
-        const int ks = ((flip_d ? kd - 1 - dz : dz) * kh + ((sel_h >> (4 * r2)) & 15)) * kw + ((sel_w >> (4 * c2)) & 15);
-        const int64_t co = dgrad ? i2 : i1, ci = dgrad ? i1 : i2;
-        float v = 0.0f;
-        if (co < cout && ci < cin) v = w[(co * cin + ci) * taps + ks];
-        out[i] = cvt_out<T>(v);
-    }
-}
-
-extern "C" int rho_prep_conv_weight_sel(const float* w, void* out, int dtype, int64_t cout, int64_t cin, int kd, int kh, int kw, int kh2,
-                                        int kw2, int sel_h, int sel_w, int flip_d, int64_t coutp, int64_t cinp, int dgrad, void* stream) {
-    if (!w || !out || cout <= 0 || cin <= 0 || kd <= 0 || kh <= 0 || kw <= 0 || kh2 <= 0 || kw2 <= 0 || kh2 > 4 || kw2 > 4 || cinp < cin ||
-        coutp < cout)
-        return RHO_E_ARG;
-    for (int r = 0; r < kh2; ++r) if (((sel_h >> (4 * r)) & 15) >= kh) return RHO_E_ARG;
-    for (int c = 0; c < kw2; ++c) if (((sel_w >> (4 * c)) & 15) >= kw) return RHO_E_ARG;
-    const int64_t d1 = dgrad ? cinp : coutp, d2 = dgrad ? coutp : cinp;
-    const int64_t total = (int64_t)kd * kh2 * kw2 * d1 * d2;
-    dim3 grid(grid_for(total, 256)), block(256);
-    if (dtype == RHO_BF16)
-        hipLaunchKernelGGL(k_prep_w_sel<bf16_raw>, grid, block, 0, as_stream(stream), w, (bf16_raw*)out, cout, cin, kd, kh, kw, kh2, kw2, sel_h, sel_w,
-                           flip_d, d1, d2, dgrad);
-    else if (dtype == RHO_F32)
-        hipLaunchKernelGGL(k_prep_w_sel<float>, grid, block, 0, as_stream(stream), w, (float*)out, cout, cin, kd, kh, kw, kh2, kw2, sel_h, sel_w,
-                           flip_d, d1, d2, dgrad);
-    else
-        return RHO_E_ARG;
-    RHO_LAUNCH_CHECK();
-    return 0;
-}
-
 // ================================================================================================ backward helpers
-
-// dgrad weights: out[tap'][ci][co'] = w[src(co')][ci][taps-1-tap']  (flipped taps, transposed channels), so that the
-// FORWARD kernel run on dY computes dX (autograd of conv_nd).  rows padded to rowsp (multiple of 32), cols to colsp.
-template <typename T>
-__global__ __launch_bounds__(256) void k_prep_w_dgrad(const float* __restrict__ w, T* __restrict__ out, int64_t cout, int64_t cin,
-                                                      int64_t taps, int64_t rowsp, int64_t colsp, const int32_t* __restrict__ col_src) {
-    const int64_t total = taps * rowsp * colsp;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t col = i % colsp;            // original output channel (possibly permuted)
-        const int64_t row = (i / colsp) % rowsp;  // original input channel
-        const int64_t tap = i / (colsp * rowsp);
-        int64_t src = col_src ? (col < cout ? (int64_t)col_src[col] : -1) : (col < cout ? col : -1);
-        float v = 0.0f;
-        if (src >= 0 && src < cout && row < cin) v = w[(src * cin + row) * taps + (taps - 1 - tap)];
-        out[i] = cvt_out<T>(v);
-    }
-}
-
-extern "C" int rho_prep_conv_weight_dgrad(const float* w, void* out, int dtype, int64_t cout, int64_t cin, int64_t taps,
-                                          int64_t rowsp, int64_t colsp, const int32_t* col_src, void* stream) {
-    if (!w || !out || cout <= 0 || cin <= 0 || taps <= 0 || rowsp < cin || colsp < cout) return RHO_E_ARG;
-    dim3 grid(grid_for(taps * rowsp * colsp, 256)), block(256);
-    if (dtype == RHO_BF16)
-        hipLaunchKernelGGL(k_prep_w_dgrad<bf16_raw>, grid, block, 0, as_stream(stream), w, (bf16_raw*)out, cout, cin, taps, rowsp, colsp, col_src);
-    else if (dtype == RHO_F32)
-        hipLaunchKernelGGL(k_prep_w_dgrad<float>, grid, block, 0, as_stream(stream), w, (float*)out, cout, cin, taps, rowsp, colsp, col_src);
-    else
-        return RHO_E_ARG;
-    RHO_LAUNCH_CHECK();
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ batched weight preparation
-// rho_prep_batch: every prepared layout of every convolution of a model (forward / data-gradient / sub-pixel phase / parity
-// selection), the padded fp32 biases and the batched FiLM matrix in ONE launch after an optimizer step, driven by a device table of
-// rho_prep_op.  The per-tensor entry points above cost ~170 launches of a few microseconds per training step at BASELINE
-// configs[2] (2.7 ms) and as many again on the launch-bound 2-D configurations.  A block finds its op by bisection on blk0.
-__device__ __forceinline__ float prep_elem(const rho_prep_op& o, int64_t i) {
-    const int64_t taps = (int64_t)o.kd * o.kh * o.kw;
-    switch (o.kind) {
-    case RHO_PREP_FWD: {                       // [taps][coutp = d1][cinp = d2]
-        const int64_t ci = i % o.d2, co = (i / o.d2) % o.d1, tap = i / (o.d2 * o.d1);
-        const int64_t src = o.perm ? (int64_t)o.perm[co] : (co < o.cout ? co : -1);
-        return (src >= 0 && src < o.cout && ci < o.cin) ? o.w[(src * o.cin + ci) * taps + tap] : 0.0f;
-    }
-    case RHO_PREP_DGRAD: {                     // [taps'][rowsp = d1][colsp = d2], flipped taps, transposed channels
-        const int64_t col = i % o.d2, row = (i / o.d2) % o.d1, tap = i / (o.d2 * o.d1);
-        const int64_t src = o.perm ? (col < o.cout ? (int64_t)o.perm[col] : -1) : (col < o.cout ? col : -1);
-        return (src >= 0 && src < o.cout && row < o.cin) ? o.w[(src * o.cin + row) * taps + (taps - 1 - tap)] : 0.0f;
-    }
-    case RHO_PREP_PHASE: {
-        const int64_t taps2 = (int64_t)o.kd * (o.ph_h ? 2 : o.kh) * (o.ph_w ? 2 : o.kw);
-        const int64_t i2 = i % o.d2, i1 = (i / o.d2) % o.d1;
-        const int tap = (int)(i / (o.d2 * o.d1));
-        if (!o.dgrad) return (i1 < o.cout && i2 < o.cin) ? phase_weight(o.w, i1, i2, o.cin, tap, o.kd, o.kh, o.kw, o.ph_h, o.ph_w) : 0.0f;
-        return (i2 < o.cout && i1 < o.cin) ? phase_weight(o.w, i2, i1, o.cin, (int)(taps2 - 1 - tap), o.kd, o.kh, o.kw, o.ph_h, o.ph_w) : 0.0f;
-    }
-    case RHO_PREP_SEL: {
-        const int64_t i2 = i % o.d2, i1 = (i / o.d2) % o.d1;
-        const int tap = (int)(i / (o.d2 * o.d1));
-        const int c2 = tap % o.kw2, r2 = (tap / o.kw2) % o.kh2, dz = tap / (o.kw2 * o.kh2);
-        const int ks = ((o.flip_d ? o.kd - 1 - dz : dz) * o.kh + ((o.sel_h >> (4 * r2)) & 15)) * o.kw + ((o.sel_w >> (4 * c2)) & 15);
-        const int64_t co = o.dgrad ? i2 : i1, ci = o.dgrad ? i1 : i2;
-        return (co < o.cout && ci < o.cin) ? o.w[(co * o.cin + ci) * taps + ks] : 0.0f;
-    }
-    default: {                                 // RHO_PREP_VEC: out[i] = w[perm ? perm[i] : i] for i < cout (perm < 0: zero), zero up to d1
-        const int64_t src = (o.perm && i < o.cout) ? (int64_t)o.perm[i] : i;
-        return (i < o.cout && src >= 0 && src < o.cin) ? o.w[src] : 0.0f;
-    }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_prep_batch(const rho_prep_op* __restrict__ ops, int nops) {
-    int lo = 0, hi = nops - 1;
-    const int b = (int)blockIdx.x;
-    while (lo < hi) {                          // last op whose first block is <= b
-        const int mid = (lo + hi + 1) >> 1;
-        if (ops[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-    }
-    const rho_prep_op o = ops[lo];
-    const int taps_ = o.kd * o.kh * o.kw;
-    if ((o.kind == RHO_PREP_FWD || o.kind == RHO_PREP_DGRAD) && taps_ > 1 && taps_ <= 32) {
-        // [row][channel][tap] -> [tap][..][..] through LDS (the elementwise walk reads the parameter with a stride of `taps` floats
-        // between consecutive threads: 0.5 TB/s).  A unit = 64 consecutive entries of the output's contiguous axis for one entry of
-        // its middle axis: FWD (co, 64 ci): one contiguous read of 64 * taps floats;  DGRAD (ci, 64 co): 64 runs of `taps` floats.
-        // Either way every tap is written as one run of 64 contiguous outputs.
-        __shared__ float tile[64 * 33];
-        const bool fwd = o.kind == RHO_PREP_FWD;
-        const int64_t mid = o.d1, inner = o.d2;                   // out [taps][d1][d2]
-        const int64_t groups = (inner + 63) / 64;
-        const int64_t units = mid * groups;
-        for (int64_t u = b - o.blk0; u < units; u += o.nblk) {
-            const int64_t m_ = u / groups;
-            const int64_t i0 = (u % groups) * 64;
-            for (int e = threadIdx.x; e < 64 * taps_; e += 256) {
-                float v = 0.0f;
-                if (fwd) {
-                    // m_ = output row co (maybe permuted / padded), inner = ci: source run w[src][i0 .. i0 + 63][taps]
-                    const int64_t src = o.perm ? (int64_t)o.perm[m_] : (m_ < o.cout ? m_ : -1);
-                    const int64_t ci = i0 + e / taps_;
-                    if (src >= 0 && src < o.cout && ci < o.cin) v = o.w[(src * o.cin + i0) * taps_ + e];
-                    tile[(e / taps_) * 33 + e % taps_] = v;
-                } else {
-                    // m_ = row = input channel ci, inner = col = output channel (maybe permuted): run w[src(col)][m_][taps]
-                    const int c = e / taps_, t = e % taps_;
-                    const int64_t col = i0 + c;
-                    const int64_t src = col < o.cout ? (o.perm ? (int64_t)o.perm[col] : col) : -1;
-                    if (src >= 0 && src < o.cout && m_ < o.cin) v = o.w[(src * o.cin + m_) * taps_ + t];
-                    tile[c * 33 + t] = v;
-                }
-            }
-            __syncthreads();
-            for (int e = threadIdx.x; e < 64 * taps_; e += 256) {
-                const int t = e >> 6, c = e & 63;
-                if (i0 + c < inner) {
-                    const float v = tile[c * 33 + (fwd ? t : taps_ - 1 - t)];
-                    const int64_t oi = ((int64_t)t * mid + m_) * inner + i0 + c;
-                    if (o.dtype == RHO_BF16) reinterpret_cast<bf16_raw*>(o.out)[oi] = f32_to_bf16(v);
-                    else reinterpret_cast<float*>(o.out)[oi] = v;
-                }
-            }
-            __syncthreads();
-        }
-        return;
-    }
-    const int64_t stride = (int64_t)o.nblk * 256;
-    for (int64_t i = (int64_t)(b - o.blk0) * 256 + threadIdx.x; i < o.total; i += stride) {
-        const float v = prep_elem(o, i);
-        if (o.dtype == RHO_BF16) reinterpret_cast<bf16_raw*>(o.out)[i] = f32_to_bf16(v);
-        else reinterpret_cast<float*>(o.out)[i] = v;
-    }
-}
-
-extern "C" int rho_prep_batch(const rho_prep_op* ops_dev, int64_t n_ops, int64_t n_blocks, void* stream) {
-    if (!ops_dev || n_ops <= 0 || n_blocks <= 0 || n_blocks > 0x7FFFFFFF || n_ops > 0x7FFFFFFF) return RHO_E_ARG;
-    hipLaunchKernelGGL(k_prep_batch, dim3((unsigned)n_blocks), dim3(256), 0, as_stream(stream), ops_dev, (int)n_ops);
-    RHO_LAUNCH_CHECK();
-    return 0;
-}
 
 // nearest x2 on H and/or W of a channels-last tensor, 16-byte pieces (materialised only for the wgrad of Upsample.conv)
 __global__ __launch_bounds__(256) void k_upsample2x(const uint4* __restrict__ x, uint4* __restrict__ y, int64_t nd, int h, int w,

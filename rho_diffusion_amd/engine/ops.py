@@ -868,20 +868,154 @@ def pack_input(x: Tensor, dtype: torch.dtype, cpad: Optional[int] = None, out: O
     return out
 
 
+# Prepared layouts of a conv weight [Cout, Cin, *k] float32 (rho_prep_op, include/rho_hip.h): one set of shape rules (prepared_shape),
+# one record builder with the extent checks (prep_op), two sinks with the same add_* methods (PrepTable: one launch; EagerPrep: at once)
+def kernel3(w) -> Tuple[int, int, int]:
+    """(kd, kh, kw) of a conv weight [Cout, Cin, *k] (a tensor or its shape; missing leading axes are 1)."""
+    k = [int(v) for v in getattr(w, "shape", w)[2:]]
+    return tuple([1] * (3 - len(k)) + k)
+
+
+def sel_code(taps) -> int:
+    """A tap selection as rho_prep_conv_weight_sel reads it: new tap r of the axis is source tap (code >> 4r) & 15."""
+    return sum(int(v) << (4 * i) for i, v in enumerate(taps))
+
+
+def _sel_taps(sel_hw, k) -> Tuple[tuple, tuple]:
+    return tuple(tuple(range(k[1 + a])) if sel_hw[a] is None else tuple(sel_hw[a]) for a in (0, 1))
+
+
+def prepared_shape(kind: int, w, dtype: torch.dtype, dgrad: bool = False, *, k=None, phase_hw=(0, 0), sel_hw=(None, None)):
+    """(taps', d1, d2) of the layout ``kind`` (hip.PREP_FWD / DGRAD / PHASE / SEL) of a weight [Cout, Cin, *k] (tensor or shape; ``k``
+    overrides the kernel extents): forward [taps', ceil32(Cout), ceilCK(Cin)], data gradient (PREP_DGRAD, or ``dgrad``) [taps',
+    ceil32(Cin), ceilCK(Cout)]; a phased axis has 2 taps, a selected axis as many as it selects."""
+    shape = getattr(w, "shape", w)
+    cout, cin = int(shape[0]), int(shape[1])
+    kd, kh, kw = kernel3(shape) if k is None else k
+    if kind == hip.PREP_PHASE:
+        kh, kw = (2 if phase_hw[0] else kh), (2 if phase_hw[1] else kw)
+    elif kind == hip.PREP_SEL:
+        kh, kw = (len(s) for s in _sel_taps(sel_hw, (kd, kh, kw)))
+    rows, cols = (cin, cout) if (dgrad or kind == hip.PREP_DGRAD) else (cout, cin)
+    ck = elem_chunk(dtype)
+    return int(kd * kh * kw), -(-rows // 32) * 32, -(-cols // ck) * ck
+
+
+def prep_op(kind: int, w: Tensor, out: Tensor, *, perm: Optional[Tensor] = None, cout=None, cin=None, k=None, phase_hw=(0, 0),
+            sel_hw=(None, None), flip_d: bool = False, dgrad: bool = False, n: Optional[int] = None) -> "hip.PrepOp":
+    """The rho_prep_op record (blk0 / nblk left 0) that writes layout ``kind`` of ``w`` into ``out`` - a pure function of its
+    arguments (any device).  ``cout`` / ``cin`` / ``k`` default to ``w``'s own shape; a caller that re-reads a parameter under
+    another geometry passes them, and every extent the device will index is checked here against what the tensors hold.
+    PREP_VEC: out.flat[i] = w.flat[perm[i] if perm else i] for i < n (default: all of w), zero beyond; ``cin`` = source length."""
+    def bad(why):
+        return RhoHipError(f"prep_op kind {kind}: {why} (w {tuple(w.shape)}, out {tuple(out.shape)} {out.dtype})")
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        raise bad(f"the source must be contiguous float32, got {w.dtype} contiguous={w.is_contiguous()}")
+    if not out.is_contiguous():
+        raise bad("out is not contiguous")
+    if perm is not None and (perm.dtype != torch.int32 or not perm.is_contiguous()):
+        raise bad("the index table must be contiguous int32")
+    op = hip.PrepOp()
+    op.w, op.out, op.perm = w.data_ptr(), out.data_ptr(), (perm.data_ptr() if perm is not None else None)
+    op.kind, op.dtype, op.total = kind, dtype_code(out.dtype), out.numel()
+    op.kd = op.kh = op.kw = 1
+    if kind == hip.PREP_VEC:
+        op.cout, op.cin = (w.numel() if n is None else int(n)), (w.numel() if cin is None else int(cin))
+        op.d1, op.d2 = out.numel(), 1
+        if w.numel() < op.cin:
+            raise bad(f"a source of {op.cin} elements is read, it holds {w.numel()}")
+        if op.cout > out.numel() or (perm is not None and perm.numel() < op.cout):
+            raise bad(f"n = {op.cout} elements are written, out holds {out.numel()}, the index table {perm.numel() if perm is not None else '-'}")
+        return op
+    if out.dim() != 3:
+        raise bad("out must be [taps, d1, d2]")
+    op.cout, op.cin = int(w.shape[0] if cout is None else cout), int(w.shape[1] if cin is None else cin)
+    op.kd, op.kh, op.kw = kd, kh, kw = tuple(int(v) for v in (kernel3(w) if k is None else k))
+    op.d1, op.d2 = int(out.shape[1]), int(out.shape[2])
+    taps2 = kd * kh * kw
+    if kind == hip.PREP_PHASE:
+        op.ph_h, op.ph_w, op.dgrad = int(phase_hw[0]), int(phase_hw[1]), int(dgrad)
+        taps2 = kd * (2 if op.ph_h else kh) * (2 if op.ph_w else kw)
+    elif kind == hip.PREP_SEL:
+        sh, sw = _sel_taps(sel_hw, (kd, kh, kw))
+        op.kh2, op.kw2, op.sel_h, op.sel_w, op.flip_d, op.dgrad = len(sh), len(sw), sel_code(sh), sel_code(sw), int(flip_d), int(dgrad)
+        taps2 = kd * len(sh) * len(sw)
+    if op.cout <= 0 or op.cin <= 0 or op.cout * op.cin * kd * kh * kw > w.numel():
+        raise bad(f"read as {op.cout} x {op.cin} x {kd}x{kh}x{kw} = {op.cout * op.cin * kd * kh * kw} elements, the source holds {w.numel()}")
+    if taps2 * op.d1 * op.d2 != out.numel():
+        raise bad(f"the layout has {taps2} taps: {taps2 * op.d1 * op.d2} elements, out holds {out.numel()}")
+    real1, real2 = (op.cin, op.cout) if (kind == hip.PREP_DGRAD or op.dgrad) else (op.cout, op.cin)
+    if op.d2 < real2 or (op.d1 < real1 and not (kind == hip.PREP_FWD and perm is not None)):
+        raise bad(f"out does not hold [{taps2}, >={real1}, >={real2}]")
+    if perm is not None and perm.numel() < (op.d1 if kind == hip.PREP_FWD else op.cout):
+        raise bad(f"the index table has {perm.numel()} entries")
+    return op
+
+
+class PrepSink:
+    """``add_*``: one method per layout kind, shared by PrepTable and EagerPrep (which say in ``_push`` what becomes of a record).
+    ``geo`` = cout / cin / k of prep_op: the geometry under which the parameter is read, when it is not its own shape."""
+
+    def add_fwd(self, w: Tensor, out: Tensor, row_src: Optional[Tensor] = None, **geo):
+        self._push(prep_op(hip.PREP_FWD, w, out, perm=row_src, **geo), w, out, row_src)
+
+    def add_dgrad(self, w: Tensor, out: Tensor, col_src: Optional[Tensor] = None, **geo):
+        self._push(prep_op(hip.PREP_DGRAD, w, out, perm=col_src, **geo), w, out, col_src)
+
+    def add_phase(self, w: Tensor, out: Tensor, phase_hw, dgrad: bool = False, **geo):
+        self._push(prep_op(hip.PREP_PHASE, w, out, phase_hw=phase_hw, dgrad=dgrad, **geo), w, out, None)
+
+    def add_sel(self, w: Tensor, out: Tensor, sel_hw, flip_d: bool = False, dgrad: bool = False, **geo):
+        self._push(prep_op(hip.PREP_SEL, w, out, sel_hw=sel_hw, flip_d=flip_d, dgrad=dgrad, **geo), w, out, None)
+
+    def add_vec(self, src: Tensor, out: Tensor, perm: Optional[Tensor] = None, n: Optional[int] = None):
+        """out.flat[i] = src.flat[perm[i] if perm else i] for i < n (default: all of src; perm[i] < 0: zero), zeros up to out.numel();
+        src float32, out float32 or bf16 - a general gather (padded biases, plain copies, layouts no other kind describes)."""
+        self._push(prep_op(hip.PREP_VEC, src, out, perm=perm, n=n), src, out, perm)
+
+
+class EagerPrep(PrepSink):
+    """Every layout at once through the per-tensor entry point of its kind (parameters the table cannot read in place, and the
+    stand-alone ops.prep_conv_weight* calls)."""
+
+    def _push(self, op, w: Tensor, out: Tensor, perm: Optional[Tensor]):
+        hip.require_gpu(w, "w")
+        hip.require_gpu(out, "out")
+        k, pads = (op.kd, op.kh, op.kw), ((op.d2, op.d1) if op.dgrad else (op.d1, op.d2)) + (op.dgrad,)      # (coutp, cinp, dgrad)
+        name, args = {hip.PREP_FWD: ("", (k[0] * k[1] * k[2], op.d1, op.d2, op.perm)),
+                      hip.PREP_DGRAD: ("_dgrad", (k[0] * k[1] * k[2], op.d1, op.d2, op.perm)),
+                      hip.PREP_PHASE: ("_phase", k + (op.ph_h, op.ph_w) + pads),
+                      hip.PREP_SEL: ("_sel", k + (op.kh2, op.kw2, op.sel_h, op.sel_w, op.flip_d) + pads)}[op.kind]
+        fn = getattr(hip.lib(), "rho_prep_conv_weight" + name)
+        check(fn(op.w, op.out, op.dtype, op.cout, op.cin, *args, stream()), "rho_prep_conv_weight" + name)
+
+    def add_vec(self, src: Tensor, out: Tensor, perm: Optional[Tensor] = None, n: Optional[int] = None):
+        """The gather in torch (data movement only: it has no per-tensor entry point)."""
+        op = prep_op(hip.PREP_VEC, src, out, perm=perm, n=n)
+        src, flat = src.reshape(-1), out.view(-1)
+        idx = perm[:op.cout].long() if perm is not None else torch.arange(op.cout, device=src.device)
+        got = torch.where((idx >= 0) & (idx < op.cin), src[idx.clamp(0, op.cin - 1)], torch.zeros((), device=src.device))
+        flat[:op.cout].copy_(got)
+        flat[op.cout:].zero_()
+
+
 def prep_conv_weight(w: Tensor, dtype: torch.dtype, coutp: Optional[int] = None, cinp: Optional[int] = None,
                      row_src: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
     """PyTorch conv weight [Cout, Cin, *k] float32 -> [taps, CoutP, CinP] in the engine dtype."""
-    _f32c(w, "w")
-    cout, cin = w.shape[0], w.shape[1]
-    taps = int(math.prod(w.shape[2:])) if w.dim() > 2 else 1
-    ck = elem_chunk(dtype)
-    cinp = cinp or ((cin + ck - 1) // ck) * ck
-    coutp = coutp or ((cout + 31) // 32) * 32
-    out = torch.empty(taps, coutp, cinp, dtype=dtype, device=w.device) if out is None else out
-    if row_src is not None and (row_src.dtype != torch.int32 or row_src.numel() != coutp):
+    taps, d1, d2 = prepared_shape(hip.PREP_FWD, w, dtype)
+    out = torch.empty(taps, coutp or d1, cinp or d2, dtype=dtype, device=w.device) if out is None else out
+    if row_src is not None and (row_src.dtype != torch.int32 or row_src.numel() != out.shape[1]):
         raise RhoHipError("row_src must be int32[coutp]")
-    check(hip.lib().rho_prep_conv_weight(ptr(w), ptr(out), dtype_code(dtype), cout, cin, taps, coutp, cinp, ptr(row_src), stream()),
-          "rho_prep_conv_weight")
+    EagerPrep().add_fwd(w, out, row_src)
+    return out
+
+
+def prep_conv_weight_dgrad(w: Tensor, dtype: torch.dtype, col_src: Optional[Tensor] = None,
+                           out: Optional[Tensor] = None) -> Tensor:
+    """PyTorch conv weight [Cout, Cin, *k] -> dgrad weights [taps, ceil32(Cin), ceilCK(Cout)] (flipped, transposed); a given
+    ``out`` [taps, rows, cols] sets the padded extents."""
+    out = torch.empty(prepared_shape(hip.PREP_DGRAD, w, dtype), dtype=dtype, device=w.device) if out is None else out
+    EagerPrep().add_dgrad(w, out, col_src)
     return out
 
 
@@ -890,22 +1024,8 @@ def prep_conv_weight_phase(w: Tensor, dtype: torch.dtype, phase_hw: Tuple[int, i
     """Weights of one sub-pixel phase of a conv behind a nearest x2 upsample (rho_conv_desc.ph_h / ph_w): parameter
     [Cout, Cin, *k] (k = 3 on a phased axis) -> [kd * kh' * kw', CoutP, CinP] with kh' / kw' = 2 on the phased axes; dgrad: the
     data-gradient layout [taps, ceil32(Cin), ceilCK(Cout)] (flipped, transposed) for a launch with phd_h / phd_w."""
-    _f32c(w, "w")
-    cout, cin = w.shape[0], w.shape[1]
-    k = [1] * (5 - w.dim()) + [int(v) for v in w.shape[2:]]
-    k2 = (k[0], 2 if phase_hw[0] else k[1], 2 if phase_hw[1] else k[2])
-    ck = elem_chunk(dtype)
-    if dgrad:
-        cinp = ((cin + 31) // 32) * 32                   # rows of the dgrad weights = its output channels
-        coutp = ((cout + ck - 1) // ck) * ck             # columns = its input channels (chunked)
-        shape = (k2[0] * k2[1] * k2[2], cinp, coutp)
-    else:
-        cinp = ((cin + ck - 1) // ck) * ck
-        coutp = ((cout + 31) // 32) * 32
-        shape = (k2[0] * k2[1] * k2[2], coutp, cinp)
-    out = torch.empty(*shape, dtype=dtype, device=w.device) if out is None else out
-    check(hip.lib().rho_prep_conv_weight_phase(ptr(w), ptr(out), dtype_code(dtype), cout, cin, k[0], k[1], k[2], int(phase_hw[0]),
-                                               int(phase_hw[1]), coutp, cinp, int(dgrad), stream()), "rho_prep_conv_weight_phase")
+    out = torch.empty(prepared_shape(hip.PREP_PHASE, w, dtype, dgrad, phase_hw=phase_hw), dtype=dtype, device=w.device) if out is None else out
+    EagerPrep().add_phase(w, out, phase_hw, dgrad=dgrad)
     return out
 
 
@@ -913,27 +1033,12 @@ def prep_conv_weight_sel(w: Tensor, dtype: torch.dtype, sel_hw, *, flip_d: bool 
                          out: Optional[Tensor] = None) -> Tensor:
     """Tap selection of a 3-tap parameter for the parity splits of a stride-2 conv (rho_prep_conv_weight_sel): sel_hw = (taps of H,
     taps of W), each a tuple of source tap indices (None keeps the axis)."""
-    _f32c(w, "w")
-    cout, cin = w.shape[0], w.shape[1]
-    k = [1] * (5 - w.dim()) + [int(v) for v in w.shape[2:]]
-    sh = tuple(range(k[1])) if sel_hw[0] is None else tuple(sel_hw[0])
-    sw = tuple(range(k[2])) if sel_hw[1] is None else tuple(sel_hw[1])
-    code = lambda t: sum(int(v) << (4 * i) for i, v in enumerate(t))      # noqa: E731
-    ck = elem_chunk(dtype)
-    taps2 = k[0] * len(sh) * len(sw)
-    if dgrad:
-        cinp, coutp = ((cin + 31) // 32) * 32, ((cout + ck - 1) // ck) * ck
-        shape = (taps2, cinp, coutp)
-    else:
-        cinp, coutp = ((cin + ck - 1) // ck) * ck, ((cout + 31) // 32) * 32
-        shape = (taps2, coutp, cinp)
-    out = torch.empty(*shape, dtype=dtype, device=w.device) if out is None else out
-    check(hip.lib().rho_prep_conv_weight_sel(ptr(w), ptr(out), dtype_code(dtype), cout, cin, k[0], k[1], k[2], len(sh), len(sw), code(sh),
-                                             code(sw), int(flip_d), coutp, cinp, int(dgrad), stream()), "rho_prep_conv_weight_sel")
+    out = torch.empty(prepared_shape(hip.PREP_SEL, w, dtype, dgrad, sel_hw=sel_hw), dtype=dtype, device=w.device) if out is None else out
+    EagerPrep().add_sel(w, out, sel_hw, flip_d=flip_d, dgrad=dgrad)
     return out
 
 
-class PrepTable:
+class PrepTable(PrepSink):
     """Device table of rho_prep_op for rho_prep_batch: every prepared weight layout / padded bias / fp32 copy of a model in one
     launch.  ``add_*`` mirror the per-tensor prep calls (same arguments, same results); ``launch()`` uploads the table once."""
 
@@ -944,54 +1049,13 @@ class PrepTable:
         self._dev = None
         self._blocks = 0
 
-    def _push(self, kind, w: Tensor, out: Tensor, *, cout, cin, d1, d2, perm=None, k=(1, 1, 1), kh2=0, kw2=0, ph=(0, 0), sel=(0, 0),
-              flip_d=False, dgrad=False):
-        _f32c(w, "w")
-        op = hip.PrepOp()
-        op.w, op.out, op.perm = w.data_ptr(), out.data_ptr(), (perm.data_ptr() if perm is not None else None)
-        op.cout, op.cin, op.d1, op.d2, op.total = int(cout), int(cin), int(d1), int(d2), int(out.numel())
-        op.kind, op.dtype = kind, hip.dtype_code(out.dtype)
-        op.kd, op.kh, op.kw, op.kh2, op.kw2 = int(k[0]), int(k[1]), int(k[2]), int(kh2), int(kw2)
-        op.ph_h, op.ph_w, op.sel_h, op.sel_w, op.flip_d, op.dgrad = int(ph[0]), int(ph[1]), int(sel[0]), int(sel[1]), int(flip_d), int(dgrad)
-        nblk = max(1, min((op.total + 1023) // 1024, int(os.environ.get("RHO_PREP_MAX_BLOCKS", "2048"))))
-        op.blk0, op.nblk = self._blocks, nblk
-        self._blocks += nblk
+    def _push(self, op, w: Tensor, out: Tensor, perm: Optional[Tensor]):
+        hip.require_gpu(w, "w")
+        op.blk0, op.nblk = self._blocks, max(1, min((op.total + 1023) // 1024, int(os.environ.get("RHO_PREP_MAX_BLOCKS", "2048"))))
+        self._blocks += op.nblk
         self.ops.append(op)
         self.keep.append((w, out, perm))
         self._dev = None
-
-    @staticmethod
-    def _k3(w: Tensor):
-        return [1] * (5 - w.dim()) + [int(v) for v in w.shape[2:]] if w.dim() > 2 else [1, 1, 1]
-
-    def add_fwd(self, w: Tensor, out: Tensor, row_src: Optional[Tensor] = None, k=None):
-        """rho_prep_conv_weight: [Cout, Cin, *k] -> out [taps, CoutP, CinP].  ``k`` overrides the kernel extents of ``w``'s shape
-        (a parameter re-read as a GEMM: any (kd, kh, kw) whose product is the tap count of the view)."""
-        k = self._k3(w) if k is None else k
-        self._push(hip.PREP_FWD, w, out, cout=w.shape[0], cin=w.shape[1], d1=out.shape[1], d2=out.shape[2], perm=row_src, k=k)
-
-    def add_dgrad(self, w: Tensor, out: Tensor, col_src: Optional[Tensor] = None):
-        self._push(hip.PREP_DGRAD, w, out, cout=w.shape[0], cin=w.shape[1], d1=out.shape[1], d2=out.shape[2], perm=col_src, k=self._k3(w))
-
-    def add_phase(self, w: Tensor, out: Tensor, phase_hw, dgrad: bool = False):
-        self._push(hip.PREP_PHASE, w, out, cout=w.shape[0], cin=w.shape[1], d1=out.shape[1], d2=out.shape[2], k=self._k3(w), ph=phase_hw,
-                   dgrad=dgrad)
-
-    def add_sel(self, w: Tensor, out: Tensor, sel_hw, flip_d: bool = False, dgrad: bool = False):
-        k = self._k3(w)
-        sh = tuple(range(k[1])) if sel_hw[0] is None else tuple(sel_hw[0])
-        sw = tuple(range(k[2])) if sel_hw[1] is None else tuple(sel_hw[1])
-        code = lambda t: sum(int(v) << (4 * i) for i, v in enumerate(t))      # noqa: E731
-        self._push(hip.PREP_SEL, w, out, cout=w.shape[0], cin=w.shape[1], d1=out.shape[1], d2=out.shape[2], k=k, kh2=len(sh), kw2=len(sw),
-                   sel=(code(sh), code(sw)), flip_d=flip_d, dgrad=dgrad)
-
-    def add_vec(self, src: Tensor, out: Tensor, perm: Optional[Tensor] = None, n: Optional[int] = None):
-        """out.flat[i] = src.flat[perm[i] if perm else i] for i < n (default: all of src; perm[i] < 0: zero), zeros up to out.numel();
-        src float32, out float32 or bf16 - a general gather (padded biases, plain copies, layouts no other kind describes)."""
-        if not out.is_contiguous():
-            raise RhoHipError("add_vec: out must be contiguous")
-        n = src.numel() if n is None else n
-        self._push(hip.PREP_VEC, src, out, cout=n, cin=src.numel(), d1=out.numel(), d2=1, perm=perm)
 
     def launch(self) -> None:
         if not self.ops:
@@ -1257,24 +1321,6 @@ def attention_variant(dtype: torch.dtype, ch: int, backward: bool = False) -> st
 
 
 # ============================================================================= backward ops
-def prep_conv_weight_dgrad(w: Tensor, dtype: torch.dtype, col_src: Optional[Tensor] = None,
-                           out: Optional[Tensor] = None) -> Tensor:
-    """PyTorch conv weight [Cout, Cin, *k] -> dgrad weights [taps, ceil32(Cin), ceilCK(Cout)] (flipped, transposed); a given
-    ``out`` [taps, rows, cols] sets the padded extents."""
-    _f32c(w, "w")
-    cout, cin = w.shape[0], w.shape[1]
-    taps = int(math.prod(w.shape[2:])) if w.dim() > 2 else 1
-    ck = elem_chunk(dtype)
-    if out is None:
-        out = torch.empty(taps, ((cin + 31) // 32) * 32, ((cout + ck - 1) // ck) * ck, dtype=dtype, device=w.device)
-    if out.shape[0] != taps or out.shape[1] < cin or out.shape[2] < cout or out.dtype != dtype or not out.is_contiguous():
-        raise RhoHipError(f"prep_conv_weight_dgrad: out {tuple(out.shape)} {out.dtype} does not hold [{taps}, >={cin}, >={cout}] {dtype}")
-    rowsp, colsp = out.shape[1], out.shape[2]
-    check(hip.lib().rho_prep_conv_weight_dgrad(ptr(w), ptr(out), dtype_code(dtype), cout, cin, taps, rowsp, colsp, ptr(col_src),
-                                               stream()), "rho_prep_conv_weight_dgrad")
-    return out
-
-
 def conv_wgrad(desc: ConvDesc, dy: Tensor, dw: Tensor, dbias: Optional[Tensor] = None) -> None:
     """Accumulate the weight gradient of the forward conv `desc` into the fp32 buffer dw [taps, coutp, cin] (and, when given,
     the channel sums of dy = the bias gradient into dbias [coutp])."""

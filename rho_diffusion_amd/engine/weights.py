@@ -1,5 +1,6 @@
-"""Conv parameters prepared for the kernels.  ``_ConvW.layouts`` is the one list of a convolution's layouts; it is written as
-records of the one-launch ``ops.PrepTable`` (``prep_into``) or, for parameters that are not contiguous, eagerly (``refresh``)."""
+"""Conv parameters prepared for the kernels.  ``_ConvW.layouts`` is the one list of a convolution's layouts and ``_ConvW._walk`` the
+one walk over it: into the one-launch ``ops.PrepTable`` (``prep_into``) or, for parameters that are not contiguous, into
+``ops.EagerPrep`` (``refresh``)."""
 from __future__ import annotations
 
 from typing import Iterator, Optional, Tuple
@@ -7,6 +8,7 @@ from typing import Iterator, Optional, Tuple
 import torch
 from torch import nn
 
+from .. import hip
 from . import ops
 
 Tensor = torch.Tensor
@@ -19,12 +21,10 @@ class _ConvW:
     def __init__(self, weight: nn.Parameter, bias: nn.Parameter, dtype, row_src: Optional[Tensor] = None):
         self.weight, self.bias_param, self.dtype = weight, bias, dtype
         self.cout, self.cin = weight.shape[0], weight.shape[1]
-        self.kernel = k = tuple([1] * (5 - weight.dim()) + [int(v) for v in weight.shape[2:]])
+        self.kernel = k = ops.kernel3(weight)
         self.taps = int(k[0] * k[1] * k[2])
         self._geometry()
-        ck = ops.elem_chunk(dtype)
-        self.cinp = ((self.cin + ck - 1) // ck) * ck
-        self.coutp = ((self.cout + 31) // 32) * 32
+        _, self.coutp, self.cinp = ops.prepared_shape(hip.PREP_FWD, (self.cout, self.cin), dtype)
         self.row_src = row_src
         dev = weight.device
         self.w = torch.empty(self.taps, self.coutp, self.cinp, dtype=dtype, device=dev)
@@ -47,15 +47,18 @@ class _ConvW:
     def _bias_source(self) -> Tensor:
         return self.bias_param.detach()
 
+    def _dgrad_rows(self) -> int:
+        return ops.prepared_shape(hip.PREP_DGRAD, (self.cout, self.cin), self.dtype)[1]
+
     def _want_zero_bias(self) -> None:          # the bias of every data-gradient launch: one zero per row of the dgrad weights
         if self.zero_bias is None:
-            self.zero_bias = torch.zeros(((self.cin + 31) // 32) * 32, dtype=torch.float32, device=self.w.device)
+            self.zero_bias = torch.zeros(self._dgrad_rows(), dtype=torch.float32, device=self.w.device)
 
     def enable_dgrad(self) -> None:
         if self.wd is None:
-            self.wd = torch.empty(self.taps, ((self.cin + 31) // 32) * 32, self.coutp, dtype=self.dtype, device=self.w.device)
+            self.wd = torch.empty(self.taps, self._dgrad_rows(), self.coutp, dtype=self.dtype, device=self.w.device)
             self._want_zero_bias()
-            ops.prep_conv_weight_dgrad(self._source(), self.dtype, self.row_src, out=self.wd)
+            ops.EagerPrep().add_dgrad(self._source(), self.wd, self.row_src, cout=self.cout, cin=self.cin, k=self.kernel)
 
     def enable_phases(self, up_hw, dgrad: bool = False) -> None:
         """The conv sits behind a nearest x2 upsample of the axes flagged in up_hw: one 2-tap weight set per output parity
@@ -101,16 +104,26 @@ class _ConvW:
     def layouts(self) -> Iterator[Tuple[str, Tensor, dict]]:
         """(kind, buffer, arguments) of every prepared layout this conv has now - the ONE enumeration ``prep_into`` and ``refresh``
         walk: a new layout is listed here."""
-        yield "fwd", self.w, {}
+        yield "fwd", self.w, dict(row_src=self.row_src)
         yield "bias", self.b, {}
         if self.wd is not None:
-            yield "dgrad", self.wd, {}
+            yield "dgrad", self.wd, dict(col_src=self.row_src)
         for lst, dg in ((self.wph, False), (self.wphd, True)):
             for ph, t in (lst or []):
                 yield "phase", t, dict(phase_hw=ph, dgrad=dg)
         for lst, dg in ((self.ws2, False), (self.ws2d, True)):
             for ab, t in (lst or []):
                 yield "sel", t, self._s2_args(ab, dg)
+
+    def _walk(self, sink, w: Tensor, bsrc: Tensor) -> None:
+        """Every layout of ``layouts()`` into ``sink`` (ops.PrepTable or ops.EagerPrep), read from the source ``w`` under this object's
+        geometry - which the sink checks against what ``w`` holds."""
+        geo = dict(cout=self.cout, cin=self.cin, k=self.kernel)
+        for kind, t, kw in self.layouts():
+            if kind == "bias":
+                sink.add_vec(bsrc, t, perm=self.row_src, n=(self.row_src.numel() if self.row_src is not None else bsrc.numel()))
+            else:
+                getattr(sink, "add_" + kind)(w, t, **kw, **geo)
 
     def prep_into(self, table: "ops.PrepTable") -> bool:
         """Append this conv's prepared layouts (what ``refresh`` writes) to a rho_prep_batch table; False if it cannot be batched."""
@@ -119,37 +132,11 @@ class _ConvW:
         w = self._source()                      # a view of the parameter (reshape of a contiguous tensor)
         if w.data_ptr() != self.weight.data_ptr():
             return False
-        bsrc = self._bias_source()
-        for kind, t, kw in self.layouts():
-            if kind == "fwd":
-                table.add_fwd(w, t, self.row_src)
-            elif kind == "bias":
-                table.add_vec(bsrc, t, perm=self.row_src, n=(self.row_src.numel() if self.row_src is not None else bsrc.numel()))
-            elif kind == "dgrad":
-                table.add_dgrad(w, t, self.row_src)
-            elif kind == "phase":
-                table.add_phase(w, t, **kw)
-            else:
-                table.add_sel(w, t, **kw)
+        self._walk(table, w, self._bias_source())
         return True
 
     def refresh(self) -> None:
-        w = self._source()
-        for kind, t, kw in self.layouts():
-            if kind == "fwd":
-                ops.prep_conv_weight(w, self.dtype, self.coutp, self.cinp, self.row_src, out=t)
-            elif kind == "bias":
-                b = self._bias_source()
-                if self.row_src is not None:
-                    b = b[self.row_src.long()]           # gather (data movement only)
-                t[: b.numel()].copy_(b)
-                t[b.numel():].zero_()                    # (the padded rows, as the batched gather writes them)
-            elif kind == "dgrad":
-                ops.prep_conv_weight_dgrad(w, self.dtype, self.row_src, out=t)
-            elif kind == "phase":
-                ops.prep_conv_weight_phase(w, self.dtype, out=t, **kw)
-            else:
-                ops.prep_conv_weight_sel(w, self.dtype, out=t, **kw)
+        self._walk(ops.EagerPrep(), self._source(), self._bias_source())
 
 
 class _StemAsGemm(_ConvW):

@@ -118,16 +118,13 @@ class _Gemm:
         return self.weight.detach().view(self.P, self.Q)
 
     def prepared(self, dt):
-        from .. import hip
         from ..engine import ops
         w = self._w2d()
         key = (w.data_ptr(), self.weight._version, dt)
         if self._key != key:
             P32, Q32 = _c32(self.P), _c32(self.Q)
             self.A = ops.prep_conv_weight(w, dt, coutp=P32, cinp=Q32)                       # [1, P32, Q32]: rows P, contraction over Q
-            self.Bm = torch.empty(1, Q32, P32, dtype=dt, device=w.device)                   # [1, Q32, P32]: rows Q, contraction over P
-            hip.check(hip.lib().rho_prep_conv_weight_dgrad(hip.ptr(w), hip.ptr(self.Bm), hip.dtype_code(dt), self.P, self.Q, 1, Q32, P32,
-                                                           None, hip.stream()), "rho_prep_conv_weight_dgrad")
+            self.Bm = ops.prep_conv_weight_dgrad(w, dt, out=torch.empty(1, Q32, P32, dtype=dt, device=w.device))   # rows Q, contraction over P
             self._key = key
         return (self.Bm, self.A) if self.transposed else (self.A, self.Bm)
 

@@ -2,15 +2,16 @@
 weight_table_cases.py (integer operands, outputs inside NaN-prefilled guarded buffers, test_weight_table_cases_host.py proves the
 references):
 
-  rho_prep_batch            (k_prep_batch, csrc/elementwise.hip) through ops.PrepTable: every layout kind in ONE table of 49 ops
+  rho_prep_batch            (k_prep_batch, csrc/weight_tables.hip) through ops.PrepTable: every layout kind in ONE table of 49 ops
                             (the bisection finds first, middle and last ops), the LDS transpose path at 3 / 9 / 27 / 32 taps with
                             ragged channel groups and row tables, the elementwise path at 1 and 36 taps, again with the per-op block
                             cap at 3 (several trips of both walks), as a one-op table, and the engine's own table against the eager
                             per-tensor refresh.
-  rho_wgrad_finalize_batch  (k_wgrad_finalize_batch, csrc/wgrad.hip) through ops.WfinTable over a synthetic arena: kinds 0 / 1 / 2,
-                            LDS and elementwise walks, row tables with holes, nblk = 1, accumulation onto prefilled gradients.
+  rho_wgrad_finalize_batch  (k_wgrad_finalize_batch, csrc/weight_tables.hip) through ops.WfinTable over a synthetic arena: kinds
+                            0 / 1 / 2, LDS and elementwise walks, row tables with holes, nblk = 1, accumulation onto prefilled gradients.
 
-Each result is also compared with the per-tensor entry point of the same layout where one exists."""
+The per-tensor entry points of the same layouts (k_prep_one through ops.EagerPrep, k_wfin_one, k_wgrad_finalize_phase) run the same
+device code on one op passed by value: they are judged by the same references, and each batched result is compared with theirs."""
 import math
 
 import pytest
@@ -45,52 +46,33 @@ def _collect(failures, fn, *a):
 
 
 # ============================================================================================ rho_prep_batch
-def _prep_table(ops, names, dtype):
-    """One PrepTable over the ops ``names`` -> (table, {name: (flat, view)}); the table keeps the device operands alive."""
-    table, outs = ops.PrepTable(DEV), {}
-    for name in names:
-        io = X.prep_io(name, dtype)
-        c, w = io["case"], io["w"].to(DEV)
-        perm = io["perm"].to(DEV) if io["perm"] is not None else None
-        flat, out = guarded(io["out_shape"], X.TORCH_DTYPE[io["out_dtype"]])
-        if c["kind"] == "fwd":
-            table.add_fwd(w, out, perm, k=c.get("k"))
-        elif c["kind"] == "dgrad":
-            table.add_dgrad(w, out, perm)
-        elif c["kind"] == "phase":
-            table.add_phase(w, out, c["ph"], dgrad=c["dgrad"])
-        elif c["kind"] == "sel":
-            table.add_sel(w, out, c["sel"], flip_d=c["flip_d"], dgrad=c["dgrad"])
-        else:
-            table.add_vec(w.reshape(-1), out, perm=perm, n=io["n"])
-        outs[name] = (flat, out)
-    return table, outs
+def _prep_into(sink, names, dtype):
+    """The ops ``names`` into ``sink`` (an ops.PrepTable, or ops.EagerPrep: the per-tensor entry points, launched at once), each
+    output inside a guarded buffer -> {name: (flat, view)}."""
+    return X.prep_into(sink, names, dtype, guarded, DEV)
 
 
 def _launch(ops, names, dtype):
-    table, outs = _prep_table(ops, names, dtype)
+    table = ops.PrepTable(DEV)
+    outs = _prep_into(table, names, dtype)
     table.launch()
     torch.cuda.synchronize()
     return table, {n: (flat, out, out.float().cpu()) for n, (flat, out) in outs.items()}
 
 
-def _per_tensor(ops, name, dtype):
-    """The per-tensor entry point's result for the op, or None where the layout has none (the general gather)."""
-    io = X.prep_io(name, dtype)
-    c, w, td = io["case"], io["w"].to(DEV), X.TORCH_DTYPE[dtype]
-    perm = io["perm"].to(DEV) if io["perm"] is not None else None
-    if c["kind"] == "fwd":
-        return ops.prep_conv_weight(w, td, io["out_shape"][1], io["out_shape"][2], perm)
-    if c["kind"] == "dgrad":
-        return ops.prep_conv_weight_dgrad(w, td, perm)
-    if c["kind"] == "phase":
-        return ops.prep_conv_weight_phase(w, td, c["ph"], dgrad=c["dgrad"])
-    if c["kind"] == "sel":
-        return ops.prep_conv_weight_sel(w, td, c["sel"], flip_d=c["flip_d"], dgrad=c["dgrad"])
-    return None
-
-
 ALL_PREP = [c["name"] for c in X.PREP_CASES]
+PER_TENSOR_PREP = [c["name"] for c in X.PREP_CASES if c["kind"] != "vec"]       # (the general gather has no per-tensor entry point)
+
+
+@pytest.fixture(scope="module")
+def per_tensor_runs(ops):
+    """Every layout with a per-tensor entry point through it (rho_prep_conv_weight / _dgrad / _phase / _sel on k_prep_one)."""
+    res = {}
+    for dt in DTYPES:
+        outs = _prep_into(ops.EagerPrep(), PER_TENSOR_PREP, dt)
+        torch.cuda.synchronize()
+        res[dt] = {n: (flat, out, out.float().cpu()) for n, (flat, out) in outs.items()}
+    return res
 
 
 @pytest.fixture(scope="module")
@@ -118,19 +100,51 @@ def test_prep_batch_every_layout_bit_equal_to_the_reference(prep_runs, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-def test_prep_batch_equals_the_per_tensor_entry_points(ops, prep_runs, dtype):
+def test_prep_batch_equals_the_per_tensor_entry_points(prep_runs, per_tensor_runs, dtype):
     _, res = prep_runs[dtype]
     failures, compared = [], 0
     for name in ALL_PREP:
-        single = _per_tensor(ops, name, dtype)
-        if single is None:
+        if name not in per_tensor_runs[dtype]:
             continue
         compared += 1
-        torch.cuda.synchronize()
+        _, single, got = per_tensor_runs[dtype][name]
         assert single.dtype == res[name][1].dtype
-        _collect(failures, assert_bit_equal, res[name][2], single.float().cpu(), f"{name} [{dtype}] vs its per-tensor launch")
+        _collect(failures, assert_bit_equal, res[name][2], got, f"{name} [{dtype}] vs its per-tensor launch")
     assert compared == sum(c["kind"] != "vec" for c in X.PREP_CASES)
     _report(failures)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_per_tensor_prep_bit_equal_to_the_reference(per_tensor_runs, dtype):
+    """rho_prep_conv_weight / _dgrad / _phase / _sel (k_prep_one) on every case with such an entry point, judged by the CPU
+    reference itself (the batched launch shares their code, so agreeing with it proves nothing): both walks, ragged 64-groups on
+    either axis, a second trip of the LDS walk at 3 taps (fwd_t3: 64 rows x 2 groups = 128 units on the 72 / 60 blocks of one
+    output element per thread) and blocks with no unit at 27, and the row table with fewer rows than the parameter (qkv /
+    holes).  Outputs through ``out=`` views of guarded buffers."""
+    res = per_tensor_runs[dtype]
+    assert len(res) == len(PER_TENSOR_PREP) >= 40
+    for name, more_units in (("fwd_t3", True), ("fwd_t27", False)):       # the launch's blocks: ceil(total / 256), at most 2048
+        g = X.prep_geometry(X.prep_io(name, dtype))
+        assert g["lds"] and (g["units"] > min(-(-g["total"] // 256), 2048)) == more_units, name
+    failures = []
+    for name in PER_TENSOR_PREP:
+        flat, _, got = res[name]
+        _collect(failures, assert_bit_equal, got, X.prep_io(name, dtype)["ref"], f"{name} [{dtype}] per-tensor")
+        if not guards_intact(flat):
+            failures.append(f"{name} [{dtype}] per-tensor: a store outside the output")
+    _report(failures)
+
+
+def test_prep_functions_allocate_the_prepared_shape(ops):
+    """The stand-alone functions without ``out``: the shape rules give the case table's shapes, the values the reference's."""
+    td = torch.bfloat16
+    for name, call in (("fwd_t9", lambda w, c: ops.prep_conv_weight(w, td)), ("dgrad_t9", lambda w, c: ops.prep_conv_weight_dgrad(w, td)),
+                       ("phase_333_12_dgrad", lambda w, c: ops.prep_conv_weight_phase(w, td, c["ph"], dgrad=True)),
+                       ("sel_01", lambda w, c: ops.prep_conv_weight_sel(w, td, c["sel"]))):
+        io = X.prep_io(name, "bf16")
+        got = call(io["w"].to(DEV), io["case"])
+        assert got.dtype == td
+        assert_bit_equal(got.float().cpu(), io["ref"], f"{name} through the function")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -276,6 +290,43 @@ def test_wfin_batch_one_op_table(ops, name):
     io, table, grads, arena, _ = _wfin_launch(ops, (name,))
     assert len(table.entries) == 1
     _wfin_check(io, grads, arena, "alone")
+
+
+@pytest.mark.parametrize("accumulate", [0, 1])
+def test_per_tensor_wgrad_finalize_bit_equal_to_the_reference(ops, accumulate):
+    """rho_wgrad_finalize (k_wfin_one) on every kind-0 case, judged by ref_wfin: accumulate = 1 adds the buffer to the prefilled
+    gradient; accumulate = 0 stores it - the reference run on a zero gradient where the op writes, the prefill kept on the rows a row
+    table with holes skips."""
+    io = X.wfin_io(ALL_WFIN)
+    arena = io["arena"].to(DEV)
+    failures, n = [], 0
+    for op in io["ops"]:
+        c = op["case"]
+        if c["kind"] != 0:
+            continue
+        n += 1
+        taps = math.prod(c["k"])
+        rs = op["rs"].to(DEV) if op["rs"] is not None else None
+        flat, g = guarded_copy(op["grad0"], torch.float32)
+        base = arena[op["off"] + c.get("off_extra", 0):]
+        ops.wgrad_finalize(base[:taps * c["coutp"] * c["cinb"]].view(taps, c["coutp"], c["cinb"]), g, rs, accumulate=bool(accumulate))
+        torch.cuda.synchronize()
+        want = op["ref"]
+        if not accumulate:
+            region = io["arena"][op["off"]:op["off"] + X.wfin_region_floats(c)]
+            written = X.ref_wfin(c, region, torch.zeros_like(op["grad0"]), op["rs"])
+            rows = torch.zeros(c["cout"], dtype=torch.bool)
+            for r in range(c["cout"]):
+                d = X._src_row(op["rs"], r, c["cout"])
+                if d >= 0:
+                    rows[d] = True
+            assert bool(rows.all()) == (c.get("rs") != "holes"), c["name"]
+            want = torch.where(rows.view(-1, *[1] * (op["grad0"].dim() - 1)), written, op["grad0"])
+        _collect(failures, assert_bit_equal, g.cpu(), want, f"{c['name']} accumulate={accumulate}")
+        if not guards_intact(flat):
+            failures.append(f"{c['name']} accumulate={accumulate}: a store outside the gradient")
+    assert n == sum(c["kind"] == 0 for c in X.WFIN_CASES) >= 12
+    _report(failures)
 
 
 def test_wfin_batch_equals_the_per_tensor_finalize(ops):

@@ -227,6 +227,29 @@ def prep_io(name: str, dtype: str) -> dict:
     return io
 
 
+def prep_into(sink, names, dtype: str, alloc, device="cpu") -> dict:
+    """The ops ``names`` into ``sink`` - anything with the add_fwd / add_dgrad / add_phase / add_sel / add_vec methods of ops.PrepTable -
+    with operands on ``device`` and each output from ``alloc(shape, torch dtype) -> (flat, view)``;  -> {name: (flat, view)}."""
+    outs = {}
+    for name in names:
+        io = prep_io(name, dtype)
+        c, w = io["case"], io["w"].to(device)
+        perm = io["perm"].to(device) if io["perm"] is not None else None
+        flat, out = alloc(io["out_shape"], TORCH_DTYPE[io["out_dtype"]])
+        if c["kind"] == "fwd":
+            sink.add_fwd(w, out, perm, k=c.get("k"))
+        elif c["kind"] == "dgrad":
+            sink.add_dgrad(w, out, perm)
+        elif c["kind"] == "phase":
+            sink.add_phase(w, out, c["ph"], dgrad=c["dgrad"])
+        elif c["kind"] == "sel":
+            sink.add_sel(w, out, c["sel"], flip_d=c["flip_d"], dgrad=c["dgrad"])
+        else:
+            sink.add_vec(w.reshape(-1), out, perm=perm, n=io["n"])
+        outs[name] = (flat, out)
+    return outs
+
+
 def prep_geometry(io: dict, max_blocks: int = 2048) -> dict:
     """The launch geometry PrepTable gives the op: nblk blocks, and on the LDS path (FWD / DGRAD, 1 < taps <= 32) the units they walk."""
     total = math.prod(io["out_shape"])
